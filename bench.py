@@ -20,7 +20,12 @@ encode -> channel -> decode round trip). `value` is units / the bracketed time o
 the median step ("median of >= 5") is reported next to it, and extras.all_clean_variant is C4's
 "all-clean variant": the same 64 x 1000 captures straight from the modulator.
 
-Also reported (same run, outside the timed steps): the reference `opv-demod -s -r -q` itself timed on the host
+A plain run (the command above) does only what the headline needs: it generates the workload, runs the warm-up steps,
+times the K steps and prints the line (metric, value, ms_per_step, the median step, config); with --dump-outputs DIR it
+also writes what the last timed step decoded as DIR/*.npy (see dump_outputs). The decode check above, the per-kernel
+times, the roofline, the CPU baseline and the extras below run only under --full.
+
+Also reported under --full (same run, outside the timed steps): the reference `opv-demod -s -r -q` itself timed on the host
 (cpu_baseline.kind = "reference") when the prebuilt oracle/_ref binary travelled with the snapshot, else the C oracle
 ("port") - always - and the EXTRAS: configs[1] (ONE clean 1000-frame stream), the all-clean variant, a many-short-streams
 sweep that shows the throughput-bound regime, configs[4]'s whole workload on one GPU, 32 768 unique streams, the
@@ -45,6 +50,9 @@ sys.path.insert(0, str(ROOT))
 FRAME_SAMPLES = 86720
 ALGO_BYTES_PER_SAMPLE = 4.0 + 134.0 / FRAME_SAMPLES  # 4 B in + 134 B / frame out
 HBM_PEAK_GBS = 8000.0                                 # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_FRAMES_BYTES = 40 << 20                         # --dump-outputs: frames.npy (float32) beyond this is a seeded sample of rows
+DUMP_METRICS_BYTES = 4 << 20                         # ... and viterbi_metric.npy (float64); counts.npy is always whole
+DUMP_SEED = 20240611
 
 
 def load_amd():
@@ -269,6 +277,43 @@ def cpu_all_cores(iq_bytes, n_samples):
                                     f"{sum(len(o) for o in outs) // 134} frames out)"}
 
 
+def _rows_or_sample(a, limit_bytes):
+    """a [streams, frames, ...] -> (a itself, None) when it fits in limit_bytes, else (a fixed, seeded sample of its
+    [stream, frame] rows, their flat indices stream * frames + frame)"""
+    rows = a.reshape(a.shape[0] * a.shape[1], -1)
+    if a.nbytes <= limit_bytes:
+        return a, None
+    k = max(1, limit_bytes // rows[0].nbytes)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], k, replace=False))
+    return rows[idx], idx
+
+
+def dump_outputs(out_dir, frames, counts, metrics):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<name>.npy (about 50 MB at most).
+    frames [streams, cap, 134] uint8 and counts [streams] int32: the library's frame buffer (with N > 1 ranks: rank 0's
+    gathered buffer, global stream order); metrics [own streams, cap] int32: the Viterbi metric of every frame rank 0
+    decoded. Written up to the largest count; slots a stream did not release are zero. frames.npy is float32
+    [streams, frames, 134] and viterbi_metric.npy float64 [streams, frames]; an array larger than its share is replaced by
+    a seeded sample of its rows ([rows, 134] / [rows]) with the flat row indices in frames_rows.npy / viterbi_metric_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    counts = counts.astype(np.int64)
+    nmax = int(counts.max()) if counts.size else 0
+    fr = frames[:, :nmax].astype(np.float32)
+    me = metrics[:, :nmax].astype(np.float64)
+    fr[~(np.arange(nmax)[None, :] < counts[:, None])] = 0.0
+    me[~(np.arange(nmax)[None, :] < counts[: len(me), None])] = 0.0
+    arrays = {"counts": counts.astype(np.float64)}
+    arrays["frames"], idx = _rows_or_sample(fr, DUMP_FRAMES_BYTES)
+    if idx is not None:
+        arrays["frames_rows"] = idx.astype(np.float64)
+    me, idx = _rows_or_sample(me, DUMP_METRICS_BYTES)
+    arrays["viterbi_metric"] = me.reshape(-1) if idx is not None else me
+    if idx is not None:
+        arrays["viterbi_metric_rows"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -277,11 +322,17 @@ def main():
     ap.add_argument("--streams", type=int, default=64, help="streams per GPU")
     ap.add_argument("--frames", type=int, default=1000, help="frames per stream")
     ap.add_argument("--ebn0", type=float, default=16.0, help="dB; <=0 disables noise")
-    ap.add_argument("--no-extras", action="store_true", help="skip configs[1], the sweep and the CPU baseline")
-    ap.add_argument("--no-big", action="store_true", help="skip the 512-stream x F-frame single-GPU run of the extras (178 GB of HBM)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip configs[1], the sweep and the CPU baseline")
+    ap.add_argument("--no-big", action="store_true", help="with --full: skip the 512-stream x F-frame single-GPU run of the extras (178 GB of HBM)")
     ap.add_argument("--extras-budget", type=float, default=75.0,
-                    help="wall-clock seconds for everything beyond the contract's line (the extras, in a fixed order of priority; "
+                    help="with --full: wall-clock seconds for everything beyond the contract's line (the extras, in a fixed order of priority; "
                          "what does not fit is listed in extras.skipped_for_budget)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the decode check, per-kernel times, roofline, CPU baseline and (unless --no-extras) "
+                         "the extras; a plain run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one decoded (frames, counts, Viterbi metrics) as DIR/<name>.npy; "
+                         "the inputs are the same for the same arguments")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -346,12 +397,11 @@ def main():
     gen_t = {}
     d_iq, tx_all, n = workload.generate(amd, dm, torch, dev, mine, F, args.ebn0, timing=gen_t)
     t_mod = gen_t["generate_s"]                          # BERT frames + device transmit chain + channel tool, all streams (allocation excluded)
-    tx_frames = amd.bert_frames(F)                       # configs[1] / CPU-baseline capture (W5NYV)
 
     frames_view, counts_view = workload.frame_views(dm, torch, dev)
     fcap = frames_view.shape[1]
     gathered = {}
-    expect = torch.from_numpy(tx_all).to(dev)
+    expect = torch.from_numpy(tx_all).to(dev) if args.full else None     # (what the decode check of --full compares with)
 
     stats = {}
 
@@ -386,151 +436,39 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        step()
-    dm.enable_timing(True)
+        step(check=args.full)
+    if args.full:
+        dm.enable_timing(True)                            # HIP events around the four kernels: kernel_ms and the roofline
     kt = []
     barrier()
     t0 = time.perf_counter()
     marks = [t0]
     for _ in range(args.steps):
         step(check=False)
-        kt.append(dm.kernel_times())
+        if args.full:
+            kt.append(dm.kernel_times())
         marks.append(time.perf_counter())                 # (every step ends in opv_sync, and in the gather when N > 1)
     barrier()
     dt = time.perf_counter() - t0
     step_s = np.diff(np.array(marks))
-    step(check=True)                                      # untimed: the timed configuration decodes correctly
-    fe_kernel = dm.frontend_kernel()                      # what opv_process actually launched for this stream count
-    # the two input classes the product reports instead of reproducing (include/opv_demod.h: edge_ties, offset_ties)
-    states = [dm.state(k) for k in range(S)]
-    stats["edge_ties"] = int(sum(st.edge_ties for st in states))
-    stats["offset_ties"] = int(sum(st.offset_ties for st in states))
-    # live issue view of the dominant kernel: every wave times itself (s_memtime / s_memrealtime, opv_tap_wave_info)
-    wi = [dm.wave_info(k) for k in range(S)]
-    cyc = np.array([w[2] for w in wi], np.float64)
-    tick = np.array([w[3] for w in wi], np.float64)
-    syms = np.array([st.total_symbols for st in states], np.float64)
-    per_wave = 16.0 if "_x16" in fe_kernel else 4.0 if "_x4" in fe_kernel else 1.0   # streams sharing a wave (k_frontend_x4.hip, k_frontend_x16.hip)
-    live_cps = float(np.median(cyc / np.maximum(syms * per_wave, 1.0))) if cyc.min() > 0 else None
-    live_clock = float(np.median(cyc / np.maximum(tick, 1.0)) * 100e6) if tick.min() > 0 else None
-    collective = None
-    if use_dist:
+    if args.dump_outputs and rank == 0:                   # what the last timed step handed its caller, before anything else runs
+        _f, m_ptr, _c, _cap = dm.device_frames()
+        metrics = torch.as_tensor(DevPtr(m_ptr, (S, fcap), "<i4"), device=dev).cpu().numpy()
+        if use_dist:
+            g_fr, g_cnt = gathered["frames"], gathered["counts"]
+            dump_outputs(args.dump_outputs, g_fr.reshape(-1, fcap, 134).cpu().numpy(), g_cnt.reshape(-1).cpu().numpy(), metrics)
+        else:
+            dump_outputs(args.dump_outputs, frames_view.cpu().numpy(), counts_view.cpu().numpy(), metrics)
+    if use_dist:                                          # the job's time is its slowest rank's (value is a whole-job figure)
         t = torch.tensor([dt], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         ts = torch.tensor(step_s, dtype=torch.float64, device=t.device)
         dist.all_reduce(ts, op=dist.ReduceOp.MAX)          # step k of the job = its slowest rank's step k
         step_s = ts.cpu().numpy()
-        # what every rank says it owned: [first global stream, one past the last, samples per stream, frames released]
-        own = torch.tensor([mine.start, mine.stop, n, int(counts_view.sum().item())], dtype=torch.int64, device=t.device)
-        owned = [torch.empty_like(own) for _ in range(world)] if rank == 0 else None
-        dist.gather(own, owned, dst=0)
-        if rank == 0:
-            g = gathered["frames"]                       # [world, S, fcap, 134] in global stream order
-            assert bool((g[0].to(dev) == frames_view).all().item()), "gathered frames of rank 0 differ from the local ones"
-            stats["gathered_equals_local_view"] = True
-            collective = {"backend": dist.get_backend(), "world": world, "gathered_shape": list(g.shape),
-                          "bytes_per_rank": int(frames_view.numel() + 4 * counts_view.numel()),
-                          "op": "one dist.gather of the [S, cap, 134] frame buffer + one of the [S] counts per step "
-                                "(zero-copy views of library memory), MAX all-reduce of the step time"}
-            assert bool((gathered["counts"] == F).all().item()), "a gathered stream released a wrong number of frames"
-            exp_all = np.stack([np.stack([workload.tx_frames(amd, gk, F) for gk in sharding.stream_range(r, world, world * S)])
-                                for r in range(world)])
-            same = (g[:, :, :F, :].cpu().numpy() == exp_all).all(axis=3)
-            stats["gathered_frames_total"] = int(same.size)
-            stats["gathered_frames_exact"] = int(same.sum())
-            # who sent what, read back from the gathered bytes themselves: the Base-40 callsign of every stream's
-            # first frame is S<global id> (workload.stream_params), so a rank that decoded a second copy of
-            # another rank's shard shows up here (and in exp_all above)
-            collective["rank_shards"] = [[int(o[0]), int(o[1])] for o in owned]
-            collective["rank_frames_released"] = [int(o[3]) for o in owned]
-            collective["gathered_callsigns"] = [amd.callsign_of(g[r, k, 0].cpu().numpy()) for r in range(world) for k in range(S)]
-            assert same.mean() > 0.99, "frames gathered from the other ranks do not match what they were sent"
-
     total_samples = float(world) * S * n * args.steps
     msps = total_samples / dt / 1e6
     med_s = float(np.median(step_s))
-    fe_ms = float(np.mean([k["msk_frontend"] for k in kt]))
-    launch_samples = float(S) * n
-    achieved = launch_samples * ALGO_BYTES_PER_SAMPLE / (fe_ms * 1e-3) / 1e9
-
-    # HBM bytes and instruction counts of the dominant kernel come from separate rocprofv3 --pmc passes (bench.py
-    # cannot profile itself); they are attached only when the stored profile is of THIS kernel and configuration.
-    # Cycles per symbol and the clock are measured live in every run (above); a stored profile whose cycles differ
-    # from the live ones by more than 3 % is flagged as stale.
-    n_sym = float(syms.sum())
-    traffic = None
-    traffic_note = "no PMC passes recorded for this kernel / configuration (see profiles/collect.sh)"
-    issue = {"wave_cycles_per_symbol": round(live_cps, 1) if live_cps else None,
-             "clock_GHz": round(live_clock / 1e9, 3) if live_clock else None,
-             "source": "live: s_memtime / s_memrealtime of every wave (opv_tap_wave_info), median over the streams"}
-    n_simd = 1024
-    waves = int(np.ceil(S / per_wave))
-    try:
-        tj = json.loads(sorted((ROOT / "profiles").glob("r[0-9][0-9]_traffic.json"))[-1].read_text())
-        w = tj["workload"]
-        if tj.get("kernel") == fe_kernel and (w["streams_per_gpu"], w["frames_per_stream"], w["ebn0"], w.get("f0_edge_hz", 1500.0)) == \
-                (S, F, args.ebn0, workload.F0_EDGE_HZ):
-            traffic = round(tj["hbm_bytes_per_launch"] / (fe_ms * 1e-3) / 1e9, 3)
-            traffic_note = tj["source"] + "; " + tj["correction"]
-            ips = tj.get("instr_per_symbol")
-            if ips:
-                per_sym = float(sum(ips.values()))
-                issue["instr_per_symbol"] = ips
-                issue["instr_source"] = "rocprofv3 SQ_INSTS_* pass of the same kernel and workload (" + tj["source"].split(";")[0] + ")"
-                stored = tj.get("wave_cycles_per_symbol")
-                if stored and live_cps:
-                    issue["profile_wave_cycles_per_symbol"] = stored
-                    issue["profile_stale"] = bool(abs(stored - live_cps) > 0.03 * live_cps)
-                if live_cps:
-                    # a wave-instruction occupies its SIMD's issue port for 4 cycles (MI355X_MICROARCH.md, 'vector-instruction
-                    # ISSUE cost', one wave per SIMD): the fraction of its own SIMD's slots a stream's wave fills ...
-                    issue["wave_issue_frac"] = round(per_sym * per_wave * 4.0 / (live_cps * per_wave), 3)
-                    # ... and the same over the whole chip for the duration of the kernel
-                    slots = n_simd * (fe_ms * 1e-3) * (live_clock or 2.4e9) / 4.0
-                    issue["chip_issue_frac"] = round(per_sym * n_sym / slots, 4)
-    except Exception:
-        pass
-    issue["waves"] = waves
-    issue["simds"] = n_simd
-    issue["note"] = ("wave_issue_frac: issued wave-instructions x 4 cycles / the wave's own cycles; chip_issue_frac: issued "
-                     "wave-instructions / (1024 SIMDs x kernel cycles / 4)")
-    # fp64 vector view: the REFERENCE formulation's arithmetic, ~150 flop per sample (2 sincos + 3 complex
-    # lerps + 6 complex MACs), at the rate this kernel demodulates, against the fp64 vector peak (AMD spec 78.6 TFLOP/s =
-    # half the fp32 vector peak of MI355X_MICROARCH.md). The kernel itself issues far fewer (no sincos, 60 lerps for 120).
-    FP64_PEAK_TF, ALGO_FLOP_PER_SAMPLE = 78.6, 150.0
-    fp64_tf = launch_samples * ALGO_FLOP_PER_SAMPLE / (fe_ms * 1e-3) / 1e12
-    fp64_view = {"bound": "fp64-valu", "algorithmic_flop_per_sample": ALGO_FLOP_PER_SAMPLE, "achieved": round(fp64_tf, 3),
-                 "peak": FP64_PEAK_TF, "unit": "TFLOP/s", "frac": round(fp64_tf / FP64_PEAK_TF, 5)}
-    # The bound that actually binds (the HBM figure above it is the contract's): with at most one wave per SIMD a stream's
-    # wave owns an issue port that takes one wave-instruction per 4 cycles, and the per-symbol feedback recurrence keeps
-    # every symbol's instructions on that one port - frac = issued instructions x 4 / the wave's cycles; once every SIMD
-    # carries stream waves the same count is taken against all 1024 ports for the duration of the kernel.
-    if waves <= n_simd:
-        binding = {"bound": "wave-issue", "frac": issue.get("wave_issue_frac"),
-                   "achieved": round(4.0 * sum(issue["instr_per_symbol"].values()), 1) if "instr_per_symbol" in issue else None,
-                   "peak": issue["wave_cycles_per_symbol"], "unit": "cycles per symbol (issuing / elapsed, one wave on its SIMD)",
-                   "waves": waves, "simds": n_simd}
-    else:
-        binding = {"bound": "chip-issue", "frac": issue.get("chip_issue_frac"), "achieved": None, "peak": None,
-                   "unit": "issued wave-instructions / (1024 SIMDs x kernel cycles / 4)", "waves": waves, "simds": n_simd}
-    binding["note"] = ("frac needs the SQ_INSTS_* pass of this kernel and workload (profiles/collect.sh); null when the stored profile "
-                       "is of another kernel or configuration") if binding["frac"] is None else \
-                      "instruction counts from the stored rocprofv3 pass (roofline.issue.instr_source), cycles measured live in this run"
-    if waves <= n_simd:
-        regime = (f"issue/latency-bound per-symbol feedback recurrence: {waves} waves on {n_simd} SIMDs "
-                  f"({100.0 * waves / n_simd:.1f} % of the chip's issue ports can be used at all), not bandwidth (DESIGN.md §3.1)")
-    else:
-        regime = f"{waves} waves on {n_simd} SIMDs: every SIMD carries a stream wave, the kernel is at the chip's issue capacity"
-
-    # the bound that binds FIRST in the note: a record that keeps only the note's head still says why 0.4 % of HBM is not the story
-    if binding["frac"] is not None and binding["bound"] == "wave-issue":
-        binding_head = f"binding=wave-issue {binding['frac']:.3f} ({binding['achieved'] / 4.0:.0f} instr x 4 / {binding['peak']:.1f} cyc); "
-    elif binding["frac"] is not None:
-        binding_head = f"binding=chip-issue {binding['frac']:.3f} (issued wave-instructions / (1024 SIMDs x kernel cycles / 4)); "
-    else:
-        binding_head = f"binding={binding['bound']} n/a (no SQ_INSTS pass stored for this kernel / workload); "
-
     out = {
         "metric": "IQ Msamples/s demod+Viterbi (×real-time @2.168MSPS); BER vs ref",
         "value": round(msps, 3), "unit": "Msamples/s", "x_realtime": round(msps / 2.168, 1),
@@ -548,320 +486,447 @@ def main():
                                (f"; x{world} GPUs = configs[4] shape, RCCL gather of frames to rank 0" if world > 1 else ""),
                    "streams_per_gpu": S, "frames_per_stream": F, "samples_per_stream": n,
                    "parallelism": f"streams sharded {S}/GPU, no data-path collective"},
-        "frames_checked": f"rank0: {stats.get('frames_exact')}/{stats.get('frames_total')} decoded frames equal the "
-                          f"transmitted bytes (rest = channel errors at {args.ebn0:g} dB); GPU==reference parity is tests/",
-        "roofline": {"bound": "hbm", "kernel": fe_kernel, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                     "traffic_note": traffic_note,
-                     "binding": binding,
-                     "issue": issue,
-                     "fp64_valu": fp64_view,
-                     "kernel_ms": round(fe_ms, 3),
-                     "note": binding_head + regime + "; extras.stream_sweep shows the front-end with the chip filled"},
-        "kernel_ms": {k: round(float(np.mean([x[k] for x in kt])), 3) for k in kt[0]},
-        "check": stats,
     }
-    if collective:
-        out["collective"] = collective
-    # what a timed step spends outside the four kernels: opv_reset_stream (two stream syncs, a 90 KB upload, a
-    # metrics fill), 64 opv_attach calls, the launches, and the frame gather when N > 1
-    out["non_kernel_ms_per_step"] = round(out["ms_per_step"] - sum(out["kernel_ms"].values()), 3)
+    if args.full:
+        step(check=True)                                      # untimed: the timed configuration decodes correctly
+        fe_kernel = dm.frontend_kernel()                      # what opv_process actually launched for this stream count
+        # the two input classes the product reports instead of reproducing (include/opv_demod.h: edge_ties, offset_ties)
+        states = [dm.state(k) for k in range(S)]
+        stats["edge_ties"] = int(sum(st.edge_ties for st in states))
+        stats["offset_ties"] = int(sum(st.offset_ties for st in states))
+        # live issue view of the dominant kernel: every wave times itself (s_memtime / s_memrealtime, opv_tap_wave_info)
+        wi = [dm.wave_info(k) for k in range(S)]
+        cyc = np.array([w[2] for w in wi], np.float64)
+        tick = np.array([w[3] for w in wi], np.float64)
+        syms = np.array([st.total_symbols for st in states], np.float64)
+        per_wave = 16.0 if "_x16" in fe_kernel else 4.0 if "_x4" in fe_kernel else 1.0   # streams sharing a wave (k_frontend_x4.hip, k_frontend_x16.hip)
+        live_cps = float(np.median(cyc / np.maximum(syms * per_wave, 1.0))) if cyc.min() > 0 else None
+        live_clock = float(np.median(cyc / np.maximum(tick, 1.0)) * 100e6) if tick.min() > 0 else None
+        collective = None
+        if use_dist:
+            # what every rank says it owned: [first global stream, one past the last, samples per stream, frames released]
+            own = torch.tensor([mine.start, mine.stop, n, int(counts_view.sum().item())], dtype=torch.int64, device=t.device)
+            owned = [torch.empty_like(own) for _ in range(world)] if rank == 0 else None
+            dist.gather(own, owned, dst=0)
+            if rank == 0:
+                g = gathered["frames"]                       # [world, S, fcap, 134] in global stream order
+                assert bool((g[0].to(dev) == frames_view).all().item()), "gathered frames of rank 0 differ from the local ones"
+                stats["gathered_equals_local_view"] = True
+                collective = {"backend": dist.get_backend(), "world": world, "gathered_shape": list(g.shape),
+                              "bytes_per_rank": int(frames_view.numel() + 4 * counts_view.numel()),
+                              "op": "one dist.gather of the [S, cap, 134] frame buffer + one of the [S] counts per step "
+                                    "(zero-copy views of library memory), MAX all-reduce of the step time"}
+                assert bool((gathered["counts"] == F).all().item()), "a gathered stream released a wrong number of frames"
+                exp_all = np.stack([np.stack([workload.tx_frames(amd, gk, F) for gk in sharding.stream_range(r, world, world * S)])
+                                    for r in range(world)])
+                same = (g[:, :, :F, :].cpu().numpy() == exp_all).all(axis=3)
+                stats["gathered_frames_total"] = int(same.size)
+                stats["gathered_frames_exact"] = int(same.sum())
+                # who sent what, read back from the gathered bytes themselves: the Base-40 callsign of every stream's
+                # first frame is S<global id> (workload.stream_params), so a rank that decoded a second copy of
+                # another rank's shard shows up here (and in exp_all above)
+                collective["rank_shards"] = [[int(o[0]), int(o[1])] for o in owned]
+                collective["rank_frames_released"] = [int(o[3]) for o in owned]
+                collective["gathered_callsigns"] = [amd.callsign_of(g[r, k, 0].cpu().numpy()) for r in range(world) for k in range(S)]
+                assert same.mean() > 0.99, "frames gathered from the other ranks do not match what they were sent"
 
-    if rank == 0 and not args.no_extras and world == 1:
-        extras = {}
-        budget = Budget(args.extras_budget)
+        fe_ms = float(np.mean([k["msk_frontend"] for k in kt]))
+        launch_samples = float(S) * n
+        achieved = launch_samples * ALGO_BYTES_PER_SAMPLE / (fe_ms * 1e-3) / 1e9
 
-        def put(key, est_s, fn):
-            r = budget.run(key, est_s, fn)
-            if r is not None:
-                extras[key] = r
-        # the clean 1000-frame capture of configs[1] (W5NYV), made on the device: the CPU baseline's input as well
-        one = amd.Demod(1, max_samples=n + 64, streaming=True, device=dev_index)
-        d_base = torch.empty(2 * n, dtype=torch.int16, device=dev)
-        t0 = time.perf_counter()
-        one.modulate_device(tx_frames, d_base.data_ptr())
-        one.sync()
-        t_dev_mod = time.perf_counter() - t0
-        raw = d_base.cpu().numpy().tobytes()
-        # the contract's cpu_baseline: not optional, only accounted for
-        t0 = time.perf_counter()
-        out["cpu_baseline"] = cpu_baseline(raw, n)
-        budget.spent["cpu_baseline"] = round(time.perf_counter() - t0, 1)
+        # HBM bytes and instruction counts of the dominant kernel come from separate rocprofv3 --pmc passes (bench.py
+        # cannot profile itself); they are attached only when the stored profile is of THIS kernel and configuration.
+        # Cycles per symbol and the clock are measured live in every --full run (above); a stored profile whose cycles differ
+        # from the live ones by more than 3 % is flagged as stale.
+        n_sym = float(syms.sum())
+        traffic = None
+        traffic_note = "no PMC passes recorded for this kernel / configuration (see profiles/collect.sh)"
+        issue = {"wave_cycles_per_symbol": round(live_cps, 1) if live_cps else None,
+                 "clock_GHz": round(live_clock / 1e9, 3) if live_clock else None,
+                 "source": "live: s_memtime / s_memrealtime of every wave (opv_tap_wave_info), median over the streams"}
+        n_simd = 1024
+        waves = int(np.ceil(S / per_wave))
+        try:
+            tj = json.loads(sorted((ROOT / "profiles").glob("r[0-9][0-9]_traffic.json"))[-1].read_text())
+            w = tj["workload"]
+            if tj.get("kernel") == fe_kernel and (w["streams_per_gpu"], w["frames_per_stream"], w["ebn0"], w.get("f0_edge_hz", 1500.0)) == \
+                    (S, F, args.ebn0, workload.F0_EDGE_HZ):
+                traffic = round(tj["hbm_bytes_per_launch"] / (fe_ms * 1e-3) / 1e9, 3)
+                traffic_note = tj["source"] + "; " + tj["correction"]
+                ips = tj.get("instr_per_symbol")
+                if ips:
+                    per_sym = float(sum(ips.values()))
+                    issue["instr_per_symbol"] = ips
+                    issue["instr_source"] = "rocprofv3 SQ_INSTS_* pass of the same kernel and workload (" + tj["source"].split(";")[0] + ")"
+                    stored = tj.get("wave_cycles_per_symbol")
+                    if stored and live_cps:
+                        issue["profile_wave_cycles_per_symbol"] = stored
+                        issue["profile_stale"] = bool(abs(stored - live_cps) > 0.03 * live_cps)
+                    if live_cps:
+                        # a wave-instruction occupies its SIMD's issue port for 4 cycles (MI355X_MICROARCH.md, 'vector-instruction
+                        # ISSUE cost', one wave per SIMD): the fraction of its own SIMD's slots a stream's wave fills ...
+                        issue["wave_issue_frac"] = round(per_sym * per_wave * 4.0 / (live_cps * per_wave), 3)
+                        # ... and the same over the whole chip for the duration of the kernel
+                        slots = n_simd * (fe_ms * 1e-3) * (live_clock or 2.4e9) / 4.0
+                        issue["chip_issue_frac"] = round(per_sym * n_sym / slots, 4)
+        except Exception:
+            pass
+        issue["waves"] = waves
+        issue["simds"] = n_simd
+        issue["note"] = ("wave_issue_frac: issued wave-instructions x 4 cycles / the wave's own cycles; chip_issue_frac: issued "
+                         "wave-instructions / (1024 SIMDs x kernel cycles / 4)")
+        # fp64 vector view: the REFERENCE formulation's arithmetic, ~150 flop per sample (2 sincos + 3 complex
+        # lerps + 6 complex MACs), at the rate this kernel demodulates, against the fp64 vector peak (AMD spec 78.6 TFLOP/s =
+        # half the fp32 vector peak of MI355X_MICROARCH.md). The kernel itself issues far fewer (no sincos, 60 lerps for 120).
+        FP64_PEAK_TF, ALGO_FLOP_PER_SAMPLE = 78.6, 150.0
+        fp64_tf = launch_samples * ALGO_FLOP_PER_SAMPLE / (fe_ms * 1e-3) / 1e12
+        fp64_view = {"bound": "fp64-valu", "algorithmic_flop_per_sample": ALGO_FLOP_PER_SAMPLE, "achieved": round(fp64_tf, 3),
+                     "peak": FP64_PEAK_TF, "unit": "TFLOP/s", "frac": round(fp64_tf / FP64_PEAK_TF, 5)}
+        # The bound that actually binds (the HBM figure above it is the contract's): with at most one wave per SIMD a stream's
+        # wave owns an issue port that takes one wave-instruction per 4 cycles, and the per-symbol feedback recurrence keeps
+        # every symbol's instructions on that one port - frac = issued instructions x 4 / the wave's cycles; once every SIMD
+        # carries stream waves the same count is taken against all 1024 ports for the duration of the kernel.
+        if waves <= n_simd:
+            binding = {"bound": "wave-issue", "frac": issue.get("wave_issue_frac"),
+                       "achieved": round(4.0 * sum(issue["instr_per_symbol"].values()), 1) if "instr_per_symbol" in issue else None,
+                       "peak": issue["wave_cycles_per_symbol"], "unit": "cycles per symbol (issuing / elapsed, one wave on its SIMD)",
+                       "waves": waves, "simds": n_simd}
+        else:
+            binding = {"bound": "chip-issue", "frac": issue.get("chip_issue_frac"), "achieved": None, "peak": None,
+                       "unit": "issued wave-instructions / (1024 SIMDs x kernel cycles / 4)", "waves": waves, "simds": n_simd}
+        binding["note"] = ("frac needs the SQ_INSTS_* pass of this kernel and workload (profiles/collect.sh); null when the stored profile "
+                           "is of another kernel or configuration") if binding["frac"] is None else \
+                          "instruction counts from the stored rocprofv3 pass (roofline.issue.instr_source), cycles measured live in this run"
+        if waves <= n_simd:
+            regime = (f"issue/latency-bound per-symbol feedback recurrence: {waves} waves on {n_simd} SIMDs "
+                      f"({100.0 * waves / n_simd:.1f} % of the chip's issue ports can be used at all), not bandwidth (DESIGN.md §3.1)")
+        else:
+            regime = f"{waves} waves on {n_simd} SIMDs: every SIMD carries a stream wave, the kernel is at the chip's issue capacity"
 
-        def x_configs1():                                # configs[1]: one clean 1000-frame stream
-            for rep in range(2):
-                one.reset()
-                one.attach(0, d_base.data_ptr(), n, eof=True)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                one.process()
-                one.sync()
-                t1 = time.perf_counter() - t0
-            fr, meta = one.pop_frames(0)
-            assert np.array_equal(fr, tx_frames), "configs[1] frames differ"
-            return {"Msamples/s": round(n / t1 / 1e6, 3), "ms": round(t1 * 1e3, 2),
-                    "frames": int(len(fr)), "all_metric_0": bool((meta["viterbi_metric"] == 0).all())}
-        put("configs1_single_clean_stream", 4.0, x_configs1)
-        one.close()
+        # the bound that binds FIRST in the note: a record that keeps only the note's head still says why 0.4 % of HBM is not the story
+        if binding["frac"] is not None and binding["bound"] == "wave-issue":
+            binding_head = f"binding=wave-issue {binding['frac']:.3f} ({binding['achieved'] / 4.0:.0f} instr x 4 / {binding['peak']:.1f} cyc); "
+        elif binding["frac"] is not None:
+            binding_head = f"binding=chip-issue {binding['frac']:.3f} (issued wave-instructions / (1024 SIMDs x kernel cycles / 4)); "
+        else:
+            binding_head = f"binding={binding['bound']} n/a (no SQ_INSTS pass stored for this kernel / workload); "
 
-        def x_all_clean():
-            # SURVEY.md §8d C4's "all-clean variant for peak throughput": the same S per-stream BERT captures exactly as the
-            # modulator emits them (full scale, no offset, no noise), same context, same step (reset, S attaches, opv_process,
-            # sync); every frame must equal the transmitted one with Viterbi metric 0
-            try:
-                d_cl, tx_cl, _n = workload.generate(amd, dm, torch, dev, mine, F, None, clean=True)
-                cl_s, cl_fe = [], []
-                for rep in range(1 + 5):
-                    dm.reset()
-                    for k in range(S):
-                        dm.attach(k, d_cl[k].data_ptr(), n, eof=True)
+        out.update({
+            "frames_checked": f"rank0: {stats.get('frames_exact')}/{stats.get('frames_total')} decoded frames equal the "
+                              f"transmitted bytes (rest = channel errors at {args.ebn0:g} dB); GPU==reference parity is tests/",
+            "roofline": {"bound": "hbm", "kernel": fe_kernel, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                         "traffic_note": traffic_note,
+                         "binding": binding,
+                         "issue": issue,
+                         "fp64_valu": fp64_view,
+                         "kernel_ms": round(fe_ms, 3),
+                         "note": binding_head + regime + "; extras.stream_sweep shows the front-end with the chip filled"},
+            "kernel_ms": {k: round(float(np.mean([x[k] for x in kt])), 3) for k in kt[0]},
+            "check": stats,
+        })
+        if collective:
+            out["collective"] = collective
+        # what a timed step spends outside the four kernels: opv_reset_stream (two stream syncs, a 90 KB upload, a
+        # metrics fill), 64 opv_attach calls, the launches, and the frame gather when N > 1
+        out["non_kernel_ms_per_step"] = round(out["ms_per_step"] - sum(out["kernel_ms"].values()), 3)
+
+        tx_frames = amd.bert_frames(F)                       # configs[1] / CPU-baseline capture (W5NYV)
+        if rank == 0 and not args.no_extras and world == 1:
+            extras = {}
+            budget = Budget(args.extras_budget)
+
+            def put(key, est_s, fn):
+                r = budget.run(key, est_s, fn)
+                if r is not None:
+                    extras[key] = r
+            # the clean 1000-frame capture of configs[1] (W5NYV), made on the device: the CPU baseline's input as well
+            one = amd.Demod(1, max_samples=n + 64, streaming=True, device=dev_index)
+            d_base = torch.empty(2 * n, dtype=torch.int16, device=dev)
+            t0 = time.perf_counter()
+            one.modulate_device(tx_frames, d_base.data_ptr())
+            one.sync()
+            t_dev_mod = time.perf_counter() - t0
+            raw = d_base.cpu().numpy().tobytes()
+            # the contract's cpu_baseline: not optional, only accounted for
+            t0 = time.perf_counter()
+            out["cpu_baseline"] = cpu_baseline(raw, n)
+            budget.spent["cpu_baseline"] = round(time.perf_counter() - t0, 1)
+
+            def x_configs1():                                # configs[1]: one clean 1000-frame stream
+                for rep in range(2):
+                    one.reset()
+                    one.attach(0, d_base.data_ptr(), n, eof=True)
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
-                    dm.process()
-                    dm.sync()
-                    if rep:                                  # (the first one is the warm-up run)
-                        cl_s.append(time.perf_counter() - t0)
-                        cl_fe.append(dm.kernel_times()["msk_frontend"])
-                exp_c = torch.from_numpy(tx_cl).to(dev)
-                cl_bad = int((frames_view[:, :F, :] != exp_c).any(dim=2).sum().item())
-                cl_cnt = bool((counts_view == F).all().item())
-                cl_states = [dm.state(k) for k in range(S)]
-                cl_med = float(np.median(cl_s))
-                res_clean = {
-                    "workload": f"{S} streams x {F} frames straight from the device modulator (amplitude 16383, no offset, no noise)",
-                    "Msamples/s": round(S * n / cl_med / 1e6, 3), "x_realtime": round(S * n / cl_med / 2.168e6, 1),
-                    "ms_per_step_median": round(cl_med * 1e3, 3), "steps": len(cl_s), "frontend_ms_median": round(float(np.median(cl_fe)), 3),
-                    "every_stream_released_all_frames": cl_cnt, "frames_exact": S * F - cl_bad, "frames_total": S * F,
-                    "frames_perfect": int(sum(st.frames_perfect for st in cl_states)),
-                    "edge_ties": int(sum(st.edge_ties for st in cl_states)), "offset_ties": int(sum(st.offset_ties for st in cl_states))}
-            finally:
-                d_cl = exp_c = None
-                torch.cuda.empty_cache()
-                step(check=False)                        # dm's frame buffer holds the contract workload's frames again (compared below)
-            assert cl_cnt and cl_bad == 0, "all-clean variant: a decoded frame differs from the transmitted one"
-            return res_clean
-        put("all_clean_variant", 8.0, x_all_clean)
-        put("cpu_baseline_all_cores", 5.0, lambda: cpu_all_cores(raw, n))
+                    one.process()
+                    one.sync()
+                    t1 = time.perf_counter() - t0
+                fr, meta = one.pop_frames(0)
+                assert np.array_equal(fr, tx_frames), "configs[1] frames differ"
+                return {"Msamples/s": round(n / t1 / 1e6, 3), "ms": round(t1 * 1e3, 2),
+                        "frames": int(len(fr)), "all_metric_0": bool((meta["viterbi_metric"] == 0).all())}
+            put("configs1_single_clean_stream", 4.0, x_configs1)
+            one.close()
 
-        def x_sweep():                                   # throughput-bound regime: many short streams carved out of the resident captures
-            sweep = {}
-            for ns, nfr in ((128, 480), (192, 320), (256, 240), (512, 120), (1024, 60), (2048, 30), (4096, 15), (8192, 7), (16384, 3)):
-                if nfr > F:
-                    continue
-                per = F // nfr
-                if S * per < ns:
-                    continue
-                sub_n = nfr * FRAME_SAMPLES
-                m = amd.Demod(ns, max_samples=sub_n + 64, streaming=True, device=dev_index)
-                m.enable_timing(True)
-                ent = {}
-                for spw in (1, 4, 16):                      # streams per wavefront (opv_set_frontend)
-                    if spw == 4 and ns < 4096:         # (the four-per-wave mapping is the automatic choice from 2049 streams on)
-                        continue
-                    if spw == 16 and ns < 4096:        # (sixteen per wave: 1024 waves = one per SIMD need 16 384 streams)
-                        continue
-                    if spw == 1 and ns > 8192:
-                        continue
-                    m.set_frontend(spw)
-                    for rep in range(2):
-                        m.reset()
-                        for j in range(ns):
-                            k, seg = j % S, j // S
-                            m.attach(j, d_iq[k].data_ptr() + 4 * seg * sub_n, sub_n, eof=True)
+            def x_all_clean():
+                # SURVEY.md §8d C4's "all-clean variant for peak throughput": the same S per-stream BERT captures exactly as the
+                # modulator emits them (full scale, no offset, no noise), same context, same step (reset, S attaches, opv_process,
+                # sync); every frame must equal the transmitted one with Viterbi metric 0
+                try:
+                    d_cl, tx_cl, _n = workload.generate(amd, dm, torch, dev, mine, F, None, clean=True)
+                    cl_s, cl_fe = [], []
+                    for rep in range(1 + 5):
+                        dm.reset()
+                        for k in range(S):
+                            dm.attach(k, d_cl[k].data_ptr(), n, eof=True)
                         torch.cuda.synchronize()
                         t0 = time.perf_counter()
-                        m.process()
-                        m.sync()
+                        dm.process()
+                        dm.sync()
+                        if rep:                                  # (the first one is the warm-up run)
+                            cl_s.append(time.perf_counter() - t0)
+                            cl_fe.append(dm.kernel_times()["msk_frontend"])
+                    exp_c = torch.from_numpy(tx_cl).to(dev)
+                    cl_bad = int((frames_view[:, :F, :] != exp_c).any(dim=2).sum().item())
+                    cl_cnt = bool((counts_view == F).all().item())
+                    cl_states = [dm.state(k) for k in range(S)]
+                    cl_med = float(np.median(cl_s))
+                    res_clean = {
+                        "workload": f"{S} streams x {F} frames straight from the device modulator (amplitude 16383, no offset, no noise)",
+                        "Msamples/s": round(S * n / cl_med / 1e6, 3), "x_realtime": round(S * n / cl_med / 2.168e6, 1),
+                        "ms_per_step_median": round(cl_med * 1e3, 3), "steps": len(cl_s), "frontend_ms_median": round(float(np.median(cl_fe)), 3),
+                        "every_stream_released_all_frames": cl_cnt, "frames_exact": S * F - cl_bad, "frames_total": S * F,
+                        "frames_perfect": int(sum(st.frames_perfect for st in cl_states)),
+                        "edge_ties": int(sum(st.edge_ties for st in cl_states)), "offset_ties": int(sum(st.offset_ties for st in cl_states))}
+                finally:
+                    d_cl = exp_c = None
+                    torch.cuda.empty_cache()
+                    step(check=False)                        # dm's frame buffer holds the contract workload's frames again (compared below)
+                assert cl_cnt and cl_bad == 0, "all-clean variant: a decoded frame differs from the transmitted one"
+                return res_clean
+            put("all_clean_variant", 8.0, x_all_clean)
+            put("cpu_baseline_all_cores", 5.0, lambda: cpu_all_cores(raw, n))
+
+            def x_sweep():                                   # throughput-bound regime: many short streams carved out of the resident captures
+                sweep = {}
+                for ns, nfr in ((128, 480), (192, 320), (256, 240), (512, 120), (1024, 60), (2048, 30), (4096, 15), (8192, 7), (16384, 3)):
+                    if nfr > F:
+                        continue
+                    per = F // nfr
+                    if S * per < ns:
+                        continue
+                    sub_n = nfr * FRAME_SAMPLES
+                    m = amd.Demod(ns, max_samples=sub_n + 64, streaming=True, device=dev_index)
+                    m.enable_timing(True)
+                    ent = {}
+                    for spw in (1, 4, 16):                      # streams per wavefront (opv_set_frontend)
+                        if spw == 4 and ns < 4096:         # (the four-per-wave mapping is the automatic choice from 2049 streams on)
+                            continue
+                        if spw == 16 and ns < 4096:        # (sixteen per wave: 1024 waves = one per SIMD need 16 384 streams)
+                            continue
+                        if spw == 1 and ns > 8192:
+                            continue
+                        m.set_frontend(spw)
+                        for rep in range(2):
+                            m.reset()
+                            for j in range(ns):
+                                k, seg = j % S, j // S
+                                m.attach(j, d_iq[k].data_ptr() + 4 * seg * sub_n, sub_n, eof=True)
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            m.process()
+                            m.sync()
+                            t1 = time.perf_counter() - t0
+                        f_, m_, c_, cap_ = m.device_frames()
+                        cnt = torch.as_tensor(DevPtr(c_, (ns,), "<i4"), device=dev).cpu().numpy()
+                        fe_ms = m.kernel_times()["msk_frontend"]
+                        ent[f"{spw}_per_wave"] = {"Msamples/s": round(ns * sub_n / t1 / 1e6, 1), "ms": round(t1 * 1e3, 2),
+                                                  "frontend_alone_Msamples/s": round(ns * sub_n / fe_ms / 1e3, 1),
+                                                  "frames_released": int(cnt.sum())}
+                    sweep[f"{ns}x{nfr}"] = ent
+                    m.close()
+                return sweep
+            put("stream_sweep", 5.0, x_sweep)
+            if "stream_sweep" in extras and "error" not in extras["stream_sweep"]:
+                sweep = extras["stream_sweep"]
+                tgt = [int(k.split("x")[0]) for k, v in sweep.items() if max(e["Msamples/s"] for e in v.values()) >= 21680.0]
+                extras["streams_for_target"] = {"target_Msamples/s": 21680.0, "smallest_swept_stream_count_meeting_it": min(tgt) if tgt else None,
+                                                "swept": sorted(int(k.split("x")[0]) for k in sweep)}
+
+            def x_configs4():
+                # BASELINE configs[4]'s whole workload (512 streams x F frames, 64 per GPU on eight of them) on THIS one GPU:
+                # the same generator, global stream ids 0..511, everything resident in HBM (178 GB at F = 1000), one launch.
+                free_b, _tot = torch.cuda.mem_get_info()
+                need_b = 512 * n * 4 * 1.10 + (4 << 30)
+                if free_b < need_b:
+                    return {"skipped": f"{free_b / 1e9:.0f} GB of HBM free, {need_b / 1e9:.0f} GB needed"}
+                else:
+                    big = amd.Demod(512, max_samples=n + 64, streaming=True, device=dev_index)
+                    d_big, tx_big, _n = workload.generate(amd, big, torch, dev, range(512), F, args.ebn0)
+                    big.enable_timing(True)
+                    for rep in range(2):
+                        big.reset()
+                        for k in range(512):
+                            big.attach(k, d_big[k].data_ptr(), n, eof=True)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        big.process()
+                        big.sync()
                         t1 = time.perf_counter() - t0
-                    f_, m_, c_, cap_ = m.device_frames()
-                    cnt = torch.as_tensor(DevPtr(c_, (ns,), "<i4"), device=dev).cpu().numpy()
-                    fe_ms = m.kernel_times()["msk_frontend"]
-                    ent[f"{spw}_per_wave"] = {"Msamples/s": round(ns * sub_n / t1 / 1e6, 1), "ms": round(t1 * 1e3, 2),
-                                              "frontend_alone_Msamples/s": round(ns * sub_n / fe_ms / 1e3, 1),
-                                              "frames_released": int(cnt.sum())}
-                sweep[f"{ns}x{nfr}"] = ent
-                m.close()
-            return sweep
-        put("stream_sweep", 5.0, x_sweep)
-        if "stream_sweep" in extras and "error" not in extras["stream_sweep"]:
-            sweep = extras["stream_sweep"]
-            tgt = [int(k.split("x")[0]) for k, v in sweep.items() if max(e["Msamples/s"] for e in v.values()) >= 21680.0]
-            extras["streams_for_target"] = {"target_Msamples/s": 21680.0, "smallest_swept_stream_count_meeting_it": min(tgt) if tgt else None,
-                                            "swept": sorted(int(k.split("x")[0]) for k in sweep)}
+                    fv, cv = workload.frame_views(big, torch, dev)
+                    ok_counts = bool((cv == F).all().item())
+                    exp_b = torch.from_numpy(tx_big).to(dev)
+                    n_bad = int((fv[:, :F, :] != exp_b).any(dim=2).sum().item())
+                    res_big = {
+                        "streams": 512, "frames_per_stream": F, "iq_GB_in_hbm": round(512 * n * 4 / 1e9, 1),
+                        "Msamples/s": round(512 * n / t1 / 1e6, 1), "x_realtime": round(512 * n / t1 / 2.168e6, 0), "ms": round(t1 * 1e3, 2),
+                        "kernel_ms": {k: round(v, 3) for k, v in big.kernel_times().items()},
+                        "every_stream_released_all_frames": ok_counts, "frames_exact": 512 * F - n_bad, "frames_total": 512 * F}
+                    big.close()
+                    del d_big, fv, cv, exp_b
+                    torch.cuda.empty_cache()
+                return res_big
+            if not args.no_big and S == 64:
+                put("configs4_workload_on_one_gpu", 9.0, x_configs4)
 
-        def x_configs4():
-            # BASELINE configs[4]'s whole workload (512 streams x F frames, 64 per GPU on eight of them) on THIS one GPU:
-            # the same generator, global stream ids 0..511, everything resident in HBM (178 GB at F = 1000), one launch.
-            free_b, _tot = torch.cuda.mem_get_info()
-            need_b = 512 * n * 4 * 1.10 + (4 << 30)
-            if free_b < need_b:
-                return {"skipped": f"{free_b / 1e9:.0f} GB of HBM free, {need_b / 1e9:.0f} GB needed"}
-            else:
-                big = amd.Demod(512, max_samples=n + 64, streaming=True, device=dev_index)
-                d_big, tx_big, _n = workload.generate(amd, big, torch, dev, range(512), F, args.ebn0)
-                big.enable_timing(True)
-                for rep in range(2):
-                    big.reset()
-                    for k in range(512):
-                        big.attach(k, d_big[k].data_ptr(), n, eof=True)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    big.process()
-                    big.sync()
-                    t1 = time.perf_counter() - t0
-                fv, cv = workload.frame_views(big, torch, dev)
-                ok_counts = bool((cv == F).all().item())
-                exp_b = torch.from_numpy(tx_big).to(dev)
-                n_bad = int((fv[:, :F, :] != exp_b).any(dim=2).sum().item())
-                res_big = {
-                    "streams": 512, "frames_per_stream": F, "iq_GB_in_hbm": round(512 * n * 4 / 1e9, 1),
-                    "Msamples/s": round(512 * n / t1 / 1e6, 1), "x_realtime": round(512 * n / t1 / 2.168e6, 0), "ms": round(t1 * 1e3, 2),
-                    "kernel_ms": {k: round(v, 3) for k, v in big.kernel_times().items()},
-                    "every_stream_released_all_frames": ok_counts, "frames_exact": 512 * F - n_bad, "frames_total": 512 * F}
-                big.close()
-                del d_big, fv, cv, exp_b
-                torch.cuda.empty_cache()
-            return res_big
-        if not args.no_big and S == 64:
-            put("configs4_workload_on_one_gpu", 9.0, x_configs4)
+            def x_many():
+                # The many-stream regime on data of its own (not carved out of the 64 captures): 32 768 independent streams x 8 frames,
+                # every one its own BERT capture through the device channel (91 GB of IQ in HBM), one opv_process on the automatic
+                # mapping - sixteen streams per wavefront, two waves per SIMD (k_frontend_x16.hip). The only place where this path's
+                # HBM fraction is not negligible: reported with its own roofline figures.
+                NS, NF = 32768, 8
+                n8 = amd.lib().opv_tx_modulated_samples(NF)
+                free_b, _tot = torch.cuda.mem_get_info()
+                need_b = NS * n8 * 4 * 1.05 + (12 << 30)
+                if free_b < need_b:
+                    return {"skipped": f"{free_b / 1e9:.0f} GB of HBM free, {need_b / 1e9:.0f} GB needed"}
+                else:
+                    ms = amd.Demod(NS, max_samples=n8 + 64, streaming=True, device=dev_index)
+                    gt = {}
+                    d_ms, tx_ms, _n8 = workload.generate(amd, ms, torch, dev, range(NS), NF, args.ebn0, timing=gt)
+                    ms.enable_timing(True)
+                    for rep in range(2):
+                        ms.reset()
+                        for k in range(NS):
+                            ms.attach(k, d_ms[k].data_ptr(), n8, eof=True)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        ms.process()
+                        ms.sync()
+                        t1 = time.perf_counter() - t0
+                    fv, cv = workload.frame_views(ms, torch, dev)
+                    exp_m = torch.from_numpy(tx_ms).to(dev)
+                    n_bad = int((fv[:, :NF - 1, :] != exp_m[:, :NF - 1, :]).any(dim=2).sum().item())
+                    ktm = ms.kernel_times()
+                    fe_gbs = NS * n8 * ALGO_BYTES_PER_SAMPLE / (ktm["msk_frontend"] * 1e-3) / 1e9
+                    res_many = {
+                        "streams": NS, "frames_per_stream": NF, "iq_GB_in_hbm": round(NS * n8 * 4 / 1e9, 1), "generate_s": round(gt["generate_s"], 1),
+                        "frontend_kernel": ms.frontend_kernel(),
+                        "Msamples/s": round(NS * n8 / t1 / 1e6, 1), "x_realtime": round(NS * n8 / t1 / 2.168e6, 0), "ms": round(t1 * 1e3, 2),
+                        "frontend_alone_Msamples/s": round(NS * n8 / ktm["msk_frontend"] / 1e3, 1),
+                        "kernel_ms": {k: round(v, 3) for k, v in ktm.items()},
+                        "roofline_frontend": {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                              "frac": round(fe_gbs / HBM_PEAK_GBS, 4)},
+                        "frames_released": int(cv.sum().item()), "frames_exact_of_first_7": NS * (NF - 1) - n_bad, "frames_compared": NS * (NF - 1)}
+                    ms.close()
+                    del d_ms, fv, cv, exp_m
+                    torch.cuda.empty_cache()
+                return res_many
+            if not args.no_big and S == 64:
+                put("many_streams_unique_captures", 14.0, x_many)
 
-        def x_many():
-            # The many-stream regime on data of its own (not carved out of the 64 captures): 32 768 independent streams x 8 frames,
-            # every one its own BERT capture through the device channel (91 GB of IQ in HBM), one opv_process on the automatic
-            # mapping - sixteen streams per wavefront, two waves per SIMD (k_frontend_x16.hip). The only place where this path's
-            # HBM fraction is not negligible: reported with its own roofline figures.
-            NS, NF = 32768, 8
-            n8 = amd.lib().opv_tx_modulated_samples(NF)
-            free_b, _tot = torch.cuda.mem_get_info()
-            need_b = NS * n8 * 4 * 1.05 + (12 << 30)
-            if free_b < need_b:
-                return {"skipped": f"{free_b / 1e9:.0f} GB of HBM free, {need_b / 1e9:.0f} GB needed"}
-            else:
-                ms = amd.Demod(NS, max_samples=n8 + 64, streaming=True, device=dev_index)
-                gt = {}
-                d_ms, tx_ms, _n8 = workload.generate(amd, ms, torch, dev, range(NS), NF, args.ebn0, timing=gt)
-                ms.enable_timing(True)
-                for rep in range(2):
-                    ms.reset()
-                    for k in range(NS):
-                        ms.attach(k, d_ms[k].data_ptr(), n8, eof=True)
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    ms.process()
-                    ms.sync()
-                    t1 = time.perf_counter() - t0
-                fv, cv = workload.frame_views(ms, torch, dev)
-                exp_m = torch.from_numpy(tx_ms).to(dev)
-                n_bad = int((fv[:, :NF - 1, :] != exp_m[:, :NF - 1, :]).any(dim=2).sum().item())
-                ktm = ms.kernel_times()
-                fe_gbs = NS * n8 * ALGO_BYTES_PER_SAMPLE / (ktm["msk_frontend"] * 1e-3) / 1e9
-                res_many = {
-                    "streams": NS, "frames_per_stream": NF, "iq_GB_in_hbm": round(NS * n8 * 4 / 1e9, 1), "generate_s": round(gt["generate_s"], 1),
-                    "frontend_kernel": ms.frontend_kernel(),
-                    "Msamples/s": round(NS * n8 / t1 / 1e6, 1), "x_realtime": round(NS * n8 / t1 / 2.168e6, 0), "ms": round(t1 * 1e3, 2),
-                    "frontend_alone_Msamples/s": round(NS * n8 / ktm["msk_frontend"] / 1e3, 1),
-                    "kernel_ms": {k: round(v, 3) for k, v in ktm.items()},
-                    "roofline_frontend": {"bound": "hbm", "achieved": round(fe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                          "frac": round(fe_gbs / HBM_PEAK_GBS, 4)},
-                    "frames_released": int(cv.sum().item()), "frames_exact_of_first_7": NS * (NF - 1) - n_bad, "frames_compared": NS * (NF - 1)}
-                ms.close()
-                del d_ms, fv, cv, exp_m
-                torch.cuda.empty_cache()
-            return res_many
-        if not args.no_big and S == 64:
-            put("many_streams_unique_captures", 14.0, x_many)
-
-        def x_pcie():
-            # PCIe-inclusive: the boundary's host-buffer entry points instead of HBM-resident captures. Pinned host copies of the
-            # first FH frames of every stream are pushed in rounds of RH frames: "host_pushed" with one opv_push_iq per stream (a copy
-            # each, on the library's copy stream), "host_pushed_batched" with one opv_push_iq_batch_async per round (ONE gather kernel
-            # for the 64 blocks; opv_process queues behind it on the device) - either way round r + 1 crosses PCIe while the kernels
-            # of round r run. Same streams attached in HBM are timed beside it. Then a live serving round.
-            both = {}
-            FH, RH = min(F, 100), 10
-            if FH >= 2 * RH:
-                sub_n = FH * FRAME_SAMPLES
-                host = [d_iq[k][: 2 * sub_n].cpu().pin_memory() for k in range(S)]
-                host_np = [h.numpy() for h in host]
-                hp = amd.Demod(S, max_samples=sub_n + 64, streaming=True, device=dev_index)
-                res = {}
-                for mode in ("hbm_attached", "host_pushed", "host_pushed", "host_pushed_batched", "host_pushed_batched"):
-                    hp.reset()
-                    torch.cuda.synchronize()
-                    t0 = time.perf_counter()
-                    if mode == "hbm_attached":
-                        for k in range(S):
-                            hp.attach(k, d_iq[k].data_ptr(), sub_n, eof=True)
-                        hp.process()
-                    else:
-                        per = RH * FRAME_SAMPLES
-                        for r in range(0, sub_n, per):
-                            m = min(per, sub_n - r)
-                            if mode == "host_pushed_batched":
-                                hp.push_batch(range(S), [host_np[k][2 * r: 2 * (r + m)] for k in range(S)], wait=False)
-                            else:
-                                for k in range(S):
-                                    hp.push(k, host_np[k][2 * r: 2 * (r + m)])
+            def x_pcie():
+                # PCIe-inclusive: the boundary's host-buffer entry points instead of HBM-resident captures. Pinned host copies of the
+                # first FH frames of every stream are pushed in rounds of RH frames: "host_pushed" with one opv_push_iq per stream (a copy
+                # each, on the library's copy stream), "host_pushed_batched" with one opv_push_iq_batch_async per round (ONE gather kernel
+                # for the 64 blocks; opv_process queues behind it on the device) - either way round r + 1 crosses PCIe while the kernels
+                # of round r run. Same streams attached in HBM are timed beside it. Then a live serving round.
+                both = {}
+                FH, RH = min(F, 100), 10
+                if FH >= 2 * RH:
+                    sub_n = FH * FRAME_SAMPLES
+                    host = [d_iq[k][: 2 * sub_n].cpu().pin_memory() for k in range(S)]
+                    host_np = [h.numpy() for h in host]
+                    hp = amd.Demod(S, max_samples=sub_n + 64, streaming=True, device=dev_index)
+                    res = {}
+                    for mode in ("hbm_attached", "host_pushed", "host_pushed", "host_pushed_batched", "host_pushed_batched"):
+                        hp.reset()
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        if mode == "hbm_attached":
+                            for k in range(S):
+                                hp.attach(k, d_iq[k].data_ptr(), sub_n, eof=True)
                             hp.process()
-                        if mode == "host_pushed_batched":
-                            hp.push_wait()
-                        for k in range(S):
-                            hp.flush(k)
-                        hp.process()
-                    hp.sync()
-                    t1 = time.perf_counter() - t0
-                    f_, m_, c_, cap_ = hp.device_frames()
-                    cnt = torch.as_tensor(DevPtr(c_, (S,), "<i4"), device=dev).cpu().numpy()
-                    res[mode] = {"Msamples/s": round(S * sub_n / t1 / 1e6, 1), "ms": round(t1 * 1e3, 2),
-                                 "GB/s_over_pcie": None if mode == "hbm_attached" else round(S * sub_n * 4 / t1 / 1e9, 2),
-                                 "frames_released": int(cnt.sum())}
-                    if mode != "hbm_attached":     # the pushed streams are fresh (reset drops the attachment)
-                        fr_h = torch.as_tensor(DevPtr(f_, (S, cap_, 134), "|u1"), device=dev)[:, : FH - 1, :]
-                        assert bool((fr_h == frames_view[:, : FH - 1, :]).all().item()), "pushed-path frames differ from the attached run"
-                res["config"] = f"{S} streams x {FH} frames, rounds of {RH} frames, pinned host buffers"
-                both["pcie_inclusive"] = res
-                hp.close()
-                # live serving round: one 86720-sample chunk (40 ms of signal) per stream pushed from host memory,
-                # processed, frames popped - what a multi-stream receiver does every 40 ms
-                lv = amd.Demod(S, max_samples=4 * FRAME_SAMPLES + 65536, streaming=True, device=dev_index)
-                rounds = []
-                for r in range(min(14, FH - 1)):
-                    blks = [host_np[k][2 * r * FRAME_SAMPLES: 2 * (r + 1) * FRAME_SAMPLES] for k in range(S)]
-                    t0 = time.perf_counter()
-                    lv.push_batch(range(S), blks)
-                    t1 = time.perf_counter()
-                    lv.process()
-                    lv.sync()
-                    t2 = time.perf_counter()
-                    got = sum(len(lv.pop_frames(k)[0]) for k in range(S))
-                    t3 = time.perf_counter()
-                    rounds.append((t3 - t0, t1 - t0, t2 - t1, t3 - t2, got))
-                med = lambda i: round(1e3 * float(np.median([x[i] for x in rounds[3:]])), 3)
-                both["live_round"] = {"streams": S, "signal_ms_per_round": 40.0, "round_ms": med(0), "push_ms": med(1),
-                                        "process_ms": med(2), "pop_ms": med(3), "frames_per_round": int(rounds[-1][4])}
-                lv.close()
-                del host, host_np
-            return both
-        both = budget.run("pcie_inclusive+live_round", 5.0, x_pcie)
-        if both is not None:
-            extras.update(both if "error" not in both else {"pcie_inclusive": both})
-        put("cli_drop_in", 3.0, lambda: cli_drop_in(raw, n))
-        if not args.no_big:
-            put("live_capacity", 18.0, lambda: live_capacity(dev_index, budget))
-        extras["budget"] = budget.report()
-        extras["skipped_for_budget"] = budget.skipped
-        out["extras"] = extras
-        out["setup"] = {"device_modulate_s_all_streams": round(t_mod, 2),
-                        "device_modulate_one_stream": {"s": round(t_dev_mod, 3), "Msamples/s": round(n / t_dev_mod / 1e6, 1),
-                                                        "note": "opv_tx_modulate_device end to end on a fresh context: 134 B/frame H2D, k_tx_encode, k_tx_scan_frames, "
-                                                                "k_tx_expand_phases (first call of a context), k_tx_modulate, count D2H + sync"}}
-    elif rank == 0 and args.no_extras:
-        out["cpu_baseline"] = None
-    elif rank == 0:
-        # N > 1: the same bounded CPU sample as the N = 1 line, timed on rank 0's host cores while
-        # the other ranks wait at the end of the job (outside the timed region)
-        raw = np.ascontiguousarray(amd.modulate(tx_frames)).tobytes()
-        out["cpu_baseline"] = cpu_baseline(raw, n)
+                        else:
+                            per = RH * FRAME_SAMPLES
+                            for r in range(0, sub_n, per):
+                                m = min(per, sub_n - r)
+                                if mode == "host_pushed_batched":
+                                    hp.push_batch(range(S), [host_np[k][2 * r: 2 * (r + m)] for k in range(S)], wait=False)
+                                else:
+                                    for k in range(S):
+                                        hp.push(k, host_np[k][2 * r: 2 * (r + m)])
+                                hp.process()
+                            if mode == "host_pushed_batched":
+                                hp.push_wait()
+                            for k in range(S):
+                                hp.flush(k)
+                            hp.process()
+                        hp.sync()
+                        t1 = time.perf_counter() - t0
+                        f_, m_, c_, cap_ = hp.device_frames()
+                        cnt = torch.as_tensor(DevPtr(c_, (S,), "<i4"), device=dev).cpu().numpy()
+                        res[mode] = {"Msamples/s": round(S * sub_n / t1 / 1e6, 1), "ms": round(t1 * 1e3, 2),
+                                     "GB/s_over_pcie": None if mode == "hbm_attached" else round(S * sub_n * 4 / t1 / 1e9, 2),
+                                     "frames_released": int(cnt.sum())}
+                        if mode != "hbm_attached":     # the pushed streams are fresh (reset drops the attachment)
+                            fr_h = torch.as_tensor(DevPtr(f_, (S, cap_, 134), "|u1"), device=dev)[:, : FH - 1, :]
+                            assert bool((fr_h == frames_view[:, : FH - 1, :]).all().item()), "pushed-path frames differ from the attached run"
+                    res["config"] = f"{S} streams x {FH} frames, rounds of {RH} frames, pinned host buffers"
+                    both["pcie_inclusive"] = res
+                    hp.close()
+                    # live serving round: one 86720-sample chunk (40 ms of signal) per stream pushed from host memory,
+                    # processed, frames popped - what a multi-stream receiver does every 40 ms
+                    lv = amd.Demod(S, max_samples=4 * FRAME_SAMPLES + 65536, streaming=True, device=dev_index)
+                    rounds = []
+                    for r in range(min(14, FH - 1)):
+                        blks = [host_np[k][2 * r * FRAME_SAMPLES: 2 * (r + 1) * FRAME_SAMPLES] for k in range(S)]
+                        t0 = time.perf_counter()
+                        lv.push_batch(range(S), blks)
+                        t1 = time.perf_counter()
+                        lv.process()
+                        lv.sync()
+                        t2 = time.perf_counter()
+                        got = sum(len(lv.pop_frames(k)[0]) for k in range(S))
+                        t3 = time.perf_counter()
+                        rounds.append((t3 - t0, t1 - t0, t2 - t1, t3 - t2, got))
+                    med = lambda i: round(1e3 * float(np.median([x[i] for x in rounds[3:]])), 3)
+                    both["live_round"] = {"streams": S, "signal_ms_per_round": 40.0, "round_ms": med(0), "push_ms": med(1),
+                                            "process_ms": med(2), "pop_ms": med(3), "frames_per_round": int(rounds[-1][4])}
+                    lv.close()
+                    del host, host_np
+                return both
+            both = budget.run("pcie_inclusive+live_round", 5.0, x_pcie)
+            if both is not None:
+                extras.update(both if "error" not in both else {"pcie_inclusive": both})
+            put("cli_drop_in", 3.0, lambda: cli_drop_in(raw, n))
+            if not args.no_big:
+                put("live_capacity", 18.0, lambda: live_capacity(dev_index, budget))
+            extras["budget"] = budget.report()
+            extras["skipped_for_budget"] = budget.skipped
+            out["extras"] = extras
+            out["setup"] = {"device_modulate_s_all_streams": round(t_mod, 2),
+                            "device_modulate_one_stream": {"s": round(t_dev_mod, 3), "Msamples/s": round(n / t_dev_mod / 1e6, 1),
+                                                            "note": "opv_tx_modulate_device end to end on a fresh context: 134 B/frame H2D, k_tx_encode, k_tx_scan_frames, "
+                                                                    "k_tx_expand_phases (first call of a context), k_tx_modulate, count D2H + sync"}}
+        elif rank == 0 and args.no_extras:
+            out["cpu_baseline"] = None
+        elif rank == 0:
+            # N > 1: the same bounded CPU sample as the N = 1 line, timed on rank 0's host cores while
+            # the other ranks wait at the end of the job (outside the timed region)
+            raw = np.ascontiguousarray(amd.modulate(tx_frames)).tobytes()
+            out["cpu_baseline"] = cpu_baseline(raw, n)
 
     dm.close()
     if rank == 0:

@@ -33,7 +33,8 @@ def _start_clock():
 _LATE = ["test_world2_real_pipeline_every_global_stream_vs_oracle", "test_real_pipeline_rank_code_under_nccl_world_1",
          "test_gather_frames_under_nccl_world_1", "test_worldN_real_pipeline_over_rccl_every_global_stream_vs_oracle",
          "test_bench_world2_under_the_drivers_launcher", "test_bench_world2_started_from_a_bare_shell",
-         "test_bench_worldN_over_rccl_under_the_drivers_launcher", "test_bench_world2_a_dead_rank_takes_the_job_down"]
+         "test_bench_worldN_over_rccl_under_the_drivers_launcher", "test_bench_world2_a_dead_rank_takes_the_job_down",
+         "test_bench_plain_run_is_lean_and_dumps_what_it_decoded"]
 # (test_bench_rccl_leg_executes_at_world_1 is not one of them: it only reads what the session-start child already did)
 _LATE_RESERVE_S = 200.0
 
@@ -96,7 +97,7 @@ def run_rccl_selftest():
     env.update(OPV_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), NCCL_DEBUG="INFO",
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--streams", "8", "--frames", "12", "--steps", "1",
-           "--warmup", "0", "--no-extras"]
+           "--warmup", "0", "--full", "--no-extras"]
     t0 = time.time()
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)     # (a hung rendezvous must not eat the suite's time)
     return {"cmd": "OPV_BENCH_FORCE_DIST=1 NCCL_DEBUG=INFO " + " ".join(cmd[1:]), "rc": p.returncode, "stdout": p.stdout,

@@ -82,7 +82,7 @@ import time
 
 import pytest
 
-WORLD2_ARGS = ["--gpus", "2", "--streams", "8", "--frames", "12", "--steps", "2", "--warmup", "1"]
+WORLD2_ARGS = ["--gpus", "2", "--streams", "8", "--frames", "12", "--steps", "2", "--warmup", "1", "--full"]     # (--full: the checks below)
 
 
 def _world2_env():
@@ -219,3 +219,41 @@ def test_bench_world2_a_dead_rank_takes_the_job_down():
     assert not [ln for ln in out.splitlines() if ln.startswith('{"metric"')]     # and no bench line from a broken job
     with open(ROOT / "gpurun_out" / "bench_world2.txt", "a") as f:
         f.write(f"$ bench.py --gpus 2 ... with rank 1 killed (SIGKILL) 20 s in: parent exit {parent.returncode} after {took:.2f} s, no bench line\n\n")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_what_it_decoded(tmp_path):
+    """the plain command (no --full): one line with the headline fields and nothing measured beside them, --steps timed steps;
+    --dump-outputs writes what the last timed step decoded - every stream's frames equal what it was sent (16 dB: at most a
+    stray channel error), counts and Viterbi metrics beside them - and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    from __graft_entry__ import load_opv_amd, load_pkg_module
+    amd, workload = load_opv_amd(), load_pkg_module("workload")
+    S, F, K = 8, 12, 3
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "OPV_BENCH_FORCE_DIST")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--streams", str(S), "--frames", str(F), "--steps", str(K),
+               "--warmup", "1", "--dump-outputs", str(d)]
+        p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+        assert len(lines) == 1, p.stdout[-2000:]
+        line = json.loads(lines[0])
+        assert line["steps"] == K and len(line["median"]["step_ms"]) == K and line["warmup"] == 1
+        assert line["unit"] == "Msamples/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+        n = line["config"]["samples_per_stream"] * S
+        assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3) / 1e6) < 0.01 * line["value"]
+        for k in ("roofline", "kernel_ms", "check", "cpu_baseline", "extras"):
+            assert k not in line, k                                  # (what --full adds)
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["counts", "frames", "viterbi_metric"] and sorted(b) == sorted(a)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert a["frames"].shape == (S, F, 134) and a["viterbi_metric"].shape == (S, F) and np.array_equal(a["counts"], np.full(S, F))
+    sent = np.stack([workload.tx_frames(amd, g, F) for g in range(S)])
+    assert int((a["frames"] == sent).all(axis=2).sum()) >= S * F - 1
+    m = a["viterbi_metric"]
+    assert np.array_equal(m, np.round(m)) and m.min() >= -1                # int32 metrics (-1: a frame the decoder dropped)

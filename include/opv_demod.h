@@ -133,7 +133,7 @@ typedef struct opv_ctx opv_ctx;
 /* ---- lifetime: replaces constructing MSKDemodulatorAFC + SyncTracker + FrameDecoder
  *      (src/opv-demod.cpp:999-1001 / :1164,:1182-1183) for n_streams independent captures */
 int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg);
-/* Environment variables. The library reads FOUR, all of them TEST HOOKS - never set in production -, all of them in opv_create
+/* Environment variables. The library reads FIVE, all of them TEST HOOKS - never set in production -, all of them in opv_create
  * and nowhere else (a context's behaviour is fixed when it is created; grep getenv csrc/):
  *   OPV_OFFSET_DISTRUST_LIBM  (any value) the offset search's last-place ties are decided by the device's sincos although the host's
  *                             libm reproduces the reference's (opv_offset_ties_on_host() == 0): moves a stream whose search ties
@@ -142,7 +142,10 @@ int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg);
  *                             the zone rule its one-time probe of sin / cos allows: same samples, slower set-up. The fallback's test uses it.
  *   OPV_PUSH_NO_GATHER        (any value) opv_push_iq_batch(_async) moves pinned blocks with one copy per block instead of one gather
  *                             kernel: same bytes, the path pageable sources take anyway. Its test runs both.
- *   OPV_PUSH_GATHER_BLOCKS    (a number > 0) workgroups of that gather kernel (default 32; a measurement knob, results unaffected). */
+ *   OPV_PUSH_GATHER_BLOCKS    (a number > 0) workgroups of that gather kernel (default 32; a measurement knob, results unaffected).
+ *   OPV_FRONTEND_INT16_RING   (any value) k_msk_frontend_rb keeps its int16 sample ring at every stream count, instead of the fp64 ring
+ *                             a helper wave fills while the context has no more streams than the device has CUs: same results
+ *                             bit for bit, slower. Its parity test runs both. */
 void opv_destroy(opv_ctx* ctx);
 const char* opv_last_error(void);
 int opv_abi_version(void);

@@ -52,7 +52,10 @@
 //     4096-sample ring (slot = sample index & 4095) plus a 4-sample guard that mirrors the head
 //     of the even tile for a lane's second interpolation tap; the next tile is requested one
 //     whole tile (~51 symbols) before its first use. Lanes read their taps straight from the
-//     int16 ring (ds_read2_b32) and widen in registers.
+//     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
+//     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
+//     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
+//     (f64_ring_helper: 6 instructions per symbol fewer).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
 //     decisions on noisy input do. No MFMA: the per-symbol contraction is
 //     3x4x60 with a serial dependence between symbols.
@@ -87,9 +90,35 @@ static_assert((kRing & (kRing - 1)) == 0, "ring must be a power of two");
 //   opv_atan2.h says why that is plenty) = 32 800 B -> 49 200 B for one wave, 98 400 B for four
 constexpr uint32_t kTabOff = kRingBytes + kGuardBytes;   // 16400
 static_assert(kTabOff % 16 == 0, "16-byte LDS alignment");
+constexpr uint32_t kAtanQBytes = 1025 * 32;
+constexpr uintptr_t kRbLdsBase = 16;                // k_msk_frontend_rb: LDS bytes [0, 16) unused (see the kernel)
+static_assert(kRbLdsBase + kTabOff + kAtanQBytes == OPV_RB_LDS_I16, "launch size of the int16-ring shape");
+
+// The fp64 ring (k_msk_frontend_rb launched with 128 threads, one stream per CU): wave 1 is a helper that reads the int16 IQ
+// once and writes each sample n as {x_r[n], x_i[n], x_r[n+1] - x_r[n], x_i[n+1] - x_i[n]} in fp64 (32 B, all exact), so that
+// the stream's wave reads its interpolation operands with two ds_read_b128 instead of unpacking and widening int16 taps.
+// LDS: atan table | ring | {low, ready, done} (table and ring offsets fit the 16-bit offset field of ds_read). `low` (wave 0): lowest sample it still needs; `ready` (wave 1): samples below
+// it are written; `done` (wave 0): the helper may leave. Hand-over per batch of symbols, not per symbol; every wait bounded.
+constexpr uint32_t kF64Ring = 2048;                  // samples, slot = index & 2047
+constexpr uint32_t kF64RingBytes = kF64Ring * 32;    // 65 536
+constexpr uint32_t kF64Chunk = 256;                  // samples the helper converts per publication (4 per lane)
+constexpr uint32_t kF64TabOff = 0;
+constexpr uint32_t kF64RingOff = kAtanQBytes;       // 32 800
+constexpr uint32_t kF64FlagOff = kF64RingOff + kF64RingBytes;
+constexpr uint32_t kF64WaitSpins = 1u << 22;         // wave 0 waiting for the helper: ~0.1 s of s_sleep 1, never reached
+constexpr uint32_t kHelperSpins = 1u << 22;          // helper waiting for a free slot: ~1 s of s_sleep 8 without progress
+static_assert(kRbLdsBase + kF64FlagOff + 16 == OPV_RB_LDS_F64, "launch size of the fp64-ring shape");
+static_assert(kF64Ring % kF64Chunk == 0 && (kF64Ring & (kF64Ring - 1)) == 0, "chunks tile the power-of-two ring");
 
 typedef __attribute__((address_space(1))) double gdouble;
 typedef __attribute__((address_space(1))) unsigned char gbyte;
+// LDS is addressed through address-space-3 pointers throughout, so that offsets from the constant base of k_msk_frontend_rb's
+// dynamic allocation fold into the ds_read / ds_write offset fields
+typedef double d2v __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) unsigned char lbyte;
+typedef __attribute__((address_space(3))) int lint;
+typedef __attribute__((address_space(3))) double ldouble;
+typedef __attribute__((address_space(3))) d2v ld2v;
 
 __device__ inline int dlo(double v) { return __double2loint(v); }
 __device__ inline int dhi(double v) { return __double2hiint(v); }
@@ -228,17 +257,66 @@ __device__ __noinline__ double2 silence_pd(double dr, double di, PrevSums prv, b
 // but the atan table.
 // (A two-waves-per-stream mapping and the round-1 symbol body were measured against this one - 6 % and 25 % slower -
 // and removed in round 6: NOTEBOOK.md has the measurements, git the code.)
-template <int WPB>
+typedef __attribute__((address_space(3))) volatile uint32_t lds_flag;
+__device__ inline lds_flag* f64_flags(lbyte* lds_all) {
+    return reinterpret_cast<lds_flag*>(lds_all + kF64FlagOff);
+}
+
+// Wave 1 of the fp64-ring shape: converts chunks of kF64Chunk samples ahead of the stream's wave, from the first tile the
+// int16 path would stage (origin - kBack) up to past the last sample the stream's wave can request. Nothing at or past
+// n_avail is read from memory: such samples (and the difference of the last one) are zeros, which no kept result uses
+// (the highest tap of a symbol is sample origin + N - 1). Writes no OpvStream field.
+__device__ void f64_ring_helper(const OpvStream& st, lbyte* lds_all) {
+    const uint32_t lane = threadIdx.x & 63u;
+    lds_flag* const fl = f64_flags(lds_all);
+    const uint32_t n_avail = uni((uint32_t)st.n_avail), origin = uni((uint32_t)st.origin);
+    const int* const iq = reinterpret_cast<const int*>(st.iq);   // one int = one int16 IQ pair
+    uint32_t fill = ((origin >= kBack ? origin - kBack : 0u) / kF64Chunk) * kF64Chunk;
+    const uint32_t fill_end = n_avail + kAhead + 2u;          // the stream's wave never waits for more (housekeeping)
+    uint32_t spins = 0;
+    while ((int)(fill - fill_end) < 0) {
+        if (fl[2] != 0u) return;                               // the stream's wave has finished
+        if ((int)(fl[0] + kF64Ring - fill - kF64Chunk) < 0) {  // the chunk's slots are still in use
+            if (++spins > kHelperSpins) return;                // (the stream's wave times out on `ready` and says so)
+            __builtin_amdgcn_s_sleep(8);
+            continue;
+        }
+        spins = 0;
+        const uint32_t n = fill + 4u * lane;
+        int w[5];
+        if (n + 4u <= n_avail) {
+            const int4 v = *reinterpret_cast<const int4*>(iq + n);   // 16-byte aligned: n is a multiple of 4
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; ++k) w[k] = n + k < n_avail ? iq[n + k] : 0;
+        }
+        w[4] = n + 4u < n_avail ? iq[n + 4u] : 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int xr = (int)(short)(w[k] & 0xFFFF), xi = w[k] >> 16;
+            const int yr = (int)(short)(w[k + 1] & 0xFFFF) - xr, yi = (w[k + 1] >> 16) - xi;
+            ld2v* e = reinterpret_cast<ld2v*>(lds_all + kF64RingOff + (((n + (uint32_t)k) & (kF64Ring - 1u)) << 5));
+            e[0] = d2v{(double)xr, (double)xi};
+            e[1] = d2v{(double)yr, (double)yi};
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // the entries before `ready`
+        fill += kF64Chunk;
+        if (lane == 0u) fl[1] = fill;
+    }
+}
+
+template <int WPB, bool F64 = false>
 __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ streams, OpvGlobalCfg cfg, int n_streams,
-                                                  unsigned char* lds_all) {
+                                                  lbyte* lds_all) {
     const int lane = threadIdx.x & 63;
     const int wave = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (a constant 0 lets the ring base fold into the tap address)
     const int sidx = (int)blockIdx.x * WPB + wave;
     const uint64_t dbg_t0 = __builtin_amdgcn_s_memtime(), dbg_r0 = __builtin_amdgcn_s_memrealtime();
 
-    unsigned char* const lds = lds_all + wave * kTabOff;      // this wave's ring + guard
-    const unsigned char* ringb = lds;
-    double* atab = reinterpret_cast<double*>(lds_all + WPB * kTabOff);   // filled by the kernel wrapper, barrier included
+    lbyte* const lds = lds_all + (F64 ? kF64RingOff : wave * kTabOff);   // this wave's ring + guard (F64: the fp64 ring)
+    const lbyte* ringb = lds;
+    const ldouble* atab = reinterpret_cast<const ldouble*>(lds_all + (F64 ? kF64TabOff : WPB * kTabOff));   // filled by the kernel wrapper, barrier included
     if (sidx >= n_streams) return;       // a last, partly filled workgroup
     OpvStream& st = streams[sidx];
 
@@ -318,7 +396,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
     uint64_t soft_keep = st.trk_next >= 24 ? st.trk_next - 24 : 0;
     if (st.trk_state != 0 && st.trk_anchor < soft_keep) soft_keep = st.trk_anchor;
     const uint32_t soft_bmask = (uint32_t)(cap_soft * 8u - 1u) & ~7u;
-    gbyte* const soft_base = (gbyte*)st.soft;
+    // (in SGPRs, the store's base operand: hipcc reads the fp64-ring shape's context with vector loads)
+    gbyte* const soft_base = (gbyte*)(((uint64_t)uni((uint32_t)((uint64_t)st.soft >> 32)) << 32) | uni((uint32_t)(uint64_t)st.soft));
     const gbyte* iq_bytes = (const gbyte*)st.iq;
     const uint64_t n_bytes = (uint64_t)n_avail * 4u;
 
@@ -335,7 +414,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                      : "v"(gsrc), "s"(uni(lds_byte))
                      : "memory");
     };
-    const uint32_t lds_base = uni((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds);
+    const uint32_t lds_base = uni((uint32_t)(uintptr_t)lds);
     auto issue_tile = [&](uint32_t t) {
         // tile t -> slot t&1: 8 wave instructions; an even tile's first 16 B are mirrored into the
         // guard behind the ring. The capture's last, incomplete 16 bytes (n_avail not a multiple
@@ -349,23 +428,37 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             if (off + 16u <= n_bytes) glds16(iq_bytes + off, lds_base + slot + (uint32_t)r * 1024u);
             else if (off < n_bytes) {
                 for (uint32_t j = 0; off + 4u * j < n_bytes; ++j)
-                    *reinterpret_cast<int*>(lds + slot + in_tile + 4u * j) = *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + off + 4u * j);
+                    *reinterpret_cast<lint*>(lds + slot + in_tile + 4u * j) = *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + off + 4u * j);
             }
         }
         if ((t & 1u) == 0u && lane == 0) {
             if (base + 16u <= n_bytes) glds16(iq_bytes + base, lds_base + kRingBytes);
             else
                 for (uint32_t j = 0; base + 4u * j < n_bytes && j < 4u; ++j)
-                    *reinterpret_cast<int*>(lds + kRingBytes + 4u * j) = *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + base + 4u * j);
+                    *reinterpret_cast<lint*>(lds + kRingBytes + 4u * j) = *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + base + 4u * j);
         }
     };
     // lowest sample any lane can touch at the first symbol of this launch
     uint32_t t_lo = (origin >= kBack ? origin - kBack : 0u) / kTile;
-    issue_tile(t_lo);
-    issue_tile(t_lo + 1u);
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): both tiles (and the guard) landed
+    if constexpr (!F64) {
+        issue_tile(t_lo);
+        issue_tile(t_lo + 1u);
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): both tiles (and the guard) landed
+    }
     bool evt_issue = true;               // next tile event: request tile t_lo+2 (else: wait for the newest)
     uint32_t next_evt = (t_lo + 1u) * kTile + kBack;
+    // fp64 ring: wait until the helper has written every sample below `need` (bounded: a hand-over that times out ends
+    // the stream's launch with overflow = 2, which opv_process reports)
+    [[maybe_unused]] lds_flag* const fl = f64_flags(lds_all);
+    [[maybe_unused]] auto f64_wait = [&](uint32_t need) {
+        uint32_t r = uni(fl[1]);
+        for (uint32_t spins = 0; (int)(r - need) < 0;) {
+            if (overflow != 0 || ++spins > kF64WaitSpins) { overflow = 2; break; }
+            __builtin_amdgcn_s_sleep(1);
+            r = uni(fl[1]);
+        }
+        return r;
+    };
 
     for (;;) {
         // ---- which demodulate() call comes next (ref :1026 / :1088 / :1173) ----------------
@@ -398,7 +491,16 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         auto housekeeping = [&](double at) {
             const uint32_t b = uni((uint32_t)at);
             const uint32_t gb = origin + b;                // global index of floor(pos)
-            while (gb >= next_evt) {
+            if constexpr (F64) {
+                // release the slots below the lowest tap, then take what the helper has written so far (it keeps
+                // about a ring ahead, so the wait below only ever happens at the launch's first symbol)
+                if (lane == 0) fl[0] = gb >= kBack ? gb - kBack : 0u;
+                uint32_t ready = uni(fl[1]);
+                if ((int)(ready - gb) < (int)(kAhead + 2u)) ready = f64_wait(gb + kAhead + 2u);
+                asm volatile("" ::: "memory");             // no tap read is hoisted above `ready`
+                next_evt = ready - kAhead;                 // taps of a symbol at gb' < next_evt lie below `ready`
+            }
+            while (!F64 && gb >= next_evt) {
                 if (evt_issue) {
                     // the lowest tap has left tile t_lo for good: refill its slot with tile
                     // t_lo+2 (asynchronous; first needed a whole tile = ~51 symbols from now)
@@ -422,6 +524,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         // One interpolated sample per lane (ref :122-128, :232-238): the two int16 IQ words around
         // pos + kf. Issued for symbol k+1 as soon as pos(k+1) exists.
         int w0 = 0, w1 = 0;
+        [[maybe_unused]] d2v x0{0.0, 0.0}, dx{0.0, 0.0};   // F64: (x_r, x_i)[idx] and the difference to idx + 1
         double f = 0.0;
         uint32_t tap_byte = 0;
         auto fetch_addr = [&](double at, bool clamp0) {
@@ -429,12 +532,19 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             if (clamp0) p = fmax(p, 0.0);                  // early gate before the chunk: s[0] (ref :237)
             const int idx = (int)p;
             f = __builtin_amdgcn_fract(p);                 // p - idx, p >= 0
-            tap_byte = (((uint32_t)idx + origin) << 2) & (kRingBytes - 4u);
+            if constexpr (F64) tap_byte = (((uint32_t)idx + origin) << 5) & (kF64RingBytes - 32u);
+            else tap_byte = (((uint32_t)idx + origin) << 2) & (kRingBytes - 4u);
         };
         auto fetch_read = [&]() {
-            const int* tap = reinterpret_cast<const int*>(ringb + tap_byte);
-            w0 = tap[0];
-            w1 = tap[1];
+            if constexpr (F64) {
+                const ld2v* tap = reinterpret_cast<const ld2v*>(ringb + tap_byte);
+                x0 = tap[0];
+                dx = tap[1];
+            } else {
+                const lint* tap = reinterpret_cast<const lint*>(ringb + tap_byte);
+                w0 = tap[0];
+                w1 = tap[1];
+            }
         };
         auto fetch = [&](double at, bool clamp0) {
             fetch_addr(at, clamp0);
@@ -474,10 +584,16 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             uint32_t soft_off_next = soft_off + 8u;                 // (32-bit filler behind the asm block above)
             asm volatile("" : "+v"(soft_off_next));
             __builtin_amdgcn_sched_barrier(0);
-            const int s0r = (int)(short)(w0 & 0xFFFF), s0i = w0 >> 16;      // ref :1023
-            const int d_r = (int)(short)(w1 & 0xFFFF) - s0r, d_i = (w1 >> 16) - s0i;
-            const double lr = fma(f, (double)d_r, (double)s0r);              // ref :122-128
-            const double li = fma(f, (double)d_i, (double)s0i);
+            double lr, li;
+            if constexpr (F64) {                                            // the same operands, widened by the helper
+                lr = fma(f, dx.x, x0.x);
+                li = fma(f, dx.y, x0.y);
+            } else {
+                const int s0r = (int)(short)(w0 & 0xFFFF), s0i = w0 >> 16;      // ref :1023
+                const int d_r = (int)(short)(w1 & 0xFFFF) - s0r, d_i = (w1 >> 16) - s0i;
+                lr = fma(f, (double)d_r, (double)s0r);                          // ref :122-128
+                li = fma(f, (double)d_i, (double)s0i);
+            }
             const double zr = fma(lr, xc, li * xs);                         // Z = Lam * conj(X)
             const double zi = fma(li, xc, -(lr * xs));
             __builtin_amdgcn_sched_barrier(0);
@@ -582,7 +698,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
 
             // ---- 3. divides (one reciprocal for both), timing loop, AFC --------------------------------
             double ted, h = 0;
-            [[maybe_unused]] double2 c01{0, 0}, c23{0, 0}, c45{0, 0};
+            [[maybe_unused]] d2v c01{0, 0}, c23{0, 0};
             if constexpr (kFirst) {
                 double y = __builtin_amdgcn_rcp(den);
                 const double num = el - ee;
@@ -606,8 +722,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 // k + 128, and subtracting the constant gives k as a double - no v_rndne, no v_cvt
                 const double kt = fma(ratio, kc_64, kc_magic);
                 h = ratio;                                          // (the rows' cubics are written in the argument itself)
-                const unsigned char* rowb = reinterpret_cast<const unsigned char*>(atab) + ((unsigned)dlo(kt) << 5);
-                const double2* trow = reinterpret_cast<const double2*>(rowb);
+                const lbyte* rowb = reinterpret_cast<const lbyte*>(atab) + ((unsigned)dlo(kt) << 5);
+                const ld2v* trow = reinterpret_cast<const ld2v*>(rowb);
                 c23 = trow[1]; c01 = trow[0];
                 ted = num * iden;
                 ted = fma(fma(-den, ted, num), iden, ted);
@@ -624,7 +740,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             if constexpr (!kFirst) {
                 const double pd_off = fma(-sx, kc_halfpi, kc_halfpi);
                 __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC17F);                 // lgkmcnt(1): the table row landed (only the tap read may be in flight)
+                if constexpr (F64) __builtin_amdgcn_s_waitcnt(0xC27F);   // lgkmcnt(2): the table row landed (the two tap reads may be in flight)
+                else __builtin_amdgcn_s_waitcnt(0xC17F);            // lgkmcnt(1): the table row landed (only the tap read may be in flight)
                 __builtin_amdgcn_sched_barrier(0);
                 pd = fma(c23.y, h, c23.x);                          // the row's cubic in q: pi/4 + atan(q) to 4e-14 rad
                 pd = fma(pd, h, c01.y);
@@ -664,6 +781,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             // alternate instead of being copied.
             while (uni_lt(pos + 40.0 + 10.0, Nd)) {        // ref :221
                 uint32_t pairs = uni(housekeeping(pos)) >> 1;
+                if (F64 && overflow != 0) break;           // the helper was lost (f64_wait)
                 fetch(pos, false);
                 // four symbols per trip: a taken branch costs a lone wave 36 cycles (scripts/microbench/dpp64.hip, empty loop)
                 for (uint32_t quads = pairs >> 1; quads != 0u; --quads) {
@@ -699,6 +817,9 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         if (last) { tail_done = 1; break; }
     }
 
+    if constexpr (F64) {
+        if (lane == 0) fl[2] = 1u;                         // the helper may leave
+    }
     if (lane == 0) {
         st.freq_offset = fo;
         st.p1r = qp.a; st.p1i = qp.b; st.p2r = qp.c; st.p2i = qp.d; st.x40c = qp.x40c; st.x40s = qp.x40s;
@@ -719,23 +840,45 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
 }
 
 // the front-end kernels: one wave per stream, one or four waves (streams) per workgroup
-constexpr uint32_t kAtanQBytes = 1025 * 32;
 template <int NT>
-__device__ __forceinline__ void load_atan_table_q(unsigned char* lds_tab) {
-    double* atab = reinterpret_cast<double*>(lds_tab);
+__device__ __forceinline__ void load_atan_table_q(lbyte* lds_tab) {
+    ldouble* atab = reinterpret_cast<ldouble*>(lds_tab);
     for (int i = threadIdx.x; i < 1025 * 4; i += NT) atab[i] = (&kOpvAtanTabQ3R[0][0])[i];
 }
-extern "C" __global__ __launch_bounds__(64) void k_msk_frontend_rb(OpvStream* __restrict__ streams, OpvGlobalCfg cfg,
-                                                                    int n_streams) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds_all[kTabOff + kAtanQBytes];
-    load_atan_table_q<64>(lds_all + kTabOff);
-    __syncthreads();
-    msk_frontend_body<1>(streams, cfg, n_streams, lds_all);
+// k_msk_frontend_rb has two launch shapes (opv_process): 64 threads, OPV_RB_LDS_I16 bytes of dynamic LDS = the int16 ring;
+// 128 threads, OPV_RB_LDS_F64 bytes = wave 0 on the fp64 ring that wave 1 fills (f64_ring_helper)
+extern "C" __global__ __launch_bounds__(128) void k_msk_frontend_rb(OpvStream* __restrict__ streams, OpvGlobalCfg cfg,
+                                                                     int n_streams) {
+    // All of the kernel's LDS is dynamic and starts at LDS address 0 (it has no static LDS; opv_create checks that). Its map
+    // starts at the constant kRbLdsBase, not at an extern array's symbol, so that ring and table offsets fold into the ds_read
+    // offset fields as they did with a static array (and not at 0: no pointer of the kernel is a null pointer).
+    lbyte* const lds_dyn = reinterpret_cast<lbyte*>(kRbLdsBase);
+    if (blockDim.x == 128) {
+        load_atan_table_q<128>(lds_dyn + kF64TabOff);
+        if (threadIdx.x == 0) {   // (plain stores: the barrier orders them before every wave's first look at a flag; wave 0
+                                  // posts `low` at its first batch, before it waits for `ready`)
+            __attribute__((address_space(3))) uint32_t* const fl = reinterpret_cast<__attribute__((address_space(3))) uint32_t*>(lds_dyn + kF64FlagOff);
+            fl[0] = 0u;                                       // low
+            fl[1] = 0u;                                       // ready
+            fl[2] = 0u;                                       // done
+        }
+        __syncthreads();
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0) {   // (wave-uniform, and hipcc is told so)
+            if ((int)blockIdx.x < n_streams) f64_ring_helper(streams[blockIdx.x], lds_dyn);
+            return;
+        }
+        msk_frontend_body<1, true>(streams, cfg, n_streams, lds_dyn);
+    } else {
+        load_atan_table_q<64>(lds_dyn + kTabOff);
+        __syncthreads();
+        msk_frontend_body<1>(streams, cfg, n_streams, lds_dyn);
+    }
 }
 extern "C" __global__ __launch_bounds__(256) void k_msk_frontend_rb_wg4(OpvStream* __restrict__ streams, OpvGlobalCfg cfg,
                                                                          int n_streams) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[4 * kTabOff + kAtanQBytes];
-    load_atan_table_q<256>(lds_all + 4 * kTabOff);
+    lbyte* const lds = (lbyte*)lds_all;
+    load_atan_table_q<256>(lds + 4 * kTabOff);
     __syncthreads();
-    msk_frontend_body<4>(streams, cfg, n_streams, lds_all);
+    msk_frontend_body<4>(streams, cfg, n_streams, lds);
 }

@@ -230,6 +230,8 @@ struct opv_ctx {
     bool tx_trust_libm = false;         // the host's sin / cos behave at the transmit NCOs' flat tops as k_tx_modulate.hip assumes (probed at opv_create)
     bool push_gather = true;            // opv_push_iq_batch moves pinned blocks with one gather kernel (else: one copy per block)
     uint32_t push_gather_blocks = 32;   // workgroups of that kernel (see push_deferred)
+    bool rb_fp64_ring = true;           // k_msk_frontend_rb in its fp64-ring shape (128 threads) while S <= n_cu
+    int n_cu = 0;                       // the device's compute units (multiProcessorCount)
     struct TieWork {                    // what the host function gets: stable for the context's life (opv_destroy drains the stream first)
         OpvTieStage* stage = nullptr;   // pinned: header + tie_slots slots
         uint32_t slots = 0;
@@ -375,6 +377,7 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
     if (!c) return fail(OPV_ENOMEM, "host allocation failed");
     c->n_streams = n_streams;
     c->cfg = *cfg;
+    c->n_cu = prop.multiProcessorCount;
     c->hs.resize(n_streams);
     c->mirror.resize(n_streams);
 
@@ -441,6 +444,14 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
     c->tx_trust_libm = libm_flat_tops_as_assumed() && !std::getenv("OPV_TX_DISTRUST_LIBM");
     c->push_gather = !std::getenv("OPV_PUSH_NO_GATHER");
     if (const char* e = std::getenv("OPV_PUSH_GATHER_BLOCKS")) { const int v = atoi(e); if (v > 0) c->push_gather_blocks = (uint32_t)v; }
+    c->rb_fp64_ring = !std::getenv("OPV_FRONTEND_INT16_RING");
+    {   // k_msk_frontend_rb addresses its dynamic LDS from address 0 on: it must have no static LDS (k_frontend.hip)
+        hipFuncAttributes fa;
+        HIPCHK_C(hipFuncGetAttributes(&fa, (const void*)k_msk_frontend_rb));
+        if (fa.sharedSizeBytes != 0) return cleanup(fail(OPV_EHIP, "k_msk_frontend_rb was built with static LDS"));
+    }
+    // the fp64-ring shape asks for more dynamic LDS than a launch gets by default (one workgroup per CU)
+    if (c->rb_fp64_ring) HIPCHK_C(hipFuncSetAttribute((const void*)k_msk_frontend_rb, hipFuncAttributeMaxDynamicSharedMemorySize, OPV_RB_LDS_F64));
     if (c->host_ties) {
         HIPCHK_C(hipMalloc(&c->d_tie_list, sizeof(uint32_t) * (S + 1)));
         c->tie.slots = (uint32_t)(S < (size_t)OPV_TIE_SLOTS_MAX ? S : (size_t)OPV_TIE_SLOTS_MAX);
@@ -902,9 +913,12 @@ extern "C" int opv_process(opv_ctx* c) {
     else if (S > kFrontendWg4MinStreams) {
         c->last_frontend = "k_msk_frontend_rb_wg4";
         k_msk_frontend_rb_wg4<<<(S + 3) / 4, 256, 0, c->stream>>>(c->d_streams, g, S);
+    } else if (c->rb_fp64_ring && S <= c->n_cu) {       // a helper wave per stream widens the IQ to fp64 (k_frontend.hip: f64_ring_helper)
+        c->last_frontend = "k_msk_frontend_rb";
+        k_msk_frontend_rb<<<S, 128, OPV_RB_LDS_F64, c->stream>>>(c->d_streams, g, S);
     } else {
         c->last_frontend = "k_msk_frontend_rb";
-        k_msk_frontend_rb<<<S, 64, 0, c->stream>>>(c->d_streams, g, S);
+        k_msk_frontend_rb<<<S, 64, OPV_RB_LDS_I16, c->stream>>>(c->d_streams, g, S);
     }
     if (tm) { HIPCHK(hipEventRecord(c->ev[3], c->stream)); HIPCHK(hipEventRecord(c->ev[4], c->stream)); }
     k_sync_track<<<S, 64, 0, c->stream>>>(c->d_streams);
@@ -1170,10 +1184,10 @@ extern "C" int opv_tap_wave_info(opv_ctx* c, int s, uint64_t out[4]) {
 extern "C" int opv_tap_occupancy(opv_ctx* c, int out[6]) {
     if (!c || !out) return fail(OPV_EINVAL, "null argument");
     HIPCHK(hipSetDevice(c->cfg.device));
-    const struct { const void* k; int threads; } ks[6] = {
-        {(const void*)k_msk_frontend_rb, 64}, {(const void*)k_msk_frontend_rb_wg4, 256}, {(const void*)k_msk_frontend_x16_wg4, 256},
-        {(const void*)k_msk_frontend_x4_wg4, 256}, {(const void*)k_frame_decode, 64}, {(const void*)k_frame_scale, 64}};
-    for (int i = 0; i < 6; ++i) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[i], ks[i].k, ks[i].threads, 0));
+    const struct { const void* k; int threads; size_t lds; } ks[6] = {
+        {(const void*)k_msk_frontend_rb, 64, OPV_RB_LDS_I16}, {(const void*)k_msk_frontend_rb_wg4, 256, 0}, {(const void*)k_msk_frontend_x16_wg4, 256, 0},
+        {(const void*)k_msk_frontend_x4_wg4, 256, 0}, {(const void*)k_frame_decode, 64, 0}, {(const void*)k_frame_scale, 64, 0}};
+    for (int i = 0; i < 6; ++i) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[i], ks[i].k, ks[i].threads, ks[i].lds));
     return OPV_OK;
 }
 

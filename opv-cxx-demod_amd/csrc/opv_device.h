@@ -18,6 +18,10 @@
 
 #define OPV_TILE_SAMPLES 2048                 // HBM->LDS staging unit of int16 IQ (two tiles = a power-of-two ring)
 #define OPV_TILE_BYTES (OPV_TILE_SAMPLES * 4) // 8192 B = 8 wave-wide 16 B/lane loads
+// dynamic LDS of k_msk_frontend_rb per launch shape (k_frontend.hip), behind 16 unused bytes: 64 threads = int16 ring of two
+// tiles + guard + angle table; 128 threads = angle table + fp64 ring of 2048 samples x 32 B + hand-over flags (one workgroup per CU)
+#define OPV_RB_LDS_I16 (16 + 2 * OPV_TILE_BYTES + 16 + 1025 * 32)   // 49 216 B
+#define OPV_RB_LDS_F64 (16 + 1025 * 32 + 2048 * 32 + 16)            // 98 368 B
 
 struct OpvFrameRec {       // written by k_sync_track, read by k_frame_decode and the host
     uint64_t payload_sym;  // index of first payload soft symbol in the soft log

@@ -197,9 +197,15 @@ def oracle_offset_energies_chunk(caps):
 
 def oracle_receive_job(x, want_soft=False):
     """one stream through the oracle's whole receive chain (-s semantics); the soft log (8 B per symbol) only on request"""
-    from oracle_lib import Oracle
-    e = Oracle().receive(x, streaming=True, want_soft=want_soft)
-    keys = ("frames", "metrics", "frame_sym", "events", "n_soft", "est_offset", "final_freq_offset") + (("soft",) if want_soft else ())
+    global _RECEIVE_ORACLE
+    try:
+        o = _RECEIVE_ORACLE                        # one per worker process (constructing one runs `make` on the oracle: ~0.3 s)
+    except NameError:
+        from oracle_lib import Oracle
+        o = _RECEIVE_ORACLE = Oracle()
+    e = o.receive(x, streaming=True, want_soft=want_soft)
+    keys = ("frames", "metrics", "frame_sym", "events", "n_soft", "est_offset", "final_freq_offset", "final_state", "chunks") + \
+        (("soft",) if want_soft else ())
     return {k: e[k] for k in keys}
 
 

@@ -188,7 +188,9 @@ def test_fp64_ring_one_stream_and_256(amd, monkeypatch):
 
 
 def test_rb_mapping_names(amd, monkeypatch):
-    """the automatic mapping names k_msk_frontend_rb at 1, 64 and 256 streams (fp64 ring) and at 300 (int16 ring)"""
+    """the automatic mapping names k_msk_frontend_rb at 1, 64, 256 and 300 streams. The name is the same for the fp64 ring (streams
+    <= CUs) and the int16 ring (beyond): both shapes are held to the oracle on either side of that boundary, the int16 ring also
+    forced at n_cu streams, by test_gpu_midrange_streams.py::test_every_stream_and_soft_symbol_vs_oracle"""
     iq = base_capture(amd, frames=1, seed=40)[: 2 * 5000]
     for S in (1, 64, 256, 300):
         d = make_demod(amd, monkeypatch, False, S, max_samples=iq.size // 2 + 64, streaming=True)

@@ -195,15 +195,36 @@ def oracle_offset_energies_chunk(caps):
     return [o.estimate_offset(c, energies=True) for c in caps]
 
 
-def oracle_receive_job(x, want_soft=False):
-    """one stream through the oracle's whole receive chain (-s semantics); the soft log (8 B per symbol) only on request"""
+def pathological_captures(iq10):
+    """Eight inputs nobody promised to be an OPV signal, 3 chunks + 12 345 samples each: full-scale white noise (int16 clipping), DC,
+    a constant carrier on one tone, alternating extremes, silence with a burst in the middle, a signal that stops and resumes,
+    hard clipping, 3-4 LSB of signal. iq10: the oracle's 10-frame BERT capture."""
+    rng = np.random.default_rng(2024)
+    n = 3 * 86720 + 12345
+    t = np.arange(n)
+    caps = []
+    caps.append(rng.integers(-32768, 32768, 2 * n, dtype=np.int64).astype(np.int16))           # white, full scale
+    caps.append(np.full(2 * n, 12345, np.int16))                                                # DC
+    tone = 16383.0 * np.exp(2j * np.pi * 13550.0 * t / 2168000.0)
+    x = np.empty(2 * n, np.int16); x[0::2] = np.rint(tone.real); x[1::2] = np.rint(tone.imag); caps.append(x)   # all-zeros bit stream
+    x = np.empty(2 * n, np.int16); x[0::2] = np.where(t % 2, 32767, -32768); x[1::2] = np.where(t % 3, -32768, 32767); caps.append(x)
+    x = np.zeros(2 * n, np.int16); x[2 * 100000: 2 * 100000 + 60000] = iq10[:60000]; caps.append(x)                # silence, burst, silence
+    x = np.concatenate([iq10[: 2 * 150000], np.zeros(2 * 20000, np.int16), iq10[2 * 150000: 2 * (n - 20000)]]); caps.append(x)  # gap
+    caps.append(np.clip(iq10[: 2 * n].astype(np.int32) * 3, -32768, 32767).astype(np.int16))    # hard clipping
+    caps.append((iq10[: 2 * n] // 4000).astype(np.int16))                                       # 3-4 LSB of signal
+    return caps
+
+
+def oracle_receive_job(x, want_soft=False, streaming=True):
+    """one stream through the oracle's whole receive chain (-s semantics, or batch with streaming=False); the soft log (8 B per
+    symbol) only on request"""
     global _RECEIVE_ORACLE
     try:
         o = _RECEIVE_ORACLE                        # one per worker process (constructing one runs `make` on the oracle: ~0.3 s)
     except NameError:
         from oracle_lib import Oracle
         o = _RECEIVE_ORACLE = Oracle()
-    e = o.receive(x, streaming=True, want_soft=want_soft)
+    e = o.receive(x, streaming=streaming, want_soft=want_soft)
     keys = ("frames", "metrics", "frame_sym", "events", "n_soft", "est_offset", "final_freq_offset", "final_state", "chunks") + \
         (("soft",) if want_soft else ())
     return {k: e[k] for k in keys}

@@ -14,6 +14,7 @@ import pytest
 
 from amd_lib import load
 from oracle_lib import CODED_BITS, FRAME_BYTES, Oracle, channel_model, format_events, impair, resample_clock
+from soak_inputs import pathological_captures
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -155,10 +156,11 @@ def test_extreme_flag_values(amd, oracle, iq10, off, alpha):
 @pytest.mark.parametrize("ppm", [-25000.0, -3000.0, 3000.0, 25000.0])
 def test_timing_loop_slipping(amd, oracle, iq10, ppm):
     """Sample-clock errors far beyond what the timing loop can follow (0.3 % and 2.5 %): it slips a symbol
-    every few hundred / few dozen symbols and the TED output is large all the time; both mappings, -s and batch."""
+    every few hundred / few dozen symbols and the TED output is large all the time; all three mappings (one, four and
+    sixteen streams per wave), -s and batch."""
     x = impair(resample_clock(iq10, ppm), amp=5000.0, f0_hz=-300.0, ebn0_db=20.0, seed=9)
     exp_s, exp_b = oracle.receive(x, streaming=True), oracle.receive(x, streaming=False)
-    for frontend in (1, 4):
+    for frontend in (1, 4, 16):
         for streaming, exp in ((True, exp_s), (False, exp_b)):
             d = amd.Demod(1, max_samples=x.size // 2 + 64, streaming=streaming)
             d.set_frontend(frontend)
@@ -1538,19 +1540,9 @@ def test_pathological_inputs_match_the_oracle(amd, oracle, iq10):
     """Inputs nobody promised to be an OPV signal: full-scale noise (int16 clipping), DC, a constant
     carrier on one tone, alternating extremes, silence with a burst in the middle, a signal that
     stops and resumes. No faults, no hangs, and the same frames / events / soft symbols as the oracle."""
-    rng = np.random.default_rng(2024)
-    n = 3 * 86720 + 12345
-    t = np.arange(n)
-    caps = []
-    caps.append(rng.integers(-32768, 32768, 2 * n, dtype=np.int64).astype(np.int16))           # white, full scale
-    caps.append(np.full(2 * n, 12345, np.int16))                                                # DC
-    tone = 16383.0 * np.exp(2j * np.pi * 13550.0 * t / 2168000.0)
-    x = np.empty(2 * n, np.int16); x[0::2] = np.rint(tone.real); x[1::2] = np.rint(tone.imag); caps.append(x)   # all-zeros bit stream
-    x = np.empty(2 * n, np.int16); x[0::2] = np.where(t % 2, 32767, -32768); x[1::2] = np.where(t % 3, -32768, 32767); caps.append(x)
-    x = np.zeros(2 * n, np.int16); x[2 * 100000: 2 * 100000 + 60000] = iq10[:60000]; caps.append(x)                # silence, burst, silence
-    x = np.concatenate([iq10[: 2 * 150000], np.zeros(2 * 20000, np.int16), iq10[2 * 150000: 2 * (n - 20000)]]); caps.append(x)  # gap
-    caps.append(np.clip(iq10[: 2 * n].astype(np.int32) * 3, -32768, 32767).astype(np.int16))    # hard clipping
-    caps.append((iq10[: 2 * n] // 4000).astype(np.int16))                                       # 3-4 LSB of signal
+    caps = pathological_captures(iq10)          # (shared with tests/test_gpu_mapping_matrix.py)
+    n = caps[0].size // 2
+    assert len(caps) == 8 and n == 3 * 86720 + 12345
     d = amd.Demod(len(caps), max_samples=n + 64, streaming=True)
     got = d.receive(caps)
     d.close()
@@ -1654,14 +1646,14 @@ def test_one_tap_windows_are_counted(amd, oracle, iq10):
     soft = -/+2^-31 there: the reference's tone choice is its own LO rounding). The product must (a) agree
     with the oracle on every soft symbol before the first such window, (b) count these windows in
     opv_stream_state.edge_ties - at least as many as the oracle shows up to the point where the two AFC
-    trajectories may part - on both stream-to-wave mappings."""
+    trajectories may part - on all three stream-to-wave mappings (one, four and sixteen streams per wave)."""
     x, starts = _gapped_capture(oracle, iq10, nudge=False)
     exp = oracle.receive(x, streaming=True)
     amb = np.nonzero((exp["soft"] != 0) & (np.abs(exp["soft"]) < 1.0))[0]
     assert amb.size >= 1, "the un-nudged capture was expected to contain one-tap windows"
     k_end = int(amb[0])
     scale = np.mean(np.abs(exp["soft"])) + 1e-300
-    for frontend in (1, 4):
+    for frontend in (1, 4, 16):
         d = amd.Demod(1, max_samples=x.size // 2 + 64, streaming=True)
         d.set_frontend(frontend)
         g = d.receive([x])[0]

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* 7: opv_process never waits on the host again - the host-libm decision of offset-search near-ties runs as a host
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
+                               7: opv_process never waits on the host again - the host-libm decision of offset-search near-ties runs as a host
                                function IN STREAM ORDER between the search and the front-end (+ opv_offset_ties_decided_on_host, opv_offset_ties_left_to_device); opv_set_frontend
                                takes 0 / 1 / 4 / 16 only (the comparison mappings are gone); opv_tap_occupancy's third entry is k_msk_frontend_x16_wg4;
                                6: offset-search near-ties are decided with the HOST's libm (opv_offset_ties_on_host), one host wait in the round
@@ -205,6 +206,39 @@ int opv_set_frontend(opv_ctx* ctx, int streams_per_wave);
 const char* opv_frontend_kernel(opv_ctx* ctx);
 /* Restores a stream (stream = -1: every stream) to its freshly-created state (keeps buffers). */
 int opv_reset_stream(opv_ctx* ctx, int stream);
+
+/* ---- stream migration: a live stream out of one context and into another -------------------------------------------
+ * Replaces nothing in the reference: its streams are processes, and a process cannot be checkpointed. Here a
+ * stream is its carry (csrc/opv_device.h: OpvStream) plus the tails of its rings, so a server can drain a GPU, re-balance contexts,
+ * move from a 256-stream context (one wavefront per stream) to a 4096-stream one (four per wavefront) or restart a process without
+ * dropping lock or the frame in flight: the moved stream decodes as if it had never moved (tests/test_gpu_stream_migration.py).
+ * opv_export_streams writes ONE self-describing blob for `count` streams into host memory (pinned or pageable; a file or a socket
+ * may carry it to another context, process or device) and returns its size in bytes; opv_export_size is an upper bound for the
+ * same arguments (0 on error; it holds until the next push or opv_process). Both imply opv_push_wait + opv_sync. The export is a
+ * SNAPSHOT: the source stream goes on as before, free its slot with opv_reset_stream. What travels per stream: the OpvStream carry
+ * with every absolute index (samples, symbols, frames, events, chunks); the unconsumed IQ from the point compaction keeps, pushed
+ * but unprocessed samples included, and the EOF mark; the soft symbols the tracker and the decoder can still read; the unpopped
+ * frames with their records, metrics and scales; the unread events; the chunk log; the pop cursors and frame counters.
+ * A stream with a released but undecoded frame is refused (OPV_ESTATE; cannot happen after opv_process); a blob buffer that is
+ * too small is OPV_ECAPACITY. An ATTACHED (zero-copy) capture is exported as its unconsumed tail and becomes an owned, pushed
+ * stream at the destination: the caller's device buffer does not travel.
+ * opv_import_streams is opv_reset_stream on each of the `count` destination slots followed by a load, re-based onto the
+ * destination's pools and rings, whose capacities (max_samples) may differ; other streams are untouched and rounds in flight
+ * are ordered in front of it. The blob format is private to one build of the library. Everything that can refuse an import is
+ * decided on the host before anything is launched, and a refused import leaves the context unchanged and usable: OPV_EINVAL for a
+ * truncated or malformed blob, a blob of another build, a count other than opv_blob_streams(blob), an index out of range or named
+ * twice, or streaming / coherent / have_init_offset / init_offset_hz / pll_bw_hz other than the blob's; OPV_ECAPACITY if the IQ
+ * tail, the soft-symbol tail or the unpopped frames do not fit the destination. opv_tap_soft / opv_tap_chunks answer for an
+ * imported stream as for any long pushed one: history older than what travelled is gone. Zero-copy consumers
+ * (opv_device_frames): the counts entry of an imported slot jumps to the stream's absolute frame number, frame i at slot
+ * i % frame_capacity. One launch packs all requested streams (k_stream_pack) in front of one copy, one launch behind one copy
+ * unpacks them (k_stream_unpack), whatever the count. Under opv_enable_timing a migration call brackets its copy + kernel the
+ * way a round brackets its first kernel: opv_kernel_times [0], the rest ~0.
+ * opv_blob_streams: streams in a blob, or OPV_EINVAL; reads the header only - host only, needs no device. */
+size_t opv_export_size(opv_ctx* ctx, int count, const int* streams);
+long opv_export_streams(opv_ctx* ctx, int count, const int* streams, void* blob, size_t cap);
+int opv_import_streams(opv_ctx* ctx, int count, const int* dst_streams, const void* blob, size_t bytes);
+int opv_blob_streams(const void* blob, size_t bytes);
 
 /* Measurement hook: when enabled, opv_process brackets each of its four hot-path kernels
  * with HIP events on the context's stream. opv_kernel_times (implies opv_sync) returns the

@@ -40,6 +40,8 @@ extern "C" __global__ void k_frame_scale_wave(OpvStream*, uint32_t);
 extern "C" __global__ void k_frame_decode(OpvStream*, uint32_t);
 extern "C" __global__ void k_payload_scale(const double*, uint32_t, double*);
 extern "C" __global__ void k_decode_payloads(const double*, uint32_t, const double*, uint8_t*, int32_t*, int8_t*, int8_t*, uint8_t*);
+extern "C" __global__ void k_stream_pack(const OpvMove*, uint32_t);
+extern "C" __global__ void k_stream_unpack(OpvStream*, int32_t*, const OpvUnpackItem*, uint32_t, const OpvMove*, uint32_t);
 extern "C" __global__ void k_channel(const int4*, int4*, uint64_t, double, double, double, uint64_t);
 extern "C" __global__ void k_resample_clock(const int*, uint64_t, int*, uint64_t, double);
 extern "C" __global__ void k_tx_encode(const uint8_t*, uint32_t, uint8_t*, uint8_t*);
@@ -190,6 +192,8 @@ struct HostStream {
     uint32_t events_popped = 0;
     uint32_t events_dropped = 0;       // overwritten in the (lossy) event ring before they were read
     int32_t decoded = 0, perfect = 0;  // over popped frames (`decoded` / `perfect` of main(), ref :1053-1054)
+    uint64_t soft_floor = 0;           // an imported stream (opv_import_streams): first soft symbol / chunk-log entry that travelled with it
+    uint32_t chunk_floor = 0;
 };
 
 }  // namespace
@@ -246,6 +250,10 @@ struct opv_ctx {
     // behind push_ev on the device, every other push entry point waits on the host first
     bool push_pending = false;
     hipEvent_t push_ev = nullptr;
+    // stream migration (opv_export_streams / opv_import_streams): device staging buffer + pinned tables of k_stream_pack.hip, grow-only
+    void* d_mig = nullptr;
+    void* h_mig_tab = nullptr;
+    size_t mig_bytes = 0, mig_tab_bytes = 0;
     uint64_t cap_soft = 0;
     uint32_t cap_frames = 0, cap_events = 0, cap_chunks = 0;
     bool mirror_valid = false;
@@ -511,6 +519,8 @@ extern "C" void opv_destroy(opv_ctx* c) {
     if (c->h_stall) (void)hipHostFree(c->h_stall);
     if (c->tie.stage) (void)hipHostFree(c->tie.stage);
     if (c->h_bulk_tab) (void)hipHostFree(c->h_bulk_tab);
+    if (c->h_mig_tab) (void)hipHostFree(c->h_mig_tab);
+    if (c->d_mig) (void)hipFree(c->d_mig);
     if (c->push_ev) (void)hipEventDestroy(c->push_ev);
     if (c->done_ev) (void)hipEventDestroy(c->done_ev);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -1134,7 +1144,7 @@ extern "C" long opv_tap_soft(opv_ctx* c, int s, uint64_t first, double* out, siz
     if (int r = check_stream(c, s)) return r;
     if (int r = c->refresh()) return r;
     const OpvStream& st = c->mirror[s];
-    if (st.n_soft > st.cap_soft && first < st.n_soft - st.cap_soft)
+    if ((st.n_soft > st.cap_soft && first < st.n_soft - st.cap_soft) || (first < c->hs[s].soft_floor && first < st.n_soft))
         return fail(OPV_EINVAL, "soft symbols that old have been overwritten (the log is a ring)");
     if (first >= st.n_soft || cap == 0 || !out) return 0;
     uint64_t n = st.n_soft - first;
@@ -1151,7 +1161,7 @@ extern "C" long opv_tap_chunks(opv_ctx* c, int s, uint32_t first, double* out5, 
     if (int r = c->refresh()) return r;
     const OpvStream& st = c->mirror[s];
     if (first >= st.n_chunks || cap == 0 || !out5) return 0;
-    if (st.n_chunks - first > st.cap_chunks) return fail(OPV_EINVAL, "chunk log entries already overwritten (ring)");
+    if (st.n_chunks - first > st.cap_chunks || first < c->hs[s].chunk_floor) return fail(OPV_EINVAL, "chunk log entries already overwritten (ring)");
     uint32_t n = st.n_chunks - first;
     if (n > cap) n = (uint32_t)cap;
     for (uint32_t k = 0; k < n; ++k)
@@ -1559,4 +1569,393 @@ extern "C" int opv_gather_frames_all(opv_ctx* const* ctxs, void* const* comms, i
                                      int32_t* d_counts_all) {
     if (!ctxs || !comms || n < 1) return fail(OPV_EINVAL, "opv_gather_frames_all: bad arguments");
     return gather_group(ctxs, comms, n, root, d_frames_all, d_counts_all);
+}
+
+// ---- stream migration: a live stream out of one context and into another (no counterpart in the reference, whose streams are
+// processes: SURVEY.md §5 "Checkpoint / resume: none") --------------------------------------------------------------------------
+// The blob: [BlobHeader][BlobEntry x count][payload]. An entry is the stream's OpvStream (pointers cleared, IQ indices re-based to
+// the exported tail exactly as compaction re-bases them), the HostStream fields, and where its eight payload segments lie; the
+// payload is what k_stream_pack put into the staging buffer, byte for byte. The format is private to one build of the library:
+// every header field must match, and parse_blob checks every offset, length and index ON THE HOST before anything is launched.
+namespace {
+constexpr uint64_t kBlobMagic = 0x31424f4c4256504full;   // "OPVBLOB1"
+constexpr uint32_t kBlobVersion = 1;
+enum { SEG_IQ, SEG_SOFT, SEG_FREC, SEG_FRAMES, SEG_METRICS, SEG_FSCALE, SEG_EVENTS, SEG_CHUNKS, SEG_N };
+constexpr uint64_t kSegElem[SEG_N] = {4, sizeof(double), sizeof(OpvFrameRec), OPV_FB, sizeof(int32_t), sizeof(double), sizeof(OpvEventRec), 5 * sizeof(double)};
+
+struct BlobHeader {
+    uint64_t magic;
+    uint32_t version, sizeof_stream, sizeof_header, sizeof_entry;
+    int32_t streaming, coherent, have_init_offset;   // the cfg fields that fix behaviour (afc_alpha travels in the OpvStream)
+    uint32_t count;
+    double init_offset_hz, pll_bw_hz;
+    uint64_t total_bytes, payload_off, payload_bytes;
+};
+struct BlobEntry {
+    uint64_t off, len;                  // the stream's payload: offset from payload_off (multiple of 16) and bytes
+    uint64_t seg_off[SEG_N];            // from `off`, multiples of 16
+    uint64_t seg_n[SEG_N];              // ELEMENTS (samples, symbols, records, frames, ..., chunk-log entries)
+    uint64_t soft_first;                // absolute index of the first carried soft symbol (even)
+    uint32_t events_first, chunks_first;   // absolute indices; frames start at `popped`
+    uint32_t popped, events_popped, events_dropped;
+    int32_t decoded, perfect, eof, search_seen, pad;
+    uint64_t last_round_avail;
+    OpvStream st;
+};
+
+uint64_t up16(uint64_t v) { return (v + 15u) & ~15ull; }
+
+// first soft symbol the tracker or the decoder can still read (k_frontend.hip: soft_keep, k_sync_track.hip), even
+uint64_t soft_tail_first(const OpvStream& st) {
+    uint64_t lo = st.trk_next;
+    if (st.trk_state != OPV_HUNTING && st.trk_anchor + 1 < lo) lo = st.trk_anchor + 1;
+    lo = lo >= 24 ? lo - 24 : 0;
+    if (lo > st.n_soft) lo = st.n_soft;
+    lo &= ~1ull;
+    if (st.n_soft > st.cap_soft && lo < st.n_soft - st.cap_soft) lo = (st.n_soft - st.cap_soft + 1) & ~1ull;   // (what the ring still holds)
+    return lo;
+}
+
+int parse_blob(const void* blob, size_t bytes, BlobHeader* h, std::vector<BlobEntry>* ents) {
+    if (!blob || bytes < sizeof(BlobHeader)) return fail(OPV_EINVAL, "stream blob: missing or shorter than its header");
+    std::memcpy(h, blob, sizeof *h);    // (the caller's bytes may sit at any alignment)
+    if (h->magic != kBlobMagic) return fail(OPV_EINVAL, "stream blob: wrong magic");
+    if (h->version != kBlobVersion || h->sizeof_stream != sizeof(OpvStream) || h->sizeof_header != sizeof(BlobHeader) || h->sizeof_entry != sizeof(BlobEntry))
+        return fail(OPV_EINVAL, "stream blob: written by another build of the library (format version / struct sizes differ)");
+    if (h->total_bytes > bytes || h->total_bytes < sizeof(BlobHeader)) return fail(OPV_EINVAL, "stream blob: truncated");
+    if (h->count > 0x7FFFFFFFu || (uint64_t)h->count > (h->total_bytes - sizeof(BlobHeader)) / sizeof(BlobEntry)) return fail(OPV_EINVAL, "stream blob: stream count does not fit the blob");
+    const uint64_t dir_end = sizeof(BlobHeader) + (uint64_t)h->count * sizeof(BlobEntry);
+    if ((h->payload_off & 15u) || h->payload_off < dir_end || h->payload_off > h->total_bytes || h->payload_bytes != h->total_bytes - h->payload_off)
+        return fail(OPV_EINVAL, "stream blob: payload offset / length out of range");
+    if (!ents) return OPV_OK;
+    ents->resize(h->count);
+    if (h->count) std::memcpy(ents->data(), (const char*)blob + sizeof(BlobHeader), (size_t)h->count * sizeof(BlobEntry));
+    for (const BlobEntry& e : *ents) {
+        if ((e.off & 15u) || e.off > h->payload_bytes || e.len > h->payload_bytes - e.off) return fail(OPV_EINVAL, "stream blob: a stream's payload lies outside the blob");
+        for (int k = 0; k < SEG_N; ++k) {
+            if (e.seg_n[k] >= (1ull << 31)) return fail(OPV_EINVAL, "stream blob: segment length out of range");
+            const uint64_t b = e.seg_n[k] * kSegElem[k];
+            if ((e.seg_off[k] & 15u) || e.seg_off[k] > e.len || b > e.len - e.seg_off[k]) return fail(OPV_EINVAL, "stream blob: a segment lies outside its stream's payload");
+        }
+        const OpvStream& st = e.st;
+        const uint32_t nf = (uint32_t)e.seg_n[SEG_FREC];
+        bool ok = e.seg_n[SEG_IQ] == st.n_avail && st.origin <= st.n_avail && st.overflow == 0;
+        ok = ok && e.soft_first + e.seg_n[SEG_SOFT] == st.n_soft && (e.soft_first & 1u) == 0 && e.soft_first <= soft_tail_first(st) && st.trk_next <= st.n_soft;
+        ok = ok && e.seg_n[SEG_FRAMES] == nf && e.seg_n[SEG_METRICS] == nf && e.seg_n[SEG_FSCALE] == nf && e.popped + nf == st.n_frames;
+        ok = ok && e.events_first + (uint32_t)e.seg_n[SEG_EVENTS] == st.n_events && e.events_first == e.events_popped;
+        ok = ok && e.chunks_first + (uint32_t)e.seg_n[SEG_CHUNKS] == st.n_chunks && e.last_round_avail <= st.n_avail;
+        if (!ok) return fail(OPV_EINVAL, "stream blob: a stream's indices contradict its segments");
+    }
+    return OPV_OK;
+}
+
+// the runs of elements [first, first + n) of a ring with `cap` slots of `elem` bytes, against a linear buffer: un-wrapped and cut into
+// pieces of at most OPV_MOVE_PIECE bytes (to_ring: linear -> ring, else ring -> linear)
+void ring_moves(std::vector<OpvMove>* mv, char* ring, uint64_t elem, uint64_t cap, uint64_t first, uint64_t n, char* linear, bool to_ring) {
+    uint64_t p = first % cap, done = 0;
+    while (done < n) {
+        const uint64_t run = n - done < cap - p ? n - done : cap - p;
+        for (uint64_t o = 0; o < run * elem; o += OPV_MOVE_PIECE) {
+            const uint64_t b = run * elem - o < OPV_MOVE_PIECE ? run * elem - o : OPV_MOVE_PIECE;
+            char* r = ring + p * elem + o;
+            char* l = linear + done * elem + o;
+            mv->push_back(to_ring ? OpvMove{l, r, (uint32_t)b, 0} : OpvMove{r, l, (uint32_t)b, 0});
+        }
+        done += run;
+        p = 0;
+    }
+}
+
+// grow-only: the device staging buffer and the pinned table (both idle here: every migration call ends with a wait for the stream)
+int mig_buffers(opv_ctx* c, size_t dev_bytes, size_t tab_bytes) {
+    if (c->mig_bytes < dev_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->d_mig) HIPCHK(hipFree(c->d_mig));
+        c->d_mig = nullptr;
+        c->mig_bytes = 0;
+        const size_t cap = dev_bytes + dev_bytes / 4 + 65536;
+        if (hipMalloc(&c->d_mig, cap) != hipSuccess) { (void)hipGetLastError(); return fail(OPV_ENOMEM, "stream migration: device staging buffer"); }
+        c->mig_bytes = cap;
+    }
+    if (c->mig_tab_bytes < tab_bytes) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->h_mig_tab) HIPCHK(hipHostFree(c->h_mig_tab));
+        c->h_mig_tab = nullptr;
+        c->mig_tab_bytes = 0;
+        const size_t cap = tab_bytes + tab_bytes / 4 + 65536;
+        if (hipHostMalloc(&c->h_mig_tab, cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(OPV_ENOMEM, "stream migration: pinned table"); }
+        c->mig_tab_bytes = cap;
+    }
+    return OPV_OK;
+}
+
+unsigned mig_grid(size_t items) { return (unsigned)(items < 1 ? 1 : items > 4096 ? 4096 : items); }
+
+// under opv_enable_timing a migration call brackets its device work (copy + kernel) like a round's first kernel: opv_kernel_times [0]
+int mig_time(opv_ctx* c, bool end) {
+    if (!c->timing) return OPV_OK;
+    if (!end) { HIPCHK(hipEventRecord(c->ev[0], c->stream)); return OPV_OK; }
+    for (int k = 1; k < 8; ++k) HIPCHK(hipEventRecord(c->ev[k], c->stream));
+    c->timing_valid = true;
+    return OPV_OK;
+}
+
+// what an export of `streams` carries, from the context as it is after opv_push_wait + opv_sync; *payload = bytes of staging needed
+int plan_export(opv_ctx* c, int count, const int* streams, std::vector<BlobEntry>* ents, uint64_t* payload) {
+    if (!c) return fail(OPV_EINVAL, "null context");
+    if (count < 0 || (count > 0 && !streams)) return fail(OPV_EINVAL, "opv_export_streams: bad arguments");
+    for (int i = 0; i < count; ++i)
+        if (streams[i] < 0 || streams[i] >= c->n_streams) return fail(OPV_EINVAL, "opv_export_streams: stream index out of range");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int r = settle_pushes(c)) return r;
+    HIPCHK(hipStreamSynchronize(c->copy_stream));
+    c->mirror_valid = false;                               // (a refresh that also waits for whatever a caller enqueued on the stream)
+    if (int r = c->refresh()) return r;
+    ents->assign((size_t)count, BlobEntry{});
+    uint64_t total = 0;
+    for (int i = 0; i < count; ++i) {
+        const HostStream& h = c->hs[streams[i]];
+        BlobEntry& e = (*ents)[i];
+        OpvStream st = c->mirror[streams[i]];
+        if (st.overflow) return fail(OPV_ESTATE, "opv_export_streams: the stream is in an error state (opv_pop_frames reports it)");
+        if (st.n_frames - h.popped > st.cap_frames) return fail(OPV_ESTATE, "opv_export_streams: more unpopped frames than the ring holds");
+        // IQ: from the point compaction keeps (compact_stream) up to everything pushed, processed or not; indices re-based like there
+        const uint64_t keep = (h.d_iq && st.origin >= 16) ? ((st.origin - 16) & ~3ull) : 0;
+        e.seg_n[SEG_IQ] = h.d_iq ? h.n_avail - keep : 0;
+        st.origin -= keep;
+        st.iq_base += keep;
+        st.n_avail = e.seg_n[SEG_IQ];
+        e.last_round_avail = h.last_round_avail > keep ? h.last_round_avail - keep : 0;
+        if (e.last_round_avail > st.n_avail) e.last_round_avail = st.n_avail;
+        e.soft_first = soft_tail_first(st);
+        e.seg_n[SEG_SOFT] = st.n_soft - e.soft_first;
+        e.popped = h.popped;
+        e.seg_n[SEG_FREC] = e.seg_n[SEG_FRAMES] = e.seg_n[SEG_METRICS] = e.seg_n[SEG_FSCALE] = st.n_frames - h.popped;
+        e.events_popped = h.events_popped;
+        e.events_dropped = h.events_dropped;
+        if (st.n_events - e.events_popped > st.cap_events) {     // lossy ring, as opv_pop_events accounts for it
+            e.events_dropped += (st.n_events - e.events_popped) - st.cap_events;
+            e.events_popped = st.n_events - st.cap_events;
+        }
+        e.events_first = e.events_popped;
+        e.seg_n[SEG_EVENTS] = st.n_events - e.events_first;
+        e.seg_n[SEG_CHUNKS] = st.n_chunks < st.cap_chunks ? st.n_chunks : st.cap_chunks;
+        if (st.n_chunks - (uint32_t)e.seg_n[SEG_CHUNKS] < h.chunk_floor) e.seg_n[SEG_CHUNKS] = st.n_chunks - h.chunk_floor;
+        e.chunks_first = st.n_chunks - (uint32_t)e.seg_n[SEG_CHUNKS];
+        e.decoded = h.decoded;
+        e.perfect = h.perfect;
+        e.eof = h.eof;
+        e.search_seen = h.search_seen ? 1 : 0;
+        st.eof = h.eof;
+        st.frames_popped = e.popped;
+        st.events_popped = e.events_popped;
+        st.iq = nullptr; st.soft = nullptr; st.frec = nullptr; st.events = nullptr; st.chunk_log = nullptr;
+        st.frames = nullptr; st.metrics = nullptr; st.fscale = nullptr;
+        e.st = st;
+        e.off = total;
+        uint64_t o = 0;
+        for (int k = 0; k < SEG_N; ++k) { e.seg_off[k] = o; o += up16(e.seg_n[k] * kSegElem[k]); }
+        e.len = o;
+        total += o;
+    }
+    *payload = total;
+    return OPV_OK;
+}
+
+uint64_t blob_payload_off(int count) { return (sizeof(BlobHeader) + (uint64_t)count * sizeof(BlobEntry) + 255u) & ~255ull; }
+
+}  // namespace
+
+extern "C" size_t opv_export_size(opv_ctx* c, int count, const int* streams) {
+    std::vector<BlobEntry> ents;
+    uint64_t payload = 0;
+    if (plan_export(c, count, streams, &ents, &payload) != OPV_OK) return 0;
+    return (size_t)(blob_payload_off(count) + payload);
+}
+
+extern "C" long opv_export_streams(opv_ctx* c, int count, const int* streams, void* blob, size_t cap) {
+    std::vector<BlobEntry> ents;
+    uint64_t payload = 0;
+    if (int r = plan_export(c, count, streams, &ents, &payload)) return r;
+    if (!blob) return fail(OPV_EINVAL, "opv_export_streams: null blob");
+    BlobHeader h{};
+    h.magic = kBlobMagic;
+    h.version = kBlobVersion;
+    h.sizeof_stream = sizeof(OpvStream);
+    h.sizeof_header = sizeof(BlobHeader);
+    h.sizeof_entry = sizeof(BlobEntry);
+    h.streaming = c->cfg.streaming;
+    h.coherent = c->cfg.coherent;
+    h.have_init_offset = c->cfg.have_init_offset;
+    h.init_offset_hz = c->cfg.have_init_offset ? c->cfg.init_offset_hz : 0.0;
+    h.pll_bw_hz = c->cfg.coherent ? c->cfg.pll_bw_hz : 0.0;
+    h.count = (uint32_t)count;
+    h.payload_off = blob_payload_off(count);
+    h.payload_bytes = payload;
+    h.total_bytes = h.payload_off + payload;
+    if (h.total_bytes > cap) return fail(OPV_ECAPACITY, "opv_export_streams: blob buffer too small (opv_export_size)");
+    // every ring segment of every stream un-wrapped into the staging buffer by ONE launch, then ONE copy to the host
+    std::vector<OpvMove> mv;
+    if (int r = mig_buffers(c, (size_t)payload, 0)) return r;
+    for (int i = 0; i < count; ++i) {
+        const BlobEntry& e = ents[i];
+        const HostStream& hs = c->hs[streams[i]];
+        const OpvStream& m = c->mirror[streams[i]];
+        char* base = (char*)c->d_mig + e.off;
+        const uint64_t keep = e.st.iq_base - m.iq_base;
+        if (e.seg_n[SEG_IQ]) ring_moves(&mv, (char*)hs.d_iq + keep * 4, 4, e.seg_n[SEG_IQ], 0, e.seg_n[SEG_IQ], base + e.seg_off[SEG_IQ], false);
+        ring_moves(&mv, (char*)m.soft, kSegElem[SEG_SOFT], m.cap_soft, e.soft_first, e.seg_n[SEG_SOFT], base + e.seg_off[SEG_SOFT], false);
+        ring_moves(&mv, (char*)m.frec, kSegElem[SEG_FREC], m.cap_frames, e.popped, e.seg_n[SEG_FREC], base + e.seg_off[SEG_FREC], false);
+        ring_moves(&mv, (char*)m.frames, kSegElem[SEG_FRAMES], m.cap_frames, e.popped, e.seg_n[SEG_FRAMES], base + e.seg_off[SEG_FRAMES], false);
+        ring_moves(&mv, (char*)m.metrics, kSegElem[SEG_METRICS], m.cap_frames, e.popped, e.seg_n[SEG_METRICS], base + e.seg_off[SEG_METRICS], false);
+        ring_moves(&mv, (char*)m.fscale, kSegElem[SEG_FSCALE], m.cap_frames, e.popped, e.seg_n[SEG_FSCALE], base + e.seg_off[SEG_FSCALE], false);
+        ring_moves(&mv, (char*)m.events, kSegElem[SEG_EVENTS], m.cap_events, e.events_first, e.seg_n[SEG_EVENTS], base + e.seg_off[SEG_EVENTS], false);
+        ring_moves(&mv, (char*)m.chunk_log, kSegElem[SEG_CHUNKS], m.cap_chunks, e.chunks_first, e.seg_n[SEG_CHUNKS], base + e.seg_off[SEG_CHUNKS], false);
+    }
+    if (int r = mig_buffers(c, (size_t)payload, mv.size() * sizeof(OpvMove))) return r;
+    char* out = (char*)blob;
+    std::memset(out, 0, (size_t)h.payload_off);
+    std::memcpy(out, &h, sizeof h);
+    if (count) std::memcpy(out + sizeof h, ents.data(), (size_t)count * sizeof(BlobEntry));
+    if (payload) {
+        std::memcpy(c->h_mig_tab, mv.data(), mv.size() * sizeof(OpvMove));
+        void* d_tab = nullptr;
+        HIPCHK(hipHostGetDevicePointer(&d_tab, c->h_mig_tab, 0));
+        if (int r = mig_time(c, false)) return r;
+        // (the padding between segments is never written by a move: cleared, so that the same state gives the same bytes)
+        HIPCHK(hipMemsetAsync(c->d_mig, 0, (size_t)payload, c->stream));
+        k_stream_pack<<<mig_grid(mv.size()), 256, 0, c->stream>>>((const OpvMove*)d_tab, (uint32_t)mv.size());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out + h.payload_off, c->d_mig, (size_t)payload, hipMemcpyDeviceToHost, c->stream));
+        if (int r = mig_time(c, true)) return r;
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    // a frame that has been released but not decoded (cannot happen after opv_process) would lose its payload's claim on the soft tail
+    for (int i = 0; i < count; ++i) {
+        const BlobEntry& e = ents[i];
+        const char* met = out + h.payload_off + e.off + e.seg_off[SEG_METRICS];
+        for (uint64_t k = 0; k < e.seg_n[SEG_METRICS]; ++k) {
+            int32_t v;
+            std::memcpy(&v, met + 4 * k, 4);
+            if (v == INT32_MIN) return fail(OPV_ESTATE, "opv_export_streams: a released frame has not been decoded yet (call opv_process first)");
+        }
+    }
+    return (long)h.total_bytes;
+}
+
+extern "C" int opv_blob_streams(const void* blob, size_t bytes) {
+    BlobHeader h;
+    if (int r = parse_blob(blob, bytes, &h, nullptr)) return r;
+    return (int)h.count;
+}
+
+extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const void* blob, size_t bytes) {
+    if (!c) return fail(OPV_EINVAL, "null context");
+    if (count < 0 || (count > 0 && !dst)) return fail(OPV_EINVAL, "opv_import_streams: bad arguments");
+    BlobHeader h;
+    std::vector<BlobEntry> ents;
+    if (int r = parse_blob(blob, bytes, &h, &ents)) return r;
+    // ---- everything that can refuse the call is decided here, on the host, before the context is touched
+    if ((uint32_t)count != h.count) return fail(OPV_EINVAL, "opv_import_streams: count differs from the streams in the blob (opv_blob_streams)");
+    {
+        std::vector<char> seen((size_t)c->n_streams, 0);
+        for (int i = 0; i < count; ++i) {
+            if (dst[i] < 0 || dst[i] >= c->n_streams) return fail(OPV_EINVAL, "opv_import_streams: destination stream index out of range");
+            if (seen[dst[i]]) return fail(OPV_EINVAL, "opv_import_streams: a destination stream is named twice");
+            seen[dst[i]] = 1;
+        }
+    }
+    const opv_cfg& g = c->cfg;
+    if (h.streaming != g.streaming || h.coherent != g.coherent || h.have_init_offset != g.have_init_offset ||
+        (g.have_init_offset && h.init_offset_hz != g.init_offset_hz) || (g.coherent && h.pll_bw_hz != g.pll_bw_hz))
+        return fail(OPV_EINVAL, "opv_import_streams: the blob was exported under another configuration (streaming / coherent / init_offset_hz / pll_bw_hz)");
+    for (const BlobEntry& e : ents) {
+        if (e.seg_n[SEG_IQ] > g.max_samples) return fail(OPV_ECAPACITY, "opv_import_streams: a stream's unconsumed IQ exceeds the destination's max_samples");
+        if (e.seg_n[SEG_SOFT] > c->cap_soft) return fail(OPV_ECAPACITY, "opv_import_streams: a stream's soft-symbol tail exceeds the destination's ring");
+        if (e.seg_n[SEG_FREC] > c->cap_frames) return fail(OPV_ECAPACITY, "opv_import_streams: more unpopped frames than the destination's frame_capacity");
+    }
+    if (count == 0) return OPV_OK;
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int r = settle_pushes(c)) return r;
+    HIPCHK(hipStreamSynchronize(c->copy_stream));
+    for (int i = 0; i < count; ++i) {                      // (a buffer more on a refused call is not a change of the context)
+        HostStream& hs = c->hs[dst[i]];
+        if (ents[i].seg_n[SEG_IQ] && !hs.d_iq_owned) {
+            if (hipMalloc(&hs.d_iq_owned, (size_t)g.max_samples * 4 + 16384) != hipSuccess) { (void)hipGetLastError(); hs.d_iq_owned = nullptr; return fail(OPV_ENOMEM, "opv_import_streams: IQ buffer"); }
+            hs.iq_cap = g.max_samples;
+            if (!hs.attached) hs.d_iq = hs.d_iq_owned;       // (as push_enqueue leaves a stream's first buffer)
+        }
+    }
+    // ---- tables: one OpvUnpackItem per stream, then the moves out of the staging buffer into the destination's rings
+    std::vector<OpvMove> mv;
+    std::vector<OpvUnpackItem> items((size_t)count);
+    if (int r = mig_buffers(c, (size_t)h.payload_bytes, 0)) return r;
+    for (int i = 0; i < count; ++i) {
+        const BlobEntry& e = ents[i];
+        const HostStream& hs = c->hs[dst[i]];
+        const OpvStream& ini = c->initial[dst[i]];
+        OpvUnpackItem& it = items[i];
+        std::memset(&it, 0, sizeof it);
+        OpvStream& st = it.st;
+        st = e.st;
+        st.iq = hs.d_iq_owned;
+        st.soft = ini.soft; st.cap_soft = ini.cap_soft;
+        st.frec = ini.frec; st.events = ini.events; st.chunk_log = ini.chunk_log;
+        st.frames = ini.frames; st.metrics = ini.metrics; st.fscale = ini.fscale;
+        st.cap_frames = ini.cap_frames; st.cap_events = ini.cap_events; st.cap_chunks = ini.cap_chunks;
+        it.stream = (uint32_t)dst[i];
+        it.live_first = e.popped % ini.cap_frames;
+        it.live_n = (uint32_t)e.seg_n[SEG_FREC];
+        char* base = (char*)c->d_mig + e.off;
+        if (e.seg_n[SEG_IQ]) ring_moves(&mv, (char*)hs.d_iq_owned, 4, e.seg_n[SEG_IQ], 0, e.seg_n[SEG_IQ], base + e.seg_off[SEG_IQ], true);
+        ring_moves(&mv, (char*)st.soft, kSegElem[SEG_SOFT], st.cap_soft, e.soft_first, e.seg_n[SEG_SOFT], base + e.seg_off[SEG_SOFT], true);
+        ring_moves(&mv, (char*)st.frec, kSegElem[SEG_FREC], st.cap_frames, e.popped, e.seg_n[SEG_FREC], base + e.seg_off[SEG_FREC], true);
+        ring_moves(&mv, (char*)st.frames, kSegElem[SEG_FRAMES], st.cap_frames, e.popped, e.seg_n[SEG_FRAMES], base + e.seg_off[SEG_FRAMES], true);
+        ring_moves(&mv, (char*)st.metrics, kSegElem[SEG_METRICS], st.cap_frames, e.popped, e.seg_n[SEG_METRICS], base + e.seg_off[SEG_METRICS], true);
+        ring_moves(&mv, (char*)st.fscale, kSegElem[SEG_FSCALE], st.cap_frames, e.popped, e.seg_n[SEG_FSCALE], base + e.seg_off[SEG_FSCALE], true);
+        // the two lossy logs: the newest entries the destination's ring holds
+        const uint64_t ne = e.seg_n[SEG_EVENTS] < st.cap_events ? e.seg_n[SEG_EVENTS] : st.cap_events, se = e.seg_n[SEG_EVENTS] - ne;
+        ring_moves(&mv, (char*)st.events, kSegElem[SEG_EVENTS], st.cap_events, e.events_first + se, ne, base + e.seg_off[SEG_EVENTS] + se * kSegElem[SEG_EVENTS], true);
+        const uint64_t nc = e.seg_n[SEG_CHUNKS] < st.cap_chunks ? e.seg_n[SEG_CHUNKS] : st.cap_chunks, sc = e.seg_n[SEG_CHUNKS] - nc;
+        ring_moves(&mv, (char*)st.chunk_log, kSegElem[SEG_CHUNKS], st.cap_chunks, e.chunks_first + sc, nc, base + e.seg_off[SEG_CHUNKS] + sc * kSegElem[SEG_CHUNKS], true);
+    }
+    const size_t items_bytes = (items.size() * sizeof(OpvUnpackItem) + 15u) & ~(size_t)15u;
+    if (int r = mig_buffers(c, (size_t)h.payload_bytes, items_bytes + mv.size() * sizeof(OpvMove))) return r;
+    std::memcpy(c->h_mig_tab, items.data(), items.size() * sizeof(OpvUnpackItem));
+    if (!mv.empty()) std::memcpy((char*)c->h_mig_tab + items_bytes, mv.data(), mv.size() * sizeof(OpvMove));
+    void* d_tab = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&d_tab, c->h_mig_tab, 0));
+    // ---- ONE copy and ONE launch on the context's stream: behind the rounds in flight, in front of the next one
+    if (int r = mig_time(c, false)) return r;
+    if (h.payload_bytes) HIPCHK(hipMemcpyAsync(c->d_mig, (const char*)blob + h.payload_off, (size_t)h.payload_bytes, hipMemcpyHostToDevice, c->stream));
+    k_stream_unpack<<<mig_grid(items.size() + mv.size()), 256, 0, c->stream>>>(c->d_streams, c->d_counts, (const OpvUnpackItem*)d_tab, (uint32_t)items.size(),
+                                                                             (const OpvMove*)((char*)d_tab + items_bytes), (uint32_t)mv.size());
+    HIPCHK(hipGetLastError());
+    if (int r = mig_time(c, true)) return r;
+    for (int i = 0; i < count; ++i) {                      // the host's half of the slot: opv_reset_stream, then the load
+        const BlobEntry& e = ents[i];
+        HostStream& hs = c->hs[dst[i]];
+        HostStream n;
+        n.d_iq_owned = hs.d_iq_owned;
+        n.d_iq_alt = hs.d_iq_alt;
+        n.iq_cap = hs.iq_cap;
+        n.d_iq = hs.d_iq_owned;
+        n.n_avail = e.seg_n[SEG_IQ];
+        n.eof = e.eof;
+        n.dirty = true;                                    // (iq / n_avail / eof and the cursors reach the kernels with the next round's inputs too)
+        n.search_seen = e.search_seen != 0;
+        n.last_round_avail = e.last_round_avail;
+        n.popped = e.popped;
+        n.events_popped = e.events_popped;
+        n.events_dropped = e.events_dropped;
+        n.decoded = e.decoded;
+        n.perfect = e.perfect;
+        n.soft_floor = e.soft_first;
+        n.chunk_floor = e.chunks_first + (uint32_t)(e.seg_n[SEG_CHUNKS] - (e.seg_n[SEG_CHUNKS] < c->cap_chunks ? e.seg_n[SEG_CHUNKS] : c->cap_chunks));
+        hs = n;
+    }
+    c->mirror_valid = false;
+    c->maybe_stalled = true;
+    HIPCHK(hipStreamSynchronize(c->stream));               // the blob is the caller's again
+    return OPV_OK;
 }

@@ -134,6 +134,25 @@ struct OpvTieStage {
     OpvTieSlot slot[1];       // [slots]
 };
 
+// ---- stream migration (k_stream_pack.hip; opv_capi.hip: opv_export_streams / opv_import_streams) ----
+// Both kernels run off tables in PINNED host memory that the host has checked entry by entry. A move is one contiguous run of at
+// most OPV_MOVE_PIECE bytes: the host un-wraps every ring segment into runs and cuts long runs (the IQ tail) into pieces, so that
+// one stream's 347 KB already spread over a dozen workgroups and a drain of thousands of streams is still one launch.
+#define OPV_MOVE_PIECE 32768u
+struct OpvMove {
+    const void* src;
+    void* dst;
+    uint32_t bytes;
+    uint32_t pad;
+};
+struct OpvUnpackItem {
+    OpvStream st;             // the imported carry, re-based onto the destination slot's pools and rings
+    uint32_t stream;          // destination slot
+    uint32_t live_first;      // ring position of the first unpopped frame ...
+    uint32_t live_n;          // ... and how many: every OTHER slot of the metrics ring is filled with INT32_MIN, as opv_reset_stream does
+    uint32_t pad;
+};
+
 struct OpvGlobalCfg {
     int32_t streaming;
     int32_t have_init_offset;

@@ -34,6 +34,7 @@ EXPORTS = [
     "opv_comm_destroy", "opv_gather_frames", "opv_gather_frames_all", "opv_tap_soft", "opv_tap_chunks",
     "opv_tap_offset_energies", "opv_offset_ties_on_host", "opv_offset_ties_decided_on_host", "opv_offset_ties_left_to_device", "opv_tap_wave_info", "opv_tap_occupancy", "opv_decode_payloads", "opv_tx_bert_frame", "opv_tx_bert_frames", "opv_tx_modulated_samples",
     "opv_tx_modulate", "opv_tap_tx_checkpoints", "opv_frontend_kernel", "opv_channel_device", "opv_resample_device", "opv_enable_timing", "opv_kernel_times", "opv_tx_modulate_device", "opv_tx_modulate_device_to_host",
+    "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
 ]
 
@@ -168,6 +169,12 @@ def lib():
         L.opv_tx_modulate_device.restype = C.c_long
         L.opv_tx_modulate_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.opv_kernel_times.argtypes = [C.c_void_p, C.c_void_p]
+        L.opv_export_size.restype = C.c_size_t
+        L.opv_export_size.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.opv_export_streams.restype = C.c_long
+        L.opv_export_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_import_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_blob_streams.argtypes = [C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -290,6 +297,21 @@ class TxStream:
             pass
 
 
+def _blob_view(blob):
+    """a blob as a contiguous uint8 array: bytes / bytearray / memoryview (a file, a socket) or an array"""
+    if isinstance(blob, np.ndarray):
+        return np.ascontiguousarray(blob).view(np.uint8).reshape(-1)
+    return np.frombuffer(blob, np.uint8)
+
+
+def blob_streams(blob):
+    """opv_blob_streams: streams in an exported blob (host only: needs no device); raises on anything that is not one"""
+    if blob is None:
+        return _chk(lib().opv_blob_streams(None, 0))
+    b = _blob_view(blob)
+    return _chk(lib().opv_blob_streams(b.ctypes.data if b.size else None, b.size))
+
+
 # ---------------------------------------------------------------- receiver
 class Demod:
     """n_streams independent receivers on one GPU (mirrors the three reference objects
@@ -361,6 +383,23 @@ class Demod:
 
     def reset(self, stream=-1):
         _chk(lib().opv_reset_stream(self.h, stream))
+
+    def export_streams(self, streams):
+        """opv_export_streams: a snapshot of the listed live streams as one self-describing blob (uint8 array) that
+        import_streams of another context - same or other process, device or stream count - continues from"""
+        ids = (C.c_int * len(streams))(*[int(s) for s in streams])
+        cap = lib().opv_export_size(self.h, len(streams), ids)
+        if cap == 0:
+            raise OpvError(f"opv_export_size: {lib().opv_last_error().decode()}")
+        blob = np.empty(cap, np.uint8)
+        n = _chk(lib().opv_export_streams(self.h, len(streams), ids, blob.ctypes.data, cap))
+        return blob[:n]
+
+    def import_streams(self, dst_streams, blob):
+        """opv_import_streams: blob's streams into the listed slots of this context (each reset first)"""
+        b = _blob_view(blob)
+        ids = (C.c_int * len(dst_streams))(*[int(s) for s in dst_streams])
+        _chk(lib().opv_import_streams(self.h, len(dst_streams), ids, b.ctypes.data if b.size else None, b.size))
 
     def enable_timing(self, on=True):
         _chk(lib().opv_enable_timing(self.h, int(on)))

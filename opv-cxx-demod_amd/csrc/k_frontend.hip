@@ -67,15 +67,9 @@
 
 #include <type_traits>
 
-#include "opv_device.h"
+#include "k_frontend_common.h"
 
 namespace {
-
-constexpr double kPi = 3.14159265358979323846;  // ref :43
-constexpr double kTwoPi = 2.0 * kPi;            // ref :44
-constexpr double kFs = 2168000.0;               // ref :40
-constexpr double kSymRate = 2168000.0 / 40.0;   // ref :41
-constexpr double kDeltaPerHz = kTwoPi / kFs;    // d = 2 pi fo / Fs (ref :210-211, :305-306)
 
 constexpr uint32_t kTile = OPV_TILE_SAMPLES;    // 2048 samples
 constexpr uint32_t kRing = 2 * kTile;           // 4096 samples, two tile slots, slot = index & 4095
@@ -110,8 +104,6 @@ constexpr uint32_t kHelperSpins = 1u << 22;          // helper waiting for a fre
 static_assert(kRbLdsBase + kF64FlagOff + 16 == OPV_RB_LDS_F64, "launch size of the fp64-ring shape");
 static_assert(kF64Ring % kF64Chunk == 0 && (kF64Ring & (kF64Ring - 1)) == 0, "chunks tile the power-of-two ring");
 
-typedef __attribute__((address_space(1))) double gdouble;
-typedef __attribute__((address_space(1))) unsigned char gbyte;
 // LDS is addressed through address-space-3 pointers throughout, so that offsets from the constant base of k_msk_frontend_rb's
 // dynamic allocation fold into the ds_read / ds_write offset fields
 typedef double d2v __attribute__((ext_vector_type(2)));
@@ -119,10 +111,6 @@ typedef __attribute__((address_space(3))) unsigned char lbyte;
 typedef __attribute__((address_space(3))) int lint;
 typedef __attribute__((address_space(3))) double ldouble;
 typedef __attribute__((address_space(3))) d2v ld2v;
-
-__device__ inline int dlo(double v) { return __double2loint(v); }
-__device__ inline int dhi(double v) { return __double2hiint(v); }
-__device__ inline double mkd(int hi, int lo) { return __hiloint2double(hi, lo); }
 
 // A-values end in lanes 0..31, B-values in lanes 32..63: returns A[l]+A[l+32] | B[l-32]+B[l]
 __device__ inline double swap32_add(double a, double b) {
@@ -149,7 +137,10 @@ __device__ inline double readlane_d(double v, int l) {
 __device__ inline bool uni_lt(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 4 /*FCMP_OLT*/) != 0ull; }
 __device__ inline bool uni_eq(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 1 /*FCMP_OEQ*/) != 0ull; }
 
-__device__ inline double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
+// instantiations of the per-symbol body (see `symbol` in the kernel)
+struct TagFirst { static constexpr bool first = true, wide = true; };     // first symbol of a demodulate() call
+struct TagSecond { static constexpr bool first = false, wide = true; };   // second symbol under an out-of-range -o
+struct TagSteady { static constexpr bool first = false, wide = false; };  // everything else
 
 // X = exp(j x), x = kfs * fo, |x| <= 0.284 (fo within the AFC clamp of +/-2000 Hz, |kf| <= 49):
 //   sin x = x + x u q(u),  cos x = 1 + u r(u),  u = x^2,
@@ -159,16 +150,7 @@ __device__ inline double clampd(double v, double lo, double hi) { return fmin(fm
 // clamp) was measured too - 9 cycles per symbol faster still - and is NOT used: on the 6 dB / -2 kHz fixture it moved the
 // integer printed by one `raw=%.0f` tracker line (tests/test_gpu_parity.py::test_noisy_configs_vs_reference_fixtures).
 // One asm block: the constants stay in registers as written and hipcc's hazard recogniser does
-// not pad between the dependent FMAs.
-// instantiations of the per-symbol body (see `symbol` in the kernel)
-struct TagFirst { static constexpr bool first = true, wide = true; };     // first symbol of a demodulate() call
-struct TagSecond { static constexpr bool first = false, wide = true; };   // second symbol under an out-of-range -o
-struct TagSteady { static constexpr bool first = false, wide = false; };  // everything else
-
-struct PrevSums {
-    double a, b, c, d;  // on-time P1..P4
-    double x40c, x40s;  // X[40] = exp(j 40 d) of that symbol
-};
+// not pad between the dependent FMAs. (k_frontend_common.h: expj_small10 is the other mappings' plain ten-coefficient pair.)
 struct SinCosK {
     double s0, s1, s2, s3;      // q(u) low -> high (cubic)
     double c0, c1, c2, c3, c4;  // r(u) low -> high (degree 4)
@@ -190,58 +172,6 @@ __device__ inline void expj_small(double kfs, double fo, const SinCosK& k, doubl
         : [x] "=&v"(x), [u] "=&v"(u), [p] "=&v"(p), [r] "=&v"(r), [t] "=&v"(t), [xs] "=&v"(xs), [xc] "=&v"(xc)
         : [kfs] "v"(kfs), [fo] "v"(fo), [s0] "v"(k.s0), [s1] "v"(k.s1), [s2] "v"(k.s2), [s3] "v"(k.s3),
           [c0] "v"(k.c0), [c1] "v"(k.c1), [c2] "v"(k.c2), [c3] "v"(k.c3), [c4] "v"(k.c4));
-}
-
-// Digital silence on either side of the phase detector (rare, wave-uniform, kept out of line).
-// The reference's product dom * conj(prev) (ref :299) is then an exact zero whose SIGNS decide
-// std::arg: atan2(+0,-0) = pi, everything else +/-0 (IEEE). Working the signs through its
-// complex multiply:
-//   dom == (+0,+0), prev != 0 : pi iff Re(prev) < 0 and Im(prev) < 0
-//   prev == (+0,+0), dom != 0 : pi iff Re(dom)  < 0 and Im(dom)  < 0
-//   both zero                  : 0
-// where dom/prev are the reference's correlations, i.e. ours times the absolute LO phasor it
-// carries: c_t(k) = S_t(k) conj(E_t(k)), prev_t = P_t conj(E_t(k)), P_t = S_t(k-1) (-/+ j) X40(k-1),
-// E_t(k) = exp(j(-/+ k pi/2 + (80 pi/Fs) sum_{j<k} fo_j)), rebuilt here from the running sum of fo
-// (fo_sum: over the symbols BEFORE this one; ksym: their number). Checked on 598 gap edges by
-// tests/test_gpu_parity.py::test_many_silence_gaps_signed_zero_rule.
-//
-// The one input class that is NOT reproducible is counted here (`ties`, reported as
-// opv_stream_state.edge_ties): a window with exactly ONE non-zero tap, i.e. the first symbol a burst
-// touches or the last one it leaves. Both tone energies are then |s|^2 in exact arithmetic (P1 P2 ==
-// P3 P4, soft = 4 (P3 P4 - P1 P2) = 0) and the reference's e1 > e2 (ref :272/:291) is decided by the
-// rounding of its own cos^2 + sin^2 at the accumulated LO phase, which this kernel does not carry. Such a
-// symbol always has digital silence on one side, so it passes through this routine either as `cur`
-// (leading edge: prev is zero) or as `prv` (trailing edge: dom is zero) - no cost on the symbol path.
-__device__ inline bool tone_tie(double p1, double p2, double p3, double p4) {
-    const double x = p1 * p2, y = p3 * p4;
-    return (p1 != 0.0 || p2 != 0.0 || p3 != 0.0 || p4 != 0.0) && fabs(y - x) <= 1e-12 * (fabs(x) + fabs(y));
-}
-// Returns {pd, 1.0 if such a tie was seen else 0.0} (by value: no stack slot on the caller's side).
-__device__ __noinline__ double2 silence_pd(double dr, double di, PrevSums prv, bool dom1, double fo_sum, uint64_t ksym,
-                                           double c1, double c2, double c3, double c4) {
-    const double pr = dom1 ? prv.a + prv.b : prv.a - prv.b, pi = dom1 ? prv.c - prv.d : prv.c + prv.d;
-    const bool dom_zero = (dr == 0.0 && di == 0.0), prev_zero = (pr == 0.0 && pi == 0.0);
-    if (dom_zero == prev_zero) return make_double2(0.0, 0.0);
-    const double tie = (prev_zero ? tone_tie(c1, c2, c3, c4) : tone_tie(prv.a, prv.b, prv.c, prv.d)) ? 1.0 : 0.0;
-    double th = (80.0 * kPi / kFs) * fo_sum;
-    th -= kTwoPi * rint(th / kTwoPi);
-    double sn, cs;
-    sincos(th, &sn, &cs);
-    // multiply by (-/+ j)^k : tone 1 rotates by -pi/2 per symbol, tone 2 by +pi/2
-    const unsigned q = (unsigned)((dom1 ? (4u - (unsigned)(ksym & 3u)) : (unsigned)(ksym & 3u)) & 3u);
-    double er2 = cs, ei2 = sn;
-    if (q == 1u) { er2 = -sn; ei2 = cs; }
-    else if (q == 2u) { er2 = -cs; ei2 = -sn; }
-    else if (q == 3u) { er2 = sn; ei2 = -cs; }
-    double vr = dr, vi = di;
-    if (dom_zero) {                                 // P = S_prev * (-/+ j) * X40_prev
-        const double jr = dom1 ? pi : -pi, ji = dom1 ? -pr : pr;
-        vr = jr * prv.x40c - ji * prv.x40s;
-        vi = jr * prv.x40s + ji * prv.x40c;
-    }
-    const double qr = vr * er2 + vi * ei2;          // v * conj(E)
-    const double qi = vi * er2 - vr * ei2;
-    return make_double2((qr < 0.0 && qi < 0.0) ? kPi : 0.0, tie);
 }
 
 }  // namespace

@@ -40,15 +40,9 @@
 
 #include <type_traits>
 
-#include "opv_device.h"
+#include "k_frontend_common.h"
 
 namespace {
-
-constexpr double kPi = 3.14159265358979323846;  // ref :43
-constexpr double kTwoPi = 2.0 * kPi;            // ref :44
-constexpr double kFs = 2168000.0;               // ref :40
-constexpr double kSymRate = 2168000.0 / 40.0;   // ref :41
-constexpr double kDeltaPerHz = kTwoPi / kFs;    // d = 2 pi fo / Fs (ref :210-211, :305-306)
 
 constexpr uint32_t kRingSamples = 1024;
 constexpr uint32_t kRingBytes = kRingSamples * 4;   // 4096
@@ -66,26 +60,8 @@ constexpr uint32_t kTabOff = 4 * kRowBytes;         // 17408
 // LDS per workgroup: WPB x kTabOff + the atan table (257 x 48 B) = 29 680 B for one wave (five workgroups per CU), 81 712 B for four (two)
 static_assert(kTabOff % 16 == 0, "16-byte LDS alignment");
 
-typedef __attribute__((address_space(1))) double gdouble;
-typedef __attribute__((address_space(1))) unsigned char gbyte;
-
-__device__ inline int dlo(double v) { return __double2loint(v); }
-__device__ inline int dhi(double v) { return __double2hiint(v); }
-__device__ inline double mkd(int hi, int lo) { return __hiloint2double(hi, lo); }
-
-// four row sums in lockstep: a DPP read needs two wait states behind the VALU write of its source, and one sum's rotation
-// steps are a dependent chain (hipcc pads every step with s_nop 1) - the other three sums' instructions fill the slots
-template <int CTRL>
-__device__ inline void dpp_add4(double& a, double& b, double& c, double& d) {
-    const int al = __builtin_amdgcn_mov_dpp(dlo(a), CTRL, 0xF, 0xF, true), ah = __builtin_amdgcn_mov_dpp(dhi(a), CTRL, 0xF, 0xF, true);
-    const int bl = __builtin_amdgcn_mov_dpp(dlo(b), CTRL, 0xF, 0xF, true), bh = __builtin_amdgcn_mov_dpp(dhi(b), CTRL, 0xF, 0xF, true);
-    const int cl = __builtin_amdgcn_mov_dpp(dlo(c), CTRL, 0xF, 0xF, true), ch = __builtin_amdgcn_mov_dpp(dhi(c), CTRL, 0xF, 0xF, true);
-    const int dl = __builtin_amdgcn_mov_dpp(dlo(d), CTRL, 0xF, 0xF, true), dh = __builtin_amdgcn_mov_dpp(dhi(d), CTRL, 0xF, 0xF, true);
-    __builtin_amdgcn_sched_barrier(0);
-    a += mkd(ah, al); b += mkd(bh, bl); c += mkd(ch, cl); d += mkd(dh, dl);
-    __builtin_amdgcn_sched_barrier(0);
-}
-// Two rotation steps leave the row's four partial sums in its lanes 0..3 (every lane l holds the one of l mod 4); the
+// Four row sums in lockstep (dpp_add4, one rotation step per call). Two rotation steps leave the row's four partial sums in
+// its lanes 0..3 (every lane l holds the one of l mod 4); the
 // DP-ALU DPP forms finish the job in 16 instructions instead of the 24 of two more rotation steps: v_mov_b64_dpp
 // row_newbcast:0 + three v_fmac_f64_dpp row_newbcast:n with a factor of 1.0 per value (k_frontend.hip: symbol_r,
 // scripts/microbench/dpp64.hip). The four adds of the step before are the wait states the first DPP reads need.
@@ -106,61 +82,6 @@ __device__ inline void row_sum4(double& a, double& b, double& c, double& d, doub
 #undef OPV_B4
     a = ra; b = rb; c = rc; d = rd;
 }
-__device__ inline double clampd(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
-
-// exp(j x), |x| <= 0.284: same near-minimax pair as k_frontend.hip (abs error 1e-19 / 1.3e-18)
-__device__ inline void expj_small(double x, double& xs, double& xc) {
-    const double u = x * x;
-    double p = fma(-0x1.add325df5e3b5p-26, u, 0x1.71de256e9bdffp-19);
-    double r = fma(-0x1.276f06eab6283p-22, u, 0x1.a019dfaa26924p-16);
-    p = fma(p, u, -0x1.a01a019da51d6p-13);
-    r = fma(r, u, -0x1.6c16c16818f3fp-10);
-    p = fma(p, u, 0x1.1111111110f73p-7);
-    r = fma(r, u, 0x1.5555555555014p-5);
-    p = fma(p, u, -0x1.5555555555555p-3);
-    r = fma(r, u, -0x1.0000000000000p-1);
-    xc = fma(r, u, 1.0);
-    xs = fma(x * u, p, x);
-}
-
-struct PrevSums {
-    double a, b, c, d;  // on-time P1..P4
-    double x40c, x40s;  // X[40] = exp(j 40 d) of that symbol
-};
-
-// std::arg on digital silence (ref :299): see k_frontend.hip::silence_pd for the derivation.
-// `ties` counts the windows with exactly one non-zero tap (opv_stream_state.edge_ties), as there.
-__device__ inline bool tone_tie(double p1, double p2, double p3, double p4) {
-    const double x = p1 * p2, y = p3 * p4;
-    return (p1 != 0.0 || p2 != 0.0 || p3 != 0.0 || p4 != 0.0) && fabs(y - x) <= 1e-12 * (fabs(x) + fabs(y));
-}
-__device__ __noinline__ double2 silence_pd_x4(double dr, double di, double pa, double pb, double pc, double pd_, double x40c,
-                                               double x40s, bool dom1, double fo_sum, uint32_t ksym,
-                                               double c1, double c2, double c3, double c4) {
-    const double pr = dom1 ? pa + pb : pa - pb, pi = dom1 ? pc - pd_ : pc + pd_;
-    const bool dom_zero = (dr == 0.0 && di == 0.0), prev_zero = (pr == 0.0 && pi == 0.0);
-    if (dom_zero == prev_zero) return make_double2(0.0, 0.0);
-    const double tie = (prev_zero ? tone_tie(c1, c2, c3, c4) : tone_tie(pa, pb, pc, pd_)) ? 1.0 : 0.0;
-    double th = (80.0 * kPi / kFs) * fo_sum;
-    th -= kTwoPi * rint(th / kTwoPi);
-    double sn, cs;
-    sincos(th, &sn, &cs);
-    const unsigned q = (unsigned)((dom1 ? (4u - (ksym & 3u)) : (ksym & 3u)) & 3u);
-    double er2 = cs, ei2 = sn;
-    if (q == 1u) { er2 = -sn; ei2 = cs; }
-    else if (q == 2u) { er2 = -cs; ei2 = -sn; }
-    else if (q == 3u) { er2 = sn; ei2 = -cs; }
-    double vr = dr, vi = di;
-    if (dom_zero) {
-        const double jr = dom1 ? pi : -pi, ji = dom1 ? -pr : pr;
-        vr = jr * x40c - ji * x40s;
-        vi = jr * x40s + ji * x40c;
-    }
-    const double qr = vr * er2 + vi * ei2;
-    const double qi = vi * er2 - vr * ei2;
-    return make_double2((qr < 0.0 && qi < 0.0) ? kPi : 0.0, tie);
-}
-
 }  // namespace
 
 // this translation unit's own image of the angle table (opv_atan2.h: kOpvAtanTabQ): every .hip file is compiled to a
@@ -331,8 +252,8 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
         }
         // ---- LO: X[m] for m = t - 10 + 16 q ---------------------------------------------------
         double xs[4], xc[4], s16, c16;
-        expj_small(kfs0 * fo, xs[0], xc[0]);
-        expj_small((16.0 * kDeltaPerHz) * fo, s16, c16);
+        expj_small10(kfs0 * fo, xs[0], xc[0]);
+        expj_small10((16.0 * kDeltaPerHz) * fo, s16, c16);
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
             xc[q] = fma(xc[q - 1], c16, -(xs[q - 1] * s16));
@@ -426,9 +347,9 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
             pd = fma(sx, pd, fma(-sx, 1.57079632679489661923, 1.57079632679489661923));
             pd = mkd((dhi(pd) & 0x7fffffff) | (dhi(cy) & (int)0x80000000), dlo(pd));
             if (sum == 0.0) {                                // digital silence on either side
-                const double2 sp = silence_pd_x4(dr, di, pv.a, pv.b, pv.c, pv.d, pv.x40c, pv.x40s, soft < 0.0, fo_sum,
-                                                 (uint32_t)n_soft + (((soft_off - soft_off0) & soft_bmask) >> 3),
-                                                 P1o, P2o, P3o, P4o);
+                const double2 sp = silence_pd(dr, di, pv, soft < 0.0, fo_sum,
+                                              (uint32_t)n_soft + (((soft_off - soft_off0) & soft_bmask) >> 3),
+                                              P1o, P2o, P3o, P4o);
                 pd = sp.x;
                 edge_ties += (uint32_t)sp.y;
             }

@@ -1,8 +1,8 @@
 """GPU: every stream-to-wave mapping of the front end - k_frontend.hip (one stream per wave: fp64 ring, int16 ring, _rb_wg4),
 k_frontend_x4.hip (four per wave) and k_frontend_x16.hip (sixteen per wave, one per DPP quad: _x16, _x16_wg4, _x16_wg8) - held to
-the ORACLE on ONE hostile capture set. The three files each carry their own sample ring and refill rule, their own digital-silence
-/ signed-zero rule (silence_pd, silence_pd_x16), their own one-tap-window counter and their own per-row chunk scheduling under exec
-masks; the input classes this suite was built on reached only some of them. No comparison here is against another mapping of the
+the ORACLE on ONE hostile capture set. The three files each carry their own sample ring and refill rule, their own call site of the one
+digital-silence / signed-zero rule (k_frontend_common.h: silence_pd), their own one-tap-window counter and their own per-row chunk
+scheduling under exec masks; the input classes this suite was built on reached only some of them. No comparison here is against another mapping of the
 product.
 
 The set (hostile_captures, 32 captures, 900 samples to 30 chunks, fixed seeds, built on the CPU from the oracle's transmit chain):
@@ -254,8 +254,8 @@ def run_shape(amd, monkeypatch, hostile, shape, pos, streaming, tag):
 def test_hostile_set_on_every_launch_shape(amd, hostile, monkeypatch, shape, arrangement):
     """Every launch shape a small context can reach (kernel name asserted) x the hostile set, every stream against the oracle by
     its class (check_capture), nothing stalled: -s mode in the identity arrangement and in one where every capture has another row
-    / quad, another wave and other neighbours (permuted), batch mode in the latter - which is where silence_pd_x16's signed-zero
-    decision, and x4's, meet the gapped captures in batch mode for the first time."""
+    / quad, another wave and other neighbours (permuted), batch mode in the latter - which is where silence_pd's signed-zero
+    decision, called from x16 and from x4, meets the gapped captures in batch mode for the first time."""
     N = len(hostile["caps"])
     pos = list(range(N)) if arrangement.startswith("identity") else permuted(N)
     run_shape(amd, monkeypatch, hostile, shape, pos, not arrangement.endswith("batch"), f"{shape} {arrangement}")

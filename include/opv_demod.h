@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
+                               still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
                                7: opv_process never waits on the host again - the host-libm decision of offset-search near-ties runs as a host
                                function IN STREAM ORDER between the search and the front-end (+ opv_offset_ties_decided_on_host, opv_offset_ties_left_to_device); opv_set_frontend
                                takes 0 / 1 / 4 / 16 only (the comparison mappings are gone); opv_tap_occupancy's third entry is k_msk_frontend_x16_wg4;
@@ -174,6 +175,54 @@ int opv_push_iq_batch(opv_ctx* ctx, int count, const int* streams, const int16_t
 int opv_push_iq_batch_async(opv_ctx* ctx, int count, const int* streams, const int16_t* const* iq_interleaved,
                             const size_t* n_samples);
 int opv_push_wait(opv_ctx* ctx);
+/* ---- wideband front door: ONE wide capture in, K of a context's streams fed ------------------------------------------------
+ * Replaces nothing in the reference, which starts at one channel's baseband. A radio delivers one wideband capture with many OPV
+ * channels side by side; an opv_wb object is a bank of K digital down-converters on the device, so that the capture crosses PCIe
+ * once and each channel arrives in its stream's device buffer as if it had been pushed with opv_push_iq. The arithmetic is
+ * integer-exact and independent of summation order (tests/test_gpu_wideband.py holds the device to a numpy int64 model with ==):
+ *   wide samples x[n] = (I, Q) int16 at decim x 2 168 000 S/s, n = 0 at the first sample pushed into the object, a = first_sample + n;
+ *   per channel k: inc_k = (uint32) llrint(centre_hz[k] / (decim x 2 168 000) x 2^32) (modulo 2^32: negative centres wrap),
+ *     phi = (uint32)(a x inc_k) (a closed form: no accumulator is carried), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095] with
+ *     T[i] = (int16) lrint(32767 cos(2 pi i / 4096)) (opv_wb_lo_table); the channel at +centre_hz comes down to 0:
+ *     mr = I c + Q s, mi = Q c - I s (int32); acc[r] = sum_t taps[t] m[r decim - t], m[n] = 0 for n < 0, for r = 0 .. ceil(N / decim) - 1
+ *     after N wide samples in all; output per component clamp(floor((acc + 2^(out_shift - 1)) / 2^out_shift), -32768, 32767) (out_shift = 0: no rounding term).
+ *   Limits (anything else is OPV_EINVAL from opv_wb_plan / opv_wb_create): 1 <= decim <= 16, 1 <= n_taps <= 1024, 1 <= n_channels <= 256,
+ *     0 <= out_shift <= 40, sum |taps| <= 2^21 (so |acc| < 2^52: exact in int64 and in fp64 alike), finite centres.
+ * The only state between pushes is the last n_taps - 1 wide samples and the count N: any split of a capture into pushes gives the
+ * bytes of one push. The object does NOT migrate (opv_export_streams moves its streams like any others): rebuild it at the
+ * destination with first_sample + N as its first_sample - and mind that its n = 0 then starts with an empty filter history.
+ * opv_wb_plan (host only, no device): validates cfg, centres and taps and writes the K increments. opv_wb_lo_table, opv_wb_outputs
+ * (ceil(N / decim): outputs per channel after n_wide_total samples; 0 for a bad cfg): host only.
+ * opv_wb_create: streams[k] of ctx is fed by channel k. OPV_EINVAL for an index out of range, a stream named twice, or a stream a
+ * live wideband object of the context feeds already. Destroy the object before its context; one that outlives it is
+ * detached: its pushes and opv_wb_flush answer OPV_ESTATE, and opv_wb_destroy frees only what is the object's own.
+ * opv_wb_push / _async / _device: n_wide samples (4-byte aligned; host memory pinned or pageable - a pinned block is read in place
+ * across PCIe by the one k_wb_ddc launch that serves all K channels, a pageable one is staged first - or a device pointer). Every
+ * channel's output count is known on the host, and room for it is reserved in all K streams before anything is launched, under the
+ * rules of opv_push_iq: a flushed or attached stream is OPV_ESTATE, a stream without room even after compaction OPV_ECAPACITY - and
+ * the call has then changed NOTHING, in any stream or in the object. opv_wb_push and opv_wb_push_device return when the block
+ * has been read; opv_wb_push_async returns once the work is enqueued, like opv_push_iq_batch_async: the block stays valid until
+ * opv_push_wait, opv_process may be called in between and queues behind the push on the device. Asynchronous pushes - of one
+ * object or of several objects of a context - queue behind each other on the device without a host wait in between.
+ * Streams fed this way are ordinary pushed streams for pop, state, taps and export; opv_reset_stream on one is allowed, the
+ * object goes on feeding it. opv_wb_flush: opv_flush on each of its streams. */
+typedef struct opv_wb_cfg {
+    int32_t decim;            /* D: wide samples per output sample */
+    int32_t n_channels;       /* K */
+    int32_t n_taps;           /* L */
+    int32_t out_shift;        /* S */
+    uint64_t first_sample;    /* absolute index of the first wide sample pushed (the LO phase is a function of it) */
+} opv_wb_cfg;
+typedef struct opv_wb opv_wb;
+int opv_wb_plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
+void opv_wb_lo_table(int16_t out4096[4096]);
+size_t opv_wb_outputs(const opv_wb_cfg* cfg, uint64_t n_wide_total);
+int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, const int* streams, const double* centre_hz, const int16_t* taps);
+void opv_wb_destroy(opv_wb* wb);
+int opv_wb_push(opv_wb* wb, const int16_t* iq_wide, size_t n_wide);
+int opv_wb_push_async(opv_wb* wb, const int16_t* iq_wide, size_t n_wide);
+int opv_wb_push_device(opv_wb* wb, const int16_t* d_iq_wide, size_t n_wide);
+int opv_wb_flush(opv_wb* wb);
 /* EOF on a stream: enables the tail processing of :1088-1113 (streaming) or the single
  * whole-capture demodulate of :1166-1173 (batch) at the next opv_process. */
 int opv_flush(opv_ctx* ctx, int stream);
@@ -292,6 +341,9 @@ int opv_gather_frames_all(opv_ctx* const* ctxs, void* const* comms, int n, int r
 /* ---- parity taps (debug): the intermediates the 1e-5 contract is checked on ------------ */
 /* soft symbols by absolute symbol index; only the retained tail of a long pushed stream is available */
 long opv_tap_soft(opv_ctx* ctx, int stream, uint64_t first_symbol, double* out, size_t cap);
+/* the IQ a pushed (or wideband-fed) stream holds on the device, by absolute sample index: up to cap samples (2 int16 each) from
+ * first_sample; returns the number copied - 0 outside what the stream's buffer still retains. Implies opv_push_wait + opv_sync. */
+long opv_tap_iq(opv_ctx* ctx, int stream, uint64_t first_sample, int16_t* out, size_t cap);
 /* per demodulate() call, starting at call number first_chunk: {freq_offset, timing_freq, mu,
  * leftover, n_symbols}. The log is a ring of the most recent calls. */
 long opv_tap_chunks(opv_ctx* ctx, int stream, uint32_t first_chunk, double* out5, size_t cap_chunks);

@@ -23,6 +23,7 @@
 #include "opv_device.h"
 #include "opv_offset_host.h"
 #include "opv_tx_internal.h"
+#include "opv_wb_internal.h"
 
 extern "C" __global__ void k_offset_search(OpvStream*, OpvGlobalCfg, const double*, uint32_t*);
 extern "C" __global__ void k_tie_collect(const OpvStream*, const uint32_t*, uint32_t, uint32_t, uint32_t, OpvTieStage*);
@@ -250,6 +251,7 @@ struct opv_ctx {
     // behind push_ev on the device, every other push entry point waits on the host first
     bool push_pending = false;
     hipEvent_t push_ev = nullptr;
+    OpvWbTie wb;                        // which streams live wideband objects feed (opv_wideband.hip); outlives the context for them
     // stream migration (opv_export_streams / opv_import_streams): device staging buffer + pinned tables of k_stream_pack.hip, grow-only
     void* d_mig = nullptr;
     void* h_mig_tab = nullptr;
@@ -1958,4 +1960,99 @@ extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const v
     c->maybe_stalled = true;
     HIPCHK(hipStreamSynchronize(c->stream));               // the blob is the caller's again
     return OPV_OK;
+}
+
+// ---- the wideband front door's way in (opv_wb_internal.h; opv_wideband.hip holds the object, k_wideband.hip the kernel) ----------
+int opv_int_fail(int code, const char* what, hipError_t e) { return fail(code, what, e); }
+
+int opv_int_door(opv_ctx* c, OpvCtxDoor* out) {
+    if (!c) return fail(OPV_EINVAL, "null context");
+    if (!c->wb.p) {
+        c->wb.p = std::make_shared<OpvWbShared>();
+        c->wb.p->owned.assign((size_t)c->n_streams, 0);
+    }
+    out->n_streams = c->n_streams;
+    out->device = c->cfg.device;
+    out->copy_stream = c->copy_stream;
+    out->shared = c->wb.p;
+    return OPV_OK;
+}
+
+// (no wait for an asynchronous push still under way: a wideband object's table, carry and staging buffer are its own and are
+// handed on in copy-stream order, and opv_int_push_reserve waits by itself before a tail is moved. So the K-channel pushes of
+// many objects queue up behind each other on the device while the host goes on.)
+int opv_int_push_begin(opv_ctx* c) {
+    HIPCHK(hipSetDevice(c->cfg.device));
+    return OPV_OK;
+}
+
+int opv_int_push_reserve(opv_ctx* c, int count, const int* streams, const uint32_t* n, int** dst) {
+    // push_enqueue's rules, for all streams before anything moves: first what refuses the call ...
+    std::vector<int> full;
+    for (int i = 0; i < count; ++i) {
+        if (int r = check_stream(c, streams[i])) return r;
+        const HostStream& h = c->hs[streams[i]];
+        if (h.attached) return fail(OPV_ESTATE, "stream has an attached device capture");
+        if (h.eof) return fail(OPV_ESTATE, "push after flush");
+        if (n[i] && h.n_avail + n[i] > c->cfg.max_samples) full.push_back(streams[i]);
+    }
+    if (!full.empty()) {
+        HIPCHK(hipStreamSynchronize(c->copy_stream));      // samples enqueued earlier land before a tail is moved
+        if (int r = c->refresh()) return r;
+        for (int i = 0; i < count; ++i) {                  // would compaction make the room? (what compact_stream keeps)
+            const HostStream& h = c->hs[streams[i]];
+            const OpvStream& st = c->mirror[streams[i]];
+            const uint64_t keep = h.d_iq_owned && st.origin >= 16 ? ((st.origin - 16) & ~3ull) : 0;
+            if (n[i] && h.n_avail - keep + n[i] > c->cfg.max_samples)
+                return fail(OPV_ECAPACITY, "opv_cfg.max_samples exceeded (unprocessed samples + this push do not fit; "
+                                           "call opv_process between pushes or raise max_samples)");
+        }
+        // ... then the changes: compaction, lazy allocation, the reservation itself
+        if (full.size() >= 2) { if (int r = compact_streams(c, full)) return r; }
+        else if (int r = compact_stream(c, full[0])) return r;
+    }
+    for (int i = 0; i < count; ++i) {
+        HostStream& h = c->hs[streams[i]];
+        if (!h.d_iq_owned) {
+            h.iq_cap = c->cfg.max_samples;
+            if (hipMalloc(&h.d_iq_owned, h.iq_cap * 4 + 16384) != hipSuccess) { (void)hipGetLastError(); h.d_iq_owned = nullptr; return fail(OPV_ENOMEM, "wideband push: IQ buffer"); }
+            h.d_iq = h.d_iq_owned;                         // (a buffer more on a refused call is not a change of the context)
+        }
+    }
+    for (int i = 0; i < count; ++i) {
+        HostStream& h = c->hs[streams[i]];
+        dst[i] = (int*)(h.d_iq_owned + 2 * h.n_avail);
+        if (n[i]) {
+            h.n_avail += n[i];
+            h.dirty = true;
+        }
+    }
+    return OPV_OK;
+}
+
+int opv_int_push_end(opv_ctx* c, bool wait) {
+    if (wait) {
+        HIPCHK(hipStreamSynchronize(c->copy_stream));
+    } else {
+        if (!c->push_ev) HIPCHK(hipEventCreateWithFlags(&c->push_ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->push_ev, c->copy_stream));
+        c->push_pending = true;
+    }
+    return OPV_OK;
+}
+
+extern "C" long opv_tap_iq(opv_ctx* c, int s, uint64_t first, int16_t* out, size_t cap) {
+    if (int r = check_stream(c, s)) return r;
+    if (!out && cap) return fail(OPV_EINVAL, "null out");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int r = settle_pushes(c)) return r;
+    HIPCHK(hipStreamSynchronize(c->copy_stream));
+    if (int r = c->refresh()) return r;
+    const HostStream& h = c->hs[s];
+    const uint64_t base = c->mirror[s].iq_base;
+    if (first < base || first >= base + h.n_avail || !h.d_iq) return 0;
+    uint64_t n = base + h.n_avail - first;
+    if (n > cap) n = cap;
+    HIPCHK(hipMemcpy(out, h.d_iq + 2 * (first - base), n * 4, hipMemcpyDeviceToHost));
+    return (long)n;
 }

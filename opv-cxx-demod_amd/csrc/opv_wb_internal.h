@@ -1,0 +1,68 @@
+// opv_wb_internal.h — the door between the context (opv_capi.hip) and the wideband front door (opv_wideband.hip, k_wideband.hip).
+// The wideband object never sees opv_ctx's fields: it asks the context to reserve room in its streams' device buffers under
+// the rules of push_enqueue, launches its own kernel on the copy stream, and tells the context when it has.
+#ifndef OPV_WB_INTERNAL_H
+#define OPV_WB_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <memory>
+#include <vector>
+
+struct opv_ctx;
+
+// Arguments of k_wb_ddc (csrc/k_wideband.hip), by value. Sample n of the object (0 = the first sample ever pushed) has the absolute
+// index first_sample + n; this push holds samples [n_before, n_before + n_new).
+struct OpvWbArgs {
+    const int* src;          // this push: n_new packed (I | Q << 16) samples, device-visible (pinned host, staging copy or device)
+    const int* hist_in;      // the hist_len samples in front of src[0] (the carry of the pushes so far)
+    int* hist_out;           // the other carry buffer: the last min(n_before + n_new, L - 1) samples, written by block (0, 0)
+    const int16_t* lo;       // T[4096]
+    const int* taps;         // h[L], widened to int32
+    const uint32_t* inc;     // inc[K]
+    int* const* dst;         // dst[K]: where each channel's first output of this push goes (device-visible table)
+    uint64_t n_before;       // N before this push
+    uint64_t r0;             // first output index of this push = ceil(n_before / D)
+    uint32_t a0_lo;          // low 32 bits of first_sample + n_before: all the closed-form phase needs
+    uint32_t n_new, hist_len, n_out;
+    uint32_t D, L, K, S;
+    uint32_t tile;           // outputs per workgroup (<= 256)
+    uint32_t lpad;           // L - 1 rounded up to a multiple of D
+    uint32_t rowlen;         // tile + lpad / D: entries per decimation phase of the workgroup's span; D * rowlen <= OPV_WB_SPAN
+    uint32_t kper;           // channels per blockIdx.y
+};
+constexpr uint32_t OPV_WB_SPAN = 4096;     // wide samples (history included) a workgroup holds in LDS
+constexpr uint32_t OPV_WB_THREADS = 256;
+
+extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
+
+// ---- what the context offers (defined at the end of opv_capi.hip)
+int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code
+// What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
+// (or used) after its context finds ctx_alive false and touches nothing of the context.
+struct OpvWbShared {
+    std::vector<uint8_t> owned;   // [n_streams]: 1 while a live wideband object feeds the stream
+    bool ctx_alive = true;
+};
+struct OpvWbTie {                 // the context's end: a member of opv_ctx, so the context's destruction clears the flag
+    std::shared_ptr<OpvWbShared> p;
+    ~OpvWbTie() { if (p) p->ctx_alive = false; }
+};
+struct OpvCtxDoor {
+    int n_streams = 0, device = 0;
+    hipStream_t copy_stream = nullptr;
+    std::shared_ptr<OpvWbShared> shared;
+};
+int opv_int_door(opv_ctx* c, OpvCtxDoor* out);
+// hipSetDevice (no host wait: pushes of wideband objects queue behind each other on the copy stream)
+int opv_int_push_begin(opv_ctx* c);
+// Room for n[i] samples behind what streams[i] holds, for ALL `count` streams or for none: attached / flushed streams are
+// OPV_ESTATE, a stream that cannot take its share even after compaction is OPV_ECAPACITY, and in both cases nothing has changed.
+// On success dst[i] is where the samples go, and n_avail / dirty are already advanced: the caller must fill the room on the
+// copy stream and then call opv_int_push_end.
+int opv_int_push_reserve(opv_ctx* c, int count, const int* streams, const uint32_t* n, int** dst);
+// wait = true: host wait for the copy stream; false: the event opv_push_iq_batch_async records (opv_process queues behind it)
+int opv_int_push_end(opv_ctx* c, bool wait);
+
+#endif

@@ -1,0 +1,256 @@
+// opv_wideband.hip — the host half of the wideband front door (include/opv_demod.h, opv_wb_*): plan and validation (host only),
+// the object that carries the last L - 1 wide samples and the count N from push to push, and the push itself: every channel's
+// output count is computed here, room is reserved in all K streams under push_enqueue's rules (opv_int_push_reserve) before
+// anything is launched, then ONE k_wb_ddc launch on the context's copy stream writes all K streams.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/opv_demod.h"
+#include "opv_wb_internal.h"
+
+#define HIPCHK(expr)                                                      \
+    do {                                                                  \
+        hipError_t _e = (expr);                                           \
+        if (_e != hipSuccess) return opv_int_fail(OPV_EHIP, #expr, _e);   \
+    } while (0)
+
+namespace {
+
+constexpr double kWideRate = 2168000.0;
+constexpr int kTabSlots = 8;             // pushes whose destination tables may be in flight before the host waits for the oldest
+
+int check_cfg(const opv_wb_cfg* cfg) {
+    if (!cfg) return opv_int_fail(OPV_EINVAL, "opv_wb: null configuration");
+    if (cfg->decim < 1 || cfg->decim > 16) return opv_int_fail(OPV_EINVAL, "opv_wb: decim outside 1..16");
+    if (cfg->n_channels < 1 || cfg->n_channels > 256) return opv_int_fail(OPV_EINVAL, "opv_wb: n_channels outside 1..256");
+    if (cfg->n_taps < 1 || cfg->n_taps > 1024) return opv_int_fail(OPV_EINVAL, "opv_wb: n_taps outside 1..1024");
+    if (cfg->out_shift < 0 || cfg->out_shift > 40) return opv_int_fail(OPV_EINVAL, "opv_wb: out_shift outside 0..40");
+    return OPV_OK;
+}
+
+int plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
+    if (int r = check_cfg(cfg)) return r;
+    if (!centre_hz || !taps || !inc_out) return opv_int_fail(OPV_EINVAL, "opv_wb: null pointer");
+    int64_t gain = 0;
+    for (int t = 0; t < cfg->n_taps; ++t) gain += taps[t] < 0 ? -(int64_t)taps[t] : (int64_t)taps[t];
+    if (gain > (1ll << 21)) return opv_int_fail(OPV_EINVAL, "opv_wb: sum of |taps| exceeds 2^21");
+    const double fs = (double)cfg->decim * kWideRate;
+    for (int k = 0; k < cfg->n_channels; ++k) {
+        const double f = centre_hz[k];
+        if (!std::isfinite(f)) return opv_int_fail(OPV_EINVAL, "opv_wb: non-finite centre frequency");
+        const double turns = f / fs * 4294967296.0;
+        if (!(std::fabs(turns) < 9.0e18)) return opv_int_fail(OPV_EINVAL, "opv_wb: centre frequency out of range");
+        inc_out[k] = (uint32_t)(uint64_t)std::llrint(turns);          // modulo 2^32: a negative centre wraps
+    }
+    return OPV_OK;
+}
+
+}  // namespace
+
+struct opv_wb {
+    opv_ctx* ctx = nullptr;
+    opv_wb_cfg cfg{};
+    OpvCtxDoor door{};
+    std::vector<int> streams;
+    uint64_t n_total = 0;                // N: wide samples pushed so far
+    uint32_t hist_len = 0;               // min(N, L - 1)
+    int cur = 0;                         // which carry buffer holds the history
+    int* d_hist[2] = {nullptr, nullptr};
+    int16_t* d_lo = nullptr;
+    int* d_taps = nullptr;
+    uint32_t* d_inc = nullptr;
+    int* d_stage = nullptr;              // pageable sources: the block is copied here first (grow-only)
+    size_t stage_cap = 0;
+    int** h_tab = nullptr;               // pinned: kTabSlots x K destination pointers, read in place by the kernel
+    hipEvent_t tab_ev[kTabSlots] = {};
+    unsigned pushes = 0;
+    uint32_t tile = 0, lpad = 0, rowlen = 0;
+};
+
+extern "C" void opv_wb_lo_table(int16_t out4096[4096]) {
+    if (!out4096) return;
+    for (int i = 0; i < 4096; ++i) out4096[i] = (int16_t)std::lrint(32767.0 * std::cos(2.0 * 3.14159265358979323846 * (double)i / 4096.0));
+}
+
+extern "C" int opv_wb_plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
+    return plan(cfg, centre_hz, taps, inc_out);
+}
+
+extern "C" size_t opv_wb_outputs(const opv_wb_cfg* cfg, uint64_t n_wide_total) {
+    if (!cfg || cfg->decim < 1) return 0;
+    const uint64_t d = (uint64_t)cfg->decim;
+    return (size_t)(n_wide_total / d + (n_wide_total % d ? 1 : 0));
+}
+
+extern "C" void opv_wb_destroy(opv_wb* w) {
+    if (!w) return;
+    (void)hipSetDevice(w->door.device);
+    if (w->door.shared && w->door.shared->ctx_alive) {                  // (a context destroyed first waited for its copy stream itself)
+        if (w->door.copy_stream) (void)hipStreamSynchronize(w->door.copy_stream);
+        for (int s : w->streams) w->door.shared->owned[s] = 0;
+    }
+    for (auto& e : w->tab_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (w->h_tab) (void)hipHostFree(w->h_tab);
+    void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->d_stage};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    delete w;
+}
+
+extern "C" int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, const int* streams, const double* centre_hz, const int16_t* taps) {
+    if (!out) return opv_int_fail(OPV_EINVAL, "opv_wb_create: null out");
+    *out = nullptr;
+    if (!ctx || !streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create: null pointer");
+    std::vector<uint32_t> inc(256);
+    if (int r = plan(cfg, centre_hz, taps, inc.data())) return r;
+    OpvCtxDoor door;
+    if (int r = opv_int_door(ctx, &door)) return r;
+    const int K = cfg->n_channels, L = cfg->n_taps, D = cfg->decim;
+    {
+        std::vector<char> seen((size_t)door.n_streams, 0);
+        for (int k = 0; k < K; ++k) {
+            const int s = streams[k];
+            if (s < 0 || s >= door.n_streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create: stream index out of range");
+            if (seen[s]) return opv_int_fail(OPV_EINVAL, "opv_wb_create: a stream is named twice");
+            if (door.shared->owned[s]) return opv_int_fail(OPV_EINVAL, "opv_wb_create: a stream is already fed by another wideband object");
+            seen[s] = 1;
+        }
+    }
+    opv_wb* w = new (std::nothrow) opv_wb;
+    if (!w) return opv_int_fail(OPV_ENOMEM, "opv_wb_create");
+    w->ctx = ctx;
+    w->cfg = *cfg;
+    w->door = door;
+    w->lpad = (uint32_t)((L - 1 + D - 1) / D * D);
+    w->tile = (OPV_WB_SPAN - w->lpad) / (uint32_t)D;
+    if (w->tile > OPV_WB_THREADS) w->tile = OPV_WB_THREADS;
+    w->rowlen = w->tile + w->lpad / (uint32_t)D;                        // D * rowlen = tile * D + lpad <= OPV_WB_SPAN
+    int16_t lo[4096];
+    opv_wb_lo_table(lo);
+    std::vector<int> taps32((size_t)L);
+    for (int t = 0; t < L; ++t) taps32[t] = taps[t];
+#define WB_CHK(expr)                                                                             \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, #expr, _e); }   \
+    } while (0)
+    WB_CHK(hipSetDevice(door.device));
+    const size_t hist_bytes = (size_t)(L > 1 ? L - 1 : 1) * 4;
+    WB_CHK(hipMalloc(&w->d_hist[0], hist_bytes));
+    WB_CHK(hipMalloc(&w->d_hist[1], hist_bytes));
+    WB_CHK(hipMalloc(&w->d_lo, sizeof lo));
+    WB_CHK(hipMalloc(&w->d_taps, (size_t)L * 4));
+    WB_CHK(hipMalloc(&w->d_inc, (size_t)K * 4));
+    WB_CHK(hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
+    WB_CHK(hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
+    WB_CHK(hipMemcpy(w->d_taps, taps32.data(), (size_t)L * 4, hipMemcpyHostToDevice));
+    WB_CHK(hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
+#undef WB_CHK
+    w->streams.assign(streams, streams + K);
+    for (int s : w->streams) door.shared->owned[s] = 1;
+    *out = w;
+    return OPV_OK;
+}
+
+namespace {
+
+enum class Src { Host, Device };
+
+int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
+    if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null object");
+    if (!w->door.shared->ctx_alive) return opv_int_fail(OPV_ESTATE, "opv_wb_push: the object's context has been destroyed");
+    if (int r = opv_int_push_begin(w->ctx)) return r;
+    if (n_new == 0) return OPV_OK;
+    if (!iq) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null IQ pointer");
+    if (((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_wb_push: IQ pointer must be 4-byte aligned");
+    if (n_new >= (1ull << 31)) return opv_int_fail(OPV_EINVAL, "opv_wb_push: more than 2^31 - 1 samples in one push");
+    const uint32_t K = (uint32_t)w->cfg.n_channels, D = (uint32_t)w->cfg.decim, L = (uint32_t)w->cfg.n_taps;
+    const uint64_t r0 = (w->n_total + D - 1) / D, r1 = (w->n_total + n_new + D - 1) / D;
+    const uint32_t n_out = (uint32_t)(r1 - r0);
+    // ---- the source as the device sees it
+    const int* src = nullptr;
+    bool stage = false;
+    if (kind == Src::Device) {
+        src = (const int*)iq;
+    } else {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, iq) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer && at.device == w->door.device) {
+            src = (const int*)at.devicePointer;                         // pinned: the kernel reads the caller's block across PCIe, once
+        } else {
+            (void)hipGetLastError();                                    // (pageable memory: "invalid value" - not an error of ours)
+            if (w->stage_cap < n_new) {
+                HIPCHK(hipStreamSynchronize(w->door.copy_stream));
+                if (w->d_stage) HIPCHK(hipFree(w->d_stage));
+                w->d_stage = nullptr;
+                w->stage_cap = 0;
+                HIPCHK(hipMalloc(&w->d_stage, n_new * 4));
+                w->stage_cap = n_new;
+            }
+            src = w->d_stage;                                           // (grown at most so far: nothing enqueued, nothing of the object's state changed)
+            stage = true;
+        }
+    }
+    // ---- this push's destination table: a slot of the pinned ring, free once the launch that read it last has finished
+    const unsigned slot = w->pushes % kTabSlots;
+    if (w->tab_ev[slot]) HIPCHK(hipEventSynchronize(w->tab_ev[slot]));
+    else HIPCHK(hipEventCreateWithFlags(&w->tab_ev[slot], hipEventDisableTiming));
+    // ---- what can refuse the push, before anything is launched: room in all K streams, or nothing changes
+    std::vector<uint32_t> counts(K, n_out);
+    std::vector<int*> dst(K);
+    if (int r = opv_int_push_reserve(w->ctx, (int)K, w->streams.data(), counts.data(), dst.data())) return r;
+    if (stage) HIPCHK(hipMemcpyAsync(w->d_stage, iq, n_new * 4, hipMemcpyHostToDevice, w->door.copy_stream));
+    int** tab = w->h_tab + (size_t)slot * K;
+    std::memcpy(tab, dst.data(), (size_t)K * sizeof(int*));
+    void* d_tab = nullptr;
+    HIPCHK(hipHostGetDevicePointer(&d_tab, tab, 0));
+    OpvWbArgs a{};
+    a.src = src;
+    a.hist_in = w->d_hist[w->cur];
+    a.hist_out = w->d_hist[w->cur ^ 1];
+    a.lo = w->d_lo;
+    a.taps = w->d_taps;
+    a.inc = w->d_inc;
+    a.dst = (int* const*)d_tab;
+    a.n_before = w->n_total;
+    a.r0 = r0;
+    a.a0_lo = (uint32_t)(w->cfg.first_sample + w->n_total);
+    a.n_new = (uint32_t)n_new;
+    a.hist_len = w->hist_len;
+    a.n_out = n_out;
+    a.D = D; a.L = L; a.K = K; a.S = (uint32_t)w->cfg.out_shift;
+    a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen;
+    // few output tiles (a short push, a large D): the channels are shared out over blockIdx.y so that the device still fills
+    const uint32_t tiles = n_out ? (n_out + w->tile - 1) / w->tile : 1;
+    uint32_t ky = tiles >= 512 ? 1 : (512 + tiles - 1) / tiles;
+    if (ky > K) ky = K;
+    a.kper = (K + ky - 1) / ky;
+    ky = (K + a.kper - 1) / a.kper;
+    k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(w->tab_ev[slot], w->door.copy_stream));
+    ++w->pushes;
+    w->cur ^= 1;
+    w->n_total += n_new;
+    w->hist_len = w->n_total < (uint64_t)(L - 1) ? (uint32_t)w->n_total : L - 1;
+    return opv_int_push_end(w->ctx, wait);
+}
+
+}  // namespace
+
+extern "C" int opv_wb_push(opv_wb* w, const int16_t* iq_wide, size_t n_wide) { return wb_push(w, iq_wide, n_wide, Src::Host, true); }
+extern "C" int opv_wb_push_async(opv_wb* w, const int16_t* iq_wide, size_t n_wide) { return wb_push(w, iq_wide, n_wide, Src::Host, false); }
+extern "C" int opv_wb_push_device(opv_wb* w, const int16_t* d_iq_wide, size_t n_wide) { return wb_push(w, d_iq_wide, n_wide, Src::Device, true); }
+
+extern "C" int opv_wb_flush(opv_wb* w) {
+    if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_flush: null object");
+    if (!w->door.shared->ctx_alive) return opv_int_fail(OPV_ESTATE, "opv_wb_flush: the object's context has been destroyed");
+    for (int s : w->streams)
+        if (int r = opv_flush(w->ctx, s)) return r;
+    return OPV_OK;
+}

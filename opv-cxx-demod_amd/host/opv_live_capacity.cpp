@@ -8,11 +8,18 @@
 // largest N whose p99 stays under 40 ms (extras.live_capacity). No kernel is specific to this tool: it is a caller of
 // include/opv_demod.h like opv-rx-bridge, without sockets so that the number is the library's.
 //
-//   opv-live-capacity <n_streams> [rounds (120)] [warmup (6)] [device (0)] [--pipelined]
+//   opv-live-capacity <n_streams> [rounds (120)] [warmup (6)] [device (0)] [--pipelined | --wideband K]
 //     --pipelined   the double-buffered server: opv_push_iq_batch_async of round r + 1 is enqueued right behind opv_process of
 //                   round r, so the chunks of the next round cross PCIe while this round's kernels run and its frames are
 //                   popped; a round then costs max(PCIe, kernels + pops). Reported per round: the time from one opv_push_wait
 //                   to the next (steady-state period); a chunk's frames surface one round later than in the serial loop.
+//
+//     --wideband K  the same pipelined rounds and the same p99 criterion with the streams fed K per pinned WIDE capture through the
+//                   wideband front door (opv_wb_push_async, D = 1): n_streams / K captures of 86 720 wide samples cross PCIe per
+//                   round - a K-th of the bytes - and one k_wb_ddc launch per capture fills its K streams. Channel k of a capture
+//                   sits at (k - (K - 1) / 2) x 100 kHz (K <= 21 fit +/-1.084 MHz) at a K-th of full scale; the bank's taps are a
+//                   161-tap Hamming-windowed sinc, cut-off 50 kHz, its gain restores the amplitude to within a factor of two. n_streams must be a
+//                   multiple of K. Capture g starts g frames into the wide run, so every capture lies at its own host addresses.
 //
 // The signal is ONE clean BERT run of N + rounds + warmup + 1 frames (the device transmit chain, bit-identical to `opv-mod -S W5NYV
 // -B ...`, brought back into pinned host memory); stream k listens to it from frame k on. So in every round every stream's
@@ -24,6 +31,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -37,15 +45,18 @@ int main(int argc, char** argv) {
         return 2;
     }
     bool pipelined = false;
+    int K = 0;                                          // --wideband K: streams per wide capture (0: one block per stream)
     if (argc > 2 && !strcmp(argv[argc - 1], "--pipelined")) { pipelined = true; --argc; }
+    else if (argc > 3 && !strcmp(argv[argc - 2], "--wideband")) { K = atoi(argv[argc - 1]); pipelined = true; argc -= 2; if (K < 1 || K > 21) { fprintf(stderr, "opv-live-capacity: --wideband takes 1..21\n"); return 2; } }
     const int N = atoi(argv[1]);
     const int rounds = argc > 2 ? atoi(argv[2]) : 120, warm = argc > 3 ? atoi(argv[3]) : 6, device = argc > 4 ? atoi(argv[4]) : 0;
-    if (N < 1 || rounds < 1 || warm < 1) { fprintf(stderr, "opv-live-capacity: bad arguments\n"); return 2; }
+    if (N < 1 || rounds < 1 || warm < 1 || (K && N % K)) { fprintf(stderr, "opv-live-capacity: bad arguments\n"); return 2; }
+    const int G = K ? N / K : 0;                        // wide captures per round
     const int total = rounds + warm;
     const size_t chunk = OPV_CHUNK_SAMPLES;
 
     // the signal: N + total + 1 frames (+ the modulator's 100 silent symbols), in pinned memory
-    const size_t n_frames = (size_t)N + (size_t)total + 1;
+    const size_t n_frames = (K ? (size_t)K + (size_t)G : (size_t)N) + (size_t)total + 1;
     std::vector<uint8_t> frames(n_frames * OPV_FRAME_BYTES);
     opv_tx_bert_frames("W5NYV", 0xBBAADD, 0, n_frames, frames.data());
     const size_t n_all = opv_tx_modulated_samples(n_frames);
@@ -66,6 +77,50 @@ int main(int argc, char** argv) {
     if (opv_create(&ctx, N, &cfg) < 0) { fprintf(stderr, "opv-live-capacity: %s\n", opv_last_error()); return 2; }
     if (opv_tx_modulate_device_to_host(ctx, frames.data(), n_frames, iq) < 0) { fprintf(stderr, "opv-live-capacity: %s\n", opv_last_error()); return 2; }
 
+    // --wideband: the wide run W[n] = sum_k base[n + k chunk] / K x exp(j 2 pi f_k n / Fs) in pinned memory; capture g of round r
+    // is W[(r + g) chunk, + chunk), so stream g K + k listens to the base run from frame g + k on
+    int16_t* wide = nullptr;
+    std::vector<opv_wb*> wbs;
+    if (K) {
+        const size_t n_w = ((size_t)G + (size_t)total) * chunk;
+        if (hipHostMalloc((void**)&wide, n_w * 4, hipHostMallocDefault) != hipSuccess) { fprintf(stderr, "opv-live-capacity: no pinned host memory\n"); return 2; }
+        std::vector<double> ct(4096), sn(4096), acc(2 * n_w, 0.0);
+        for (int i = 0; i < 4096; ++i) { ct[i] = cos(2 * M_PI * i / 4096.0) / K; sn[i] = sin(2 * M_PI * i / 4096.0) / K; }
+        std::vector<double> centre(K);
+        for (int k = 0; k < K; ++k) {
+            centre[k] = (k - (K - 1) / 2.0) * 100000.0;
+            const uint32_t inc = (uint32_t)(int64_t)llrint(centre[k] / 2168000.0 * 4294967296.0);
+            const int16_t* b = iq + 2 * (size_t)k * chunk;
+            uint32_t ph = 0;
+            for (size_t n = 0; n < n_w; ++n, ph += inc) {
+                const double c = ct[ph >> 20], s_ = sn[ph >> 20];
+                acc[2 * n] += b[2 * n] * c - b[2 * n + 1] * s_;
+                acc[2 * n + 1] += b[2 * n] * s_ + b[2 * n + 1] * c;
+            }
+        }
+        for (size_t i = 0; i < 2 * n_w; ++i) wide[i] = (int16_t)lrint(acc[i]);
+        constexpr int L = 161;                           // delay (L - 1) / 2 = 80 samples = two whole symbols: the streams' timing loops start on a symbol boundary
+        int16_t taps[L];
+        double h[L], sum = 0;
+        for (int t = 0; t < L; ++t) {
+            const double x = 2.0 * 50000.0 / 2168000.0 * (t - (L - 1) / 2.0);
+            h[t] = (x == 0 ? 1.0 : sin(M_PI * x) / (M_PI * x)) * (0.54 - 0.46 * cos(2 * M_PI * t / (L - 1.0)));
+            sum += h[t];
+        }
+        for (int t = 0; t < L; ++t) taps[t] = (int16_t)lrint(h[t] / sum * 32768.0);
+        int shift = 30;                                  // unity gain (taps sum 2^15, LO 2^15); less by log2 K, rounded down
+        for (int k = K; k > 1; k >>= 1) --shift;
+        std::vector<int> sid(K);
+        for (int g = 0; g < G; ++g) {
+            opv_wb_cfg wc;
+            memset(&wc, 0, sizeof wc);
+            wc.decim = 1; wc.n_channels = K; wc.n_taps = L; wc.out_shift = shift; wc.first_sample = (uint64_t)g * chunk;
+            for (int k = 0; k < K; ++k) sid[k] = g * K + k;
+            opv_wb* w = nullptr;
+            if (opv_wb_create(&w, ctx, &wc, sid.data(), centre.data(), taps) < 0) { fprintf(stderr, "opv-live-capacity: %s\n", opv_last_error()); return 2; }
+            wbs.push_back(w);
+        }
+    }
     std::vector<int> ids(N);
     std::vector<const int16_t*> ptrs(N);
     std::vector<size_t> lens(N, chunk);
@@ -78,9 +133,14 @@ int main(int argc, char** argv) {
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     auto set_ptrs = [&](int r) { for (int k = 0; k < N; ++k) ptrs[k] = iq + 2 * ((size_t)r + (size_t)k) * chunk; };   // stream k is k frames into the run
+    auto push_async = [&](int r) -> int {               // round r's samples, enqueued: one block per stream, or one wide capture per K streams
+        if (!K) { set_ptrs(r); return opv_push_iq_batch_async(ctx, N, ids.data(), ptrs.data(), lens.data()); }
+        for (int g = 0; g < G; ++g)
+            if (int rc = opv_wb_push_async(wbs[g], wide + 2 * ((size_t)r + (size_t)g) * chunk, chunk)) return rc;
+        return 0;
+    };
     if (pipelined) {
-        set_ptrs(0);
-        if (opv_push_iq_batch_async(ctx, N, ids.data(), ptrs.data(), lens.data()) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
+        if (push_async(0) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
     }
     for (int r = 0; r < total; ++r) {
         const auto t0 = clk::now();
@@ -94,8 +154,7 @@ int main(int argc, char** argv) {
         if (opv_process(ctx) < 0) { fprintf(stderr, "process: %s\n", opv_last_error()); return 2; }
         const auto t1a = clk::now();
         if (pipelined && r + 1 < total) {                 // round r + 1 starts crossing PCIe behind round r's launches
-            set_ptrs(r + 1);
-            if (opv_push_iq_batch_async(ctx, N, ids.data(), ptrs.data(), lens.data()) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
+            if (push_async(r + 1) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
         }
         const auto t1b = clk::now();
         if (opv_sync(ctx) < 0) { fprintf(stderr, "process: %s\n", opv_last_error()); return 2; }
@@ -105,7 +164,7 @@ int main(int argc, char** argv) {
             const long g = opv_pop_frames(ctx, k, out, 4, meta);
             if (g < 0) { fprintf(stderr, "pop: %s\n", opv_last_error()); return 2; }
             for (long f = 0; f < g; ++f) {
-                const size_t idx = (size_t)k + next[k]++;
+                const size_t idx = (K ? (size_t)(k / K + k % K) : (size_t)k) + next[k]++;
                 if (idx >= n_frames || memcmp(out + f * OPV_FRAME_BYTES, frames.data() + idx * OPV_FRAME_BYTES, OPV_FRAME_BYTES) != 0) ++wrong;
                 if (meta[f].viterbi_metric != 0) ++imperfect;
             }
@@ -128,13 +187,15 @@ int main(int argc, char** argv) {
         const size_t i = (size_t)(p * (double)(v.size() - 1) + 0.5);
         return v[i < v.size() ? i : v.size() - 1];
     };
-    printf("{\"streams\": %d, \"pipelined\": %s, \"rounds\": %d, \"signal_ms_per_round\": 40.0, \"round_ms_p50\": %.3f, \"round_ms_p99\": %.3f, \"round_ms_max\": %.3f, "
+    printf("{\"streams\": %d, \"wideband\": %d, \"pipelined\": %s, \"rounds\": %d, \"signal_ms_per_round\": 40.0, \"round_ms_p50\": %.3f, \"round_ms_p99\": %.3f, \"round_ms_max\": %.3f, "
            "\"push_ms_p50\": %.3f, \"process_ms_p50\": %.3f, \"pop_ms_p50\": %.3f, \"pcie_GBps_p50\": %.2f, \"frames_released\": %ld, "
            "\"frames_wrong\": %ld, \"frames_imperfect\": %ld, \"rounds_not_one_frame_per_stream\": %ld, \"process_call_ms_p50\": %.3f, \"async_enqueue_ms_p50\": %.3f}\n",
-           N, pipelined ? "true" : "false", rounds, pct(t_round, 0.5), pct(t_round, 0.99), pct(t_round, 1.0), pct(t_push, 0.5), pct(t_proc, 0.5), pct(t_pop, 0.5),
+           N, K, pipelined ? "true" : "false", rounds, pct(t_round, 0.5), pct(t_round, 0.99), pct(t_round, 1.0), pct(t_push, 0.5), pct(t_proc, 0.5), pct(t_pop, 0.5),
            // serial: the moves alone; pipelined: push_ms is only the wait for moves that ran beside the previous round - the rate over the period
-           (double)N * chunk * 4 / (pct(pipelined ? t_round : t_push, 0.5) * 1e-3) / 1e9, released, wrong, imperfect, uneven, pct(t_launch, 0.5), pct(t_enq, 0.5));
+           (double)(K ? G : N) * chunk * 4 / (pct(pipelined ? t_round : t_push, 0.5) * 1e-3) / 1e9, released, wrong, imperfect, uneven, pct(t_launch, 0.5), pct(t_enq, 0.5));
+    for (opv_wb* w : wbs) opv_wb_destroy(w);
     opv_destroy(ctx);
+    if (wide) (void)hipHostFree(wide);
     (void)hipHostFree(iq);
     return wrong ? 1 : 0;
 }

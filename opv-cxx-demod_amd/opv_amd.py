@@ -12,6 +12,7 @@ There is no CPU fallback: if the library is missing or no MI355X is visible, cal
 import ctypes as C
 import os
 import subprocess
+import weakref
 from pathlib import Path
 
 import numpy as np
@@ -35,6 +36,7 @@ EXPORTS = [
     "opv_tap_offset_energies", "opv_offset_ties_on_host", "opv_offset_ties_decided_on_host", "opv_offset_ties_left_to_device", "opv_tap_wave_info", "opv_tap_occupancy", "opv_decode_payloads", "opv_tx_bert_frame", "opv_tx_bert_frames", "opv_tx_modulated_samples",
     "opv_tx_modulate", "opv_tap_tx_checkpoints", "opv_frontend_kernel", "opv_channel_device", "opv_resample_device", "opv_enable_timing", "opv_kernel_times", "opv_tx_modulate_device", "opv_tx_modulate_device_to_host",
     "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
+    "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
 ]
 
@@ -47,6 +49,11 @@ class Cfg(C.Structure):
     _fields_ = [("streaming", C.c_int32), ("have_init_offset", C.c_int32), ("init_offset_hz", C.c_double),
                 ("afc_alpha", C.c_double), ("device", C.c_int32), ("coherent", C.c_int32),
                 ("max_samples", C.c_uint64), ("pll_bw_hz", C.c_double)]
+
+
+class WbCfg(C.Structure):
+    _fields_ = [("decim", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
+                ("first_sample", C.c_uint64)]
 
 
 class FrameMeta(C.Structure):
@@ -175,6 +182,20 @@ def lib():
         L.opv_export_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.opv_import_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         L.opv_blob_streams.argtypes = [C.c_void_p, C.c_size_t]
+        L.opv_wb_plan.argtypes = [C.POINTER(WbCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wb_lo_table.restype = None
+        L.opv_wb_lo_table.argtypes = [C.c_void_p]
+        L.opv_wb_outputs.restype = C.c_size_t
+        L.opv_wb_outputs.argtypes = [C.POINTER(WbCfg), C.c_uint64]
+        L.opv_wb_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wb_destroy.restype = None
+        L.opv_wb_destroy.argtypes = [C.c_void_p]
+        L.opv_wb_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_wb_push_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_wb_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_wb_flush.argtypes = [C.c_void_p]
+        L.opv_tap_iq.restype = C.c_long
+        L.opv_tap_iq.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -312,6 +333,79 @@ def blob_streams(blob):
     return _chk(lib().opv_blob_streams(b.ctypes.data if b.size else None, b.size))
 
 
+# ---------------------------------------------------------------- wideband front door (opv_wb_*)
+def _wb_args(decim, centre_hz, taps, out_shift, first_sample):
+    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
+    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
+    return WbCfg(int(decim), centre.size, taps.size, int(out_shift), int(first_sample)), centre, taps
+
+
+def wb_plan(decim, centre_hz, taps, out_shift, first_sample=0):
+    """opv_wb_plan: validates a plan and returns its K phase increments (uint32); host only, needs no device"""
+    cfg, centre, taps = _wb_args(decim, centre_hz, taps, out_shift, first_sample)
+    inc = np.zeros(max(centre.size, 1), np.uint32)
+    _chk(lib().opv_wb_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
+    return inc[:centre.size]
+
+
+def wb_lo_table():
+    """opv_wb_lo_table: T[i] = lrint(32767 cos(2 pi i / 4096)) as int16"""
+    out = np.empty(4096, np.int16)
+    lib().opv_wb_lo_table(out.ctypes.data)
+    return out
+
+
+def wb_outputs(decim, n_wide_total):
+    """opv_wb_outputs: outputs per channel after n_wide_total wide samples, ceil(N / decim)"""
+    cfg = WbCfg(int(decim), 1, 1, 0, 0)
+    return int(lib().opv_wb_outputs(C.byref(cfg), int(n_wide_total)))
+
+
+class Wideband:
+    """A bank of DDCs on the device that feeds streams[k] of `demod` with the channel at centre_hz[k] of one wide capture
+    (opv_wb_*, include/opv_demod.h). Close it before its Demod."""
+
+    def __init__(self, demod, decim, streams, centre_hz, taps, out_shift, first_sample=0):
+        self.demod = demod
+        self.cfg, centre, taps = _wb_args(decim, centre_hz, taps, out_shift, first_sample)
+        ids = (C.c_int * len(streams))(*[int(s) for s in streams])
+        if len(streams) != centre.size:
+            raise OpvError("Wideband: one centre frequency per stream")
+        self.h = C.c_void_p()
+        _chk(lib().opv_wb_create(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
+        self._inflight = []
+        demod._wideband.add(self)
+
+    def push(self, iq_wide):
+        iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
+        _chk(lib().opv_wb_push(self.h, iq.ctypes.data, iq.size // 2))
+
+    def push_async(self, iq_wide):
+        """opv_wb_push_async: the block must stay alive and unchanged until demod.push_wait(). Several pushes may be in flight, so
+        every block (or the copy made of it) is kept referenced here until then."""
+        iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
+        self._inflight.append(iq)
+        _chk(lib().opv_wb_push_async(self.h, iq.ctypes.data, iq.size // 2))
+
+    def push_device(self, dev_ptr, n_wide):
+        _chk(lib().opv_wb_push_device(self.h, C.c_void_p(dev_ptr), int(n_wide)))
+
+    def flush(self):
+        _chk(lib().opv_wb_flush(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().opv_wb_destroy(self.h)                                     # (waits for the copy stream: nothing reads the blocks any more)
+            self.h = C.c_void_p()
+        self._inflight = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 # ---------------------------------------------------------------- receiver
 class Demod:
     """n_streams independent receivers on one GPU (mirrors the three reference objects
@@ -320,6 +414,7 @@ class Demod:
     def __init__(self, n_streams=1, max_samples=1 << 22, streaming=True, init_offset=None, afc_alpha=0.001,
                  device=0, coherent=False, pll_bw=50.0):
         self.n_streams = n_streams
+        self._wideband = weakref.WeakSet()      # Wideband objects feeding this context: push_wait releases their blocks too
         self.cfg = Cfg(int(streaming), int(init_offset is not None), float(init_offset or 0.0), afc_alpha,
                        device, int(coherent), int(max_samples), float(pll_bw))
         self.h = C.c_void_p()
@@ -361,6 +456,8 @@ class Demod:
     def push_wait(self):
         _chk(lib().opv_push_wait(self.h))
         self._inflight = None
+        for wb in self._wideband:
+            wb._inflight = []
 
     def flush(self, stream):
         _chk(lib().opv_flush(self.h, stream))
@@ -433,6 +530,13 @@ class Demod:
         out = np.empty(cap, np.float64)
         n = _chk(lib().opv_tap_soft(self.h, stream, first, out.ctypes.data, cap))
         return out[:n].copy()
+
+    def iq(self, stream, first=0, cap=None):
+        """opv_tap_iq: the int16 IQ the stream's device buffer holds from absolute sample `first` on (interleaved)"""
+        cap = cap or int(self.cfg.max_samples)
+        out = np.empty(2 * cap, np.int16)
+        n = _chk(lib().opv_tap_iq(self.h, stream, first, out.ctypes.data, cap))
+        return out[:2 * n].copy()
 
     def chunks(self, stream, first=0):
         cap = int(self.cfg.max_samples) // 80000 + 4

@@ -55,7 +55,7 @@
 //     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
 //     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
 //     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
-//     (f64_ring_helper: 6 instructions per symbol fewer).
+//     (f64_ring_helper: 6 instructions per symbol fewer; measured 687 against 750 cycles per symbol, profiles/r08_pmc_*.txt).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
 //     decisions on noisy input do. No MFMA: the per-symbol contraction is
 //     3x4x60 with a serial dependence between symbols.
@@ -212,21 +212,29 @@ __device__ void f64_ring_helper(const OpvStream& st, lbyte* lds_all) {
             continue;
         }
         spins = 0;
-        const uint32_t n = fill + 4u * lane;
-        int w[5];
-        if (n + 4u <= n_avail) {
-            const int4 v = *reinterpret_cast<const int4*>(iq + n);   // 16-byte aligned: n is a multiple of 4
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        // Lane l converts samples fill + l + 64 k: consecutive lanes write consecutive 32-byte entries, so the eight lanes
+        // one ds_write_b128 group serves cover all 32 banks twice (2-way; four samples in a row per lane put a group's eight
+        // lanes 128 B apart on the same four banks, 8-way, in bursts the stream's wave's tap reads queued behind). Sample n
+        // and its successor as two dword loads, coalesced across the wave.
+        constexpr uint32_t kPerLane = kF64Chunk / 64u;
+        const uint32_t n0 = fill + lane;
+        int w[kPerLane], wn[kPerLane];
+        if (fill + kF64Chunk < n_avail) {                      // (wave-uniform) the chunk and the sample behind it exist
+#pragma unroll
+            for (uint32_t k = 0; k < kPerLane; ++k) { w[k] = iq[n0 + 64u * k]; wn[k] = iq[n0 + 64u * k + 1u]; }
         } else {
 #pragma unroll
-            for (uint32_t k = 0; k < 4u; ++k) w[k] = n + k < n_avail ? iq[n + k] : 0;
+            for (uint32_t k = 0; k < kPerLane; ++k) {
+                const uint32_t n = n0 + 64u * k;
+                w[k] = n < n_avail ? iq[n] : 0;
+                wn[k] = n + 1u < n_avail ? iq[n + 1u] : 0;
+            }
         }
-        w[4] = n + 4u < n_avail ? iq[n + 4u] : 0;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (uint32_t k = 0; k < kPerLane; ++k) {
             const int xr = (int)(short)(w[k] & 0xFFFF), xi = w[k] >> 16;
-            const int yr = (int)(short)(w[k + 1] & 0xFFFF) - xr, yi = (w[k + 1] >> 16) - xi;
-            ld2v* e = reinterpret_cast<ld2v*>(lds_all + kF64RingOff + (((n + (uint32_t)k) & (kF64Ring - 1u)) << 5));
+            const int yr = (int)(short)(wn[k] & 0xFFFF) - xr, yi = (wn[k] >> 16) - xi;
+            ld2v* e = reinterpret_cast<ld2v*>(lds_all + kF64RingOff + (((n0 + 64u * k) & (kF64Ring - 1u)) << 5));
             e[0] = d2v{(double)xr, (double)xi};
             e[1] = d2v{(double)yr, (double)yi};
         }

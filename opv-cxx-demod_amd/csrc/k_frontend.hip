@@ -37,7 +37,8 @@
 //     samples; with 15 samples per row, 2 x 15 FMACs give ALL window sums of the symbol (on-time / early / late
 //     correlations of both tones + the on-time sums P1..P4) as row partials in lane t = lane & 15, one all-reduce over
 //     the four rows completes them, v_mov_b64_dpp row_newbcast hands out what the loop filters need, the energies and
-//     the dominant-tone select are lane-parallel. 153 VALU instructions per symbol.
+//     the dominant-tone select (shift and select in one v_cndmask_b32_dpp per word) are lane-parallel. The four-symbol loop
+//     holds 142.25 instructions per symbol on the fp64 ring, 150.25 on the int16 ring (census of the device assembly).
 //     The scalar loop filters run redundantly on all lanes (wave-uniform, no divergence).
 //   * A LONE wave on a SIMD issues one instruction of ANY kind (VALU, SALU, LDS, s_nop, branch)
 //     every ~4.7 cycles and gains nothing from independent chains (scripts/microbench): the
@@ -55,7 +56,7 @@
 //     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
 //     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
 //     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
-//     (f64_ring_helper: 6 instructions per symbol fewer; measured 687 against 750 cycles per symbol, profiles/r08_pmc_*.txt).
+//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, profiles/r10_bench_ab.txt).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
 //     decisions on noisy input do. No MFMA: the per-symbol contraction is
 //     3x4x60 with a serial dependence between symbols.
@@ -130,9 +131,6 @@ __device__ inline double swap16_add(double a, double b) {
 template <int N>
 __device__ inline double row_bcast(double old, double v) { return __builtin_amdgcn_update_dpp(old, v, 0x150 + N, 0xF, 0xF, false); }
 __device__ inline uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ inline double readlane_d(double v, int l) {
-    return mkd(__builtin_amdgcn_readlane(dhi(v), l), __builtin_amdgcn_readlane(dlo(v), l));
-}
 // wave-uniform floating compare -> scalar branch (the operands are identical in every lane)
 __device__ inline bool uni_lt(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 4 /*FCMP_OLT*/) != 0ull; }
 __device__ inline bool uni_eq(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 1 /*FCMP_OEQ*/) != 0ull; }
@@ -155,24 +153,38 @@ struct SinCosK {
     double s0, s1, s2, s3;      // q(u) low -> high (cubic)
     double c0, c1, c2, c3, c4;  // r(u) low -> high (degree 4)
 };
+#define OPV_EXPJ_ASM \
+    "v_mul_f64 %[x], %[kfs], %[fo]\n\t" \
+    "v_mul_f64 %[u], %[x], %[x]\n\t" \
+    "v_fma_f64 %[r], %[c4], %[u], %[c3]\n\t" \
+    "v_fma_f64 %[p], %[s3], %[u], %[s2]\n\t" \
+    "v_fma_f64 %[r], %[r], %[u], %[c2]\n\t" \
+    "v_fma_f64 %[p], %[p], %[u], %[s1]\n\t" \
+    "v_fma_f64 %[r], %[r], %[u], %[c1]\n\t" \
+    "v_fma_f64 %[p], %[p], %[u], %[s0]\n\t" \
+    "v_fma_f64 %[r], %[r], %[u], %[c0]\n\t" \
+    "v_mul_f64 %[t], %[x], %[u]\n\t" \
+    "v_fma_f64 %[xc], %[r], %[u], 1.0\n\t" \
+    "v_fma_f64 %[xs], %[t], %[p], %[x]"
 __device__ inline void expj_small(double kfs, double fo, const SinCosK& k, double& xs, double& xc) {
     double x, u, p, r, t;
-    asm("v_mul_f64 %[x], %[kfs], %[fo]\n\t"
-        "v_mul_f64 %[u], %[x], %[x]\n\t"
-        "v_fma_f64 %[r], %[c4], %[u], %[c3]\n\t"
-        "v_fma_f64 %[p], %[s3], %[u], %[s2]\n\t"
-        "v_fma_f64 %[r], %[r], %[u], %[c2]\n\t"
-        "v_fma_f64 %[p], %[p], %[u], %[s1]\n\t"
-        "v_fma_f64 %[r], %[r], %[u], %[c1]\n\t"
-        "v_fma_f64 %[p], %[p], %[u], %[s0]\n\t"
-        "v_fma_f64 %[r], %[r], %[u], %[c0]\n\t"
-        "v_mul_f64 %[t], %[x], %[u]\n\t"
-        "v_fma_f64 %[xc], %[r], %[u], 1.0\n\t"
-        "v_fma_f64 %[xs], %[t], %[p], %[x]"
+    asm(OPV_EXPJ_ASM
         : [x] "=&v"(x), [u] "=&v"(u), [p] "=&v"(p), [r] "=&v"(r), [t] "=&v"(t), [xs] "=&v"(xs), [xc] "=&v"(xc)
         : [kfs] "v"(kfs), [fo] "v"(fo), [s0] "v"(k.s0), [s1] "v"(k.s1), [s2] "v"(k.s2), [s3] "v"(k.s3),
           [c0] "v"(k.c0), [c1] "v"(k.c1), [c2] "v"(k.c2), [c3] "v"(k.c3), [c4] "v"(k.c4));
 }
+// The steady-state form: the AFC clamp of the previous symbol's update (ref :302-303) and the LO factor of this symbol in ONE
+// block, so that no padding stands between the clamp and the first product (hipcc pads an fp64 instruction behind an asm block).
+__device__ inline void expj_small_clamped(double kfs, double fo_raw, double fo_lo, double fo_hi, const SinCosK& k, double& fo,
+                                          double& xs, double& xc) {
+    double x, u, p, r, t;
+    asm("v_max_f64 %[fo], %[raw], %[lo]\n\t"
+        "v_min_f64 %[fo], %[fo], %[hi]\n\t" OPV_EXPJ_ASM
+        : [fo] "=&v"(fo), [x] "=&v"(x), [u] "=&v"(u), [p] "=&v"(p), [r] "=&v"(r), [t] "=&v"(t), [xs] "=&v"(xs), [xc] "=&v"(xc)
+        : [raw] "v"(fo_raw), [lo] "v"(fo_lo), [hi] "v"(fo_hi), [kfs] "v"(kfs), [s0] "v"(k.s0), [s1] "v"(k.s1), [s2] "v"(k.s2), [s3] "v"(k.s3),
+          [c0] "v"(k.c0), [c1] "v"(k.c1), [c2] "v"(k.c2), [c3] "v"(k.c3), [c4] "v"(k.c4));
+}
+#undef OPV_EXPJ_ASM
 
 }  // namespace
 
@@ -259,9 +271,11 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
     OpvStream& st = streams[sidx];
 
     // ---- per-lane constants -------------------------------------------------------------
-    // rows of 15 samples (lane 16 r + n <-> sample 15 r + n, n < 15; a row's last lane repeats its neighbour's
-    // sample and carries no weight), so that the 60 samples take 15 broadcast steps per row instead of 16
-    const int jsamp = lane - (lane >> 4) - ((lane & 15) == 15 ? 1 : 0);
+    // rows of 15 samples (lane 16 r + n <-> sample 15 r + n, n < 15), so that the 60 samples take 15 broadcast steps per
+    // row instead of 16. A row's last lane carries no weight - no row_newbcast:0..14 reads its Z - and is given sample 50
+    // (kf = 40): its LO factor IS X[40], which the next symbol's phase detector needs in every lane, one row_newbcast:15
+    // away in each row (its taps, floor(pos) + 40 and + 41, lie inside what kAhead guarantees in both rings)
+    const int jsamp = (lane & 15) == 15 ? 50 : lane - (lane >> 4);
     const double kf = (double)(jsamp - 10);
     const double kfs = kf * kDeltaPerHz;
     // T_1[i] = exp(-j 2 pi i / 160) = (a, b) = (cos(pi i/80), -sin(pi i/80)); zero outside a gate's window.
@@ -420,8 +434,19 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         const double Nd = (double)N;
         double pos = mu;                                   // ref :217
         const uint32_t soft_off0 = ((uint32_t)n_soft * 8u) & soft_bmask;  // ring byte offset of this call's first symbol
+        // The offset of the next symbol to be logged, unwrapped: inside a batch of symbols the soft ring does not wrap
+        // (housekeeping), so that a symbol's store is soft_v + a constant and only the batch boundary applies the ring mask.
+        // soft_off: wave-uniform, advanced once per batch; soft_v: the store's address operand, one add per loop trip.
         uint32_t soft_off = soft_off0;
-        asm volatile("" : "+v"(soft_off));            // lives in a VGPR: it is the store's address operand
+        uint32_t soft_v = soft_off0;
+        asm volatile("" : "+v"(soft_v));
+        auto soft_advance = [&](uint32_t nsym) {           // behind a batch of nsym symbols
+            soft_off = (soft_off + 8u * nsym) & soft_bmask;
+            soft_v = soft_off;
+            asm volatile("" : "+v"(soft_v));
+        };
+        const uint32_t ring_c = (origin << 5) & (kF64RingBytes - 1u);   // fp64 ring: byte offset of the call's sample 0
+        double fo_raw = fo;                                // the AFC's update before its clamp (symbol_r)
 
         // Tile bookkeeping for the symbol at `at` (wave-uniform, rare). Returns how many FOLLOWING
         // symbols need neither it nor the end-of-call test: pos advances by at most 42 samples per
@@ -456,7 +481,10 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             const int lim1 = (int)(next_evt - gb) - 2, lim2 = (int)N - 52 - (int)b;
             int lim = lim1 < lim2 ? lim1 : lim2;
             if (lim < 0) lim = 0;
-            return ((uint32_t)lim * 1560u) >> 16;          // <= floor(lim / 42), lim < 2^17
+            // ... and while the soft ring does not wrap: soft_off is masked, so at least one symbol fits behind it
+            const uint32_t by_samples = ((uint32_t)lim * 1560u) >> 16;     // <= floor(lim / 42), lim < 2^17
+            const uint32_t by_ring = ((soft_bmask + 8u - soft_off) >> 3) - 1u;
+            return by_samples < by_ring ? by_samples : by_ring;
         };
 
         // One interpolated sample per lane (ref :122-128, :232-238): the two int16 IQ words around
@@ -470,7 +498,9 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             if (clamp0) p = fmax(p, 0.0);                  // early gate before the chunk: s[0] (ref :237)
             const int idx = (int)p;
             f = __builtin_amdgcn_fract(p);                 // p - idx, p >= 0
-            if constexpr (F64) tap_byte = (((uint32_t)idx + origin) << 5) & (kF64RingBytes - 32u);
+            // fp64 ring: exactly 2^16 bytes, so (32 idx + ring_c) mod 2^16 is one 16-bit multiply-add. tap_byte is written by
+            // nothing else in this shape and starts as 0: its high half is 0 whether the instruction clears or keeps it.
+            if constexpr (F64) asm("v_mad_legacy_u16 %0, %1, 32, %2" : "+v"(tap_byte) : "v"(idx), "s"(ring_c));
             else tap_byte = (((uint32_t)idx + origin) << 2) & (kRingBytes - 4u);
         };
         auto fetch_read = [&]() {
@@ -500,13 +530,15 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         // early / late energies are formed lane-parallel (square, row_ror:8, add: Re at t, Im at t + 8), the dominant
         // tone's pair selected lane-parallel (row_shl:2), before two of them are handed out. The phase detector's angle
         // comes without the octant fix-up (opv_atan2.h: opv_atan2_q3r, 1025-row table of pi/4 + atan, cubics in the argument itself; round 2: 257 rows, degree 5).
-        // Scheduling notes: hipcc counts an asm block as no wait state and pads the fp64 instruction behind one with an
-        // s_nop; every block here is therefore followed by a 32-bit instruction that was needed anyway, and the wait
-        // states DPP reads / permlane swaps need behind a VALU write are filled with useful instructions, not s_nop.
-        // (scripts/microbench/dpp64.hip has the instruction costs.)
-        auto symbol_r = [&](auto tag, PrevSums& cur, const PrevSums& prv) {
+        // Scheduling notes: hipcc counts an asm block as no wait state and pads behind one, so neighbouring pieces are ONE block
+        // (the AFC clamp with the LO factor, the thirty FMACs with the sum and its copy, the tone compare with the P3 / P4
+        // hand-outs and the selects), and the wait states DPP reads / permlane swaps need behind a VALU write are filled with
+        // useful instructions where there are any: two s_nop per symbol remain (in front of the second swap, nothing
+        // independent is left; behind the select block). (scripts/microbench/dpp64.hip has the instruction costs.)
+        auto symbol_r = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) {
             constexpr bool kFirst = decltype(tag)::first;
             constexpr bool kWide = decltype(tag)::wide;
+            constexpr uint32_t kSlot = decltype(slot)::value;          // the symbol's place in its loop trip: logged at soft_v + 8 kSlot
             // The LO factor FIRST: it needs fo only, and its twelve instructions are the cover the tap read of the previous
             // symbol's tail still lacked (round 3: without that read the kernel ran 34 cycles per symbol faster, i.e. ~26 of
             // its latency were exposed when the unpack below came first)
@@ -515,12 +547,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 if (__builtin_expect(uni_lt(2000.0, fabs(fo)), 0)) sincos(kfs * fo, &xs, &xc);
                 else expj_small(kfs, fo, sck, xs, xc);
             } else {
-                expj_small(kfs, fo, sck, xs, xc);
+                expj_small_clamped(kfs, fo_raw, kc_nfomax, kc_fomax, sck, fo, xs, xc);   // fo: the previous symbol's update, clamped here
             }
-            __builtin_amdgcn_sched_barrier(0);
-            const uint32_t my_soft_off = soft_off;
-            uint32_t soft_off_next = soft_off + 8u;                 // (32-bit filler behind the asm block above)
-            asm volatile("" : "+v"(soft_off_next));
             __builtin_amdgcn_sched_barrier(0);
             double lr, li;
             if constexpr (F64) {                                            // the same operands, widened by the helper
@@ -541,35 +569,29 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             double acc0, acc1, v, t;
 #define OPV_RB(N) "v_fmac_f64_dpp %[a0], %[zr], %[r" #N "] row_newbcast:" #N " row_mask:0xf bank_mask:0xf\n\t" \
                   "v_fmac_f64_dpp %[a1], %[zi], %[i" #N "] row_newbcast:" #N " row_mask:0xf bank_mask:0xf\n\t"
+            // (one block: the sum of the two accumulators and the copy the all-reduce swaps with behind the thirty FMACs)
             asm("v_mov_b64 %[a0], 0\n\tv_mov_b64 %[a1], 0\n\t" OPV_RB(0) OPV_RB(1) OPV_RB(2) OPV_RB(3) OPV_RB(4) OPV_RB(5) OPV_RB(6) OPV_RB(7)
-                : [a0] "=&v"(acc0), [a1] "=&v"(acc1)
-                : [zr] "v"(zr), [zi] "v"(zi), [r0] "v"(wr[0]), [i0] "v"(wi[0]), [r1] "v"(wr[1]), [i1] "v"(wi[1]), [r2] "v"(wr[2]), [i2] "v"(wi[2]),
-                  [r3] "v"(wr[3]), [i3] "v"(wi[3]), [r4] "v"(wr[4]), [i4] "v"(wi[4]), [r5] "v"(wr[5]), [i5] "v"(wi[5]),
-                  [r6] "v"(wr[6]), [i6] "v"(wi[6]), [r7] "v"(wr[7]), [i7] "v"(wi[7]));
-            __builtin_amdgcn_sched_barrier(0);
-            soft_off = soft_off_next & soft_bmask;                  // (32-bit filler between the two blocks)
-            asm volatile("" : "+v"(soft_off));
-            __builtin_amdgcn_sched_barrier(0);
-            // second half, the sum of the two accumulators and the copy the all-reduce swaps with
-            asm(OPV_RB(8) OPV_RB(9) OPV_RB(10) OPV_RB(11) OPV_RB(12) OPV_RB(13) OPV_RB(14)
+                OPV_RB(8) OPV_RB(9) OPV_RB(10) OPV_RB(11) OPV_RB(12) OPV_RB(13) OPV_RB(14)
                 "v_add_f64 %[v], %[a0], %[a1]\n\t"
                 "v_mov_b64 %[t], %[v]"
-                : [a0] "+v"(acc0), [a1] "+v"(acc1), [v] "=&v"(v), [t] "=&v"(t)
-                : [zr] "v"(zr), [zi] "v"(zi), [r8] "v"(wr[8]), [i8] "v"(wi[8]), [r9] "v"(wr[9]), [i9] "v"(wi[9]), [r10] "v"(wr[10]), [i10] "v"(wi[10]),
+                : [a0] "=&v"(acc0), [a1] "=&v"(acc1), [v] "=&v"(v), [t] "=&v"(t)
+                : [zr] "v"(zr), [zi] "v"(zi), [r0] "v"(wr[0]), [i0] "v"(wi[0]), [r1] "v"(wr[1]), [i1] "v"(wi[1]), [r2] "v"(wr[2]), [i2] "v"(wi[2]),
+                  [r3] "v"(wr[3]), [i3] "v"(wi[3]), [r4] "v"(wr[4]), [i4] "v"(wi[4]), [r5] "v"(wr[5]), [i5] "v"(wi[5]),
+                  [r6] "v"(wr[6]), [i6] "v"(wi[6]), [r7] "v"(wr[7]), [i7] "v"(wi[7]),
+                  [r8] "v"(wr[8]), [i8] "v"(wi[8]), [r9] "v"(wr[9]), [i9] "v"(wi[9]), [r10] "v"(wr[10]), [i10] "v"(wi[10]),
                   [r11] "v"(wr[11]), [i11] "v"(wi[11]), [r12] "v"(wr[12]), [i12] "v"(wi[12]), [r13] "v"(wr[13]), [i13] "v"(wi[13]),
                   [r14] "v"(wr[14]), [i14] "v"(wi[14]));
 #undef OPV_RB
             __builtin_amdgcn_sched_barrier(0);
-            // ---- all-reduce over the four rows; the X[40] hand-over (sample 50 sits in row 3, lane 5) fills the two wait
-            // states a swap needs behind the copy
-            cur.x40c = readlane_d(xc, 53);
+            // ---- all-reduce over the four rows; the X[40] hand-over (the spare lane 15 of every row carries sample 50: two
+            // DPP moves, equal in every lane) fills the two wait states a swap needs behind the copy
+            cur.x40c = row_bcast<15>(lr, xc);                       // (`old` operands: dead temporaries)
+            cur.x40s = row_bcast<15>(li, xs);
             __builtin_amdgcn_sched_barrier(0);
             v = swap32_add(v, t);
             asm("v_mov_b64 %0, %1" : "=v"(t) : "v"(v));
             __builtin_amdgcn_sched_barrier(0);
-            cur.x40s = readlane_d(xs, 53);
-            __builtin_amdgcn_sched_barrier(0);
-            v = swap16_add(v, t);
+            v = swap16_add(v, t);                                   // (nothing independent is left for this swap's wait states: one s_nop 1)
             __builtin_amdgcn_sched_barrier(0);
             double fo_sum_next = fo_sum + fo;                       // sum of the fo every symbol USED
             asm volatile("" : "+v"(fo_sum_next));
@@ -579,25 +601,37 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             const double shv = mkd(__builtin_amdgcn_mov_dpp(dhi(v), 0x128, 0xF, 0xF, true), __builtin_amdgcn_mov_dpp(dlo(v), 0x128, 0xF, 0xF, true));
             const double en = fma(shv, shv, sq);
             __builtin_amdgcn_sched_barrier(0);
-            // on-time sums P1..P4 to every lane (`old` operands: dead temporaries of the stages above)
-            const double P1o = row_bcast<6>(zr, v), P2o = row_bcast<7>(zi, v), P3o = row_bcast<14>(lr, v), P4o = row_bcast<15>(li, v);
+            // on-time sums P1, P2 to every lane (`old` operands: dead temporaries of the stages above; the two moves are en's
+            // wait states before the DPP reads below); P3, P4 follow further down
+            const double P1o = row_bcast<6>(zr, v), P2o = row_bcast<7>(zi, v);
             __builtin_amdgcn_sched_barrier(0);
             // soft value = |S_2|^2 - |S_1|^2 (ref :264-268): the difference of the two energies like the reference, each from its
             // own correlation. (Where the reference's tones tie exactly - a real or imaginary Z - so do these: the two
             // correlations' accumulation chains are mirror images.)
-            const double en1 = row_bcast<0>(acc0, en), en2 = row_bcast<1>(acc1, en);   // (behind the four hand-outs above: en's wait states)
+            const double en1 = row_bcast<0>(acc0, en), en2 = row_bcast<1>(acc1, en);
             const double soft = en2 - en1;
             __builtin_amdgcn_sched_barrier(0);
-            // the dominant tone's early / late pair moves to t = 2, 3 (row_shl:2 brings tone 2's over), then one hand-out each;
-            // tone 1 iff e1 > e2 (ref :272 / :291; a tie gives +0: tone 2). sg = +1 for tone 1, -1 for tone 2.
-            const bool dom1 = soft < 0.0;
+            // The dominant tone's early / late pair moves to t = 2, 3, then one hand-out each; tone 1 iff e1 > e2 (ref :272 / :291;
+            // a tie gives +0: tone 2). Shift and select are ONE instruction per word: v_cndmask_b32_dpp takes its first source
+            // through row_shl:2 (tone 2's pair, two lanes up) and keeps the lane's own word where vcc is set. The hand-outs of
+            // P3, P4 stand between the compare and the selects (the two wait states a DPP instruction is given behind a write
+            // it depends on); en was written seven instructions earlier.
+            double P3o, P4o;
+            int sel_lo, sel_hi;
+            asm("v_cmp_gt_f64 vcc, 0, %[soft]\n\t"
+                "v_mov_b64_dpp %[p3], %[v] row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
+                "v_mov_b64_dpp %[p4], %[v] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
+                "v_cndmask_b32_dpp %[sl], %[el], %[el], vcc row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                "v_cndmask_b32_dpp %[sh], %[eh], %[eh], vcc row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                : [p3] "=&v"(P3o), [p4] "=&v"(P4o), [sl] "=&v"(sel_lo), [sh] "=&v"(sel_hi)
+                : [soft] "v"(soft), [v] "v"(v), [el] "v"(dlo(en)), [eh] "v"(dhi(en))
+                : "vcc");
+            const double seln = mkd(sel_hi, sel_lo);
+            __builtin_amdgcn_sched_barrier(0);
+            // sg = +1 for tone 1, -1 for tone 2 (the sign insert is the 32-bit instruction hipcc wants behind an asm block)
             nsg = mkd((dhi(soft) & (int)0x80000000) | (dhi(nsg) & 0x7fffffff), dlo(nsg));
             asm volatile("" : "+v"(nsg));                           // (updated in place: no copy of the low word)
             const double sg = -nsg;
-            const double oth = mkd(__builtin_amdgcn_mov_dpp(dhi(en), 0x102, 0xF, 0xF, true), __builtin_amdgcn_mov_dpp(dlo(en), 0x102, 0xF, 0xF, true));
-            __builtin_amdgcn_sched_barrier(0);
-            double seln = dom1 ? en : oth;
-            asm volatile("" : "+v"(seln));                          // (the select stays here: the phase detector's arithmetic below is its two wait states)
             __builtin_amdgcn_sched_barrier(0);
 
             [[maybe_unused]] double pd = 0.0, cx = 0, cy = 0, sum = 1.0, dif = 0, dm_ = 1.0, ee, el;
@@ -674,7 +708,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             __builtin_amdgcn_sched_barrier(0);
             fetch_read();                                             // next symbol's taps requested as soon as their address exists
             __builtin_amdgcn_sched_barrier(0);
-            *(gdouble*)(soft_base + my_soft_off) = soft;
+            *(gdouble*)(soft_base + soft_v + 8u * kSlot) = soft;      // (the slot's 8 kSlot is the store's immediate offset)
             if constexpr (!kFirst) {
                 const double pd_off = fma(-sx, kc_halfpi, kc_halfpi);
                 __builtin_amdgcn_sched_barrier(0);
@@ -688,28 +722,39 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 pd = mkd((dhi(pd) & 0x7fffffff) | (dhi(cy) & (int)0x80000000), dlo(pd));  // sign of cy
                 if (__builtin_expect(WPB == 1 ? zmask != 0ull : uni_eq(sum, 0.0), 0)) {   // digital silence on either side
                     const double dr = fma(sg, P2o, P1o), di = fma(-sg, P4o, P3o);
-                    const double2 sp = silence_pd(dr, di, prv, soft < 0.0, fo_sum, n_soft + (((my_soft_off - soft_off0) & soft_bmask) >> 3),
+                    const double2 sp = silence_pd(dr, di, prv, soft < 0.0, fo_sum, n_soft + (((soft_v + 8u * kSlot - soft_off0) & soft_bmask) >> 3),
                                                   P1o, P2o, P3o, P4o);
                     pd = sp.x;
                     edge_ties += uni((uint32_t)sp.y);
                 }
-                const double fo_new = fma(kc_gain, pd, fo);         // ref :300-303
-                asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3" : "=&v"(fo) : "v"(fo_new), "v"(kc_nfomax), "v"(kc_fomax));
+                fo_raw = fma(kc_gain, pd, fo);                      // ref :300-303; clamped by the next symbol, or by fo_settle
             }
             fo_sum = fo_sum_next;
             cur.a = P1o; cur.b = P2o; cur.c = P3o; cur.d = P4o;     // prev <- this symbol's on-time correlations (ref :309-310)
         };
 
-        auto sym = [&](auto tag, PrevSums& cur, const PrevSums& prv) { symbol_r(tag, cur, prv); };
+        // behind the last symbol of a batch: the AFC clamp its successor would have applied (idempotent: the successor applies it again)
+        auto fo_settle = [&]() {
+            asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3" : "=&v"(fo) : "v"(fo_raw), "v"(kc_nfomax), "v"(kc_fomax));
+            fo_raw = fo;
+        };
+        using Slot0 = std::integral_constant<uint32_t, 0>;
+        using Slot1 = std::integral_constant<uint32_t, 1>;
+        using Slot2 = std::integral_constant<uint32_t, 2>;
+        using Slot3 = std::integral_constant<uint32_t, 3>;
+        auto sym = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) { symbol_r(tag, slot, cur, prv); };
 
         if (uni_lt(pos + 40.0 + 10.0, Nd)) {               // ref :221
             (void)housekeeping(pos);
             fetch(pos, true);
-            sym(TagFirst{}, qp, qp);
+            sym(TagFirst{}, Slot0{}, qp, qp);
+            soft_advance(1u);
             if (__builtin_expect(uni_lt(2000.0, fabs(fo)), 0) && uni_lt(pos + 40.0 + 10.0, Nd)) {
                 (void)housekeeping(pos);                   // an out-of-range -o is still in force for one more symbol
                 fetch(pos, false);
-                sym(TagSecond{}, qq, qp);
+                sym(TagSecond{}, Slot0{}, qq, qp);
+                fo_settle();
+                soft_advance(1u);
                 qp = qq;
             }
             // Batches: the end-of-call test and the tile events once, then as many symbols as are
@@ -721,19 +766,24 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 uint32_t pairs = uni(housekeeping(pos)) >> 1;
                 if (F64 && overflow != 0) break;           // the helper was lost (f64_wait)
                 fetch(pos, false);
+                const uint32_t batch = 2u * pairs + 1u;    // symbols of this batch: they fit in front of the soft ring's wrap
                 // four symbols per trip: a taken branch costs a lone wave 36 cycles (scripts/microbench/dpp64.hip, empty loop)
                 for (uint32_t quads = pairs >> 1; quads != 0u; --quads) {
-                    sym(TagSteady{}, qq, qp);
-                    sym(TagSteady{}, qp, qq);
-                    sym(TagSteady{}, qq, qp);
-                    sym(TagSteady{}, qp, qq);
+                    sym(TagSteady{}, Slot0{}, qq, qp);
+                    sym(TagSteady{}, Slot1{}, qp, qq);
+                    sym(TagSteady{}, Slot2{}, qq, qp);
+                    sym(TagSteady{}, Slot3{}, qp, qq);
+                    soft_v += 32u;
                 }
                 pairs &= 1u;
                 for (; pairs != 0u; --pairs) {
-                    sym(TagSteady{}, qq, qp);
-                    sym(TagSteady{}, qp, qq);
+                    sym(TagSteady{}, Slot0{}, qq, qp);
+                    sym(TagSteady{}, Slot1{}, qp, qq);
+                    soft_v += 16u;
                 }
-                sym(TagSteady{}, qq, qp);
+                sym(TagSteady{}, Slot0{}, qq, qp);
+                fo_settle();
+                soft_advance(batch);
                 qp = qq;
             }
         }

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
+                               still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
                                still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
                                7: opv_process never waits on the host again - the host-libm decision of offset-search near-ties runs as a host
                                function IN STREAM ORDER between the search and the front-end (+ opv_offset_ties_decided_on_host, opv_offset_ties_left_to_device); opv_set_frontend
@@ -344,6 +345,19 @@ long opv_tap_soft(opv_ctx* ctx, int stream, uint64_t first_symbol, double* out, 
 /* the IQ a pushed (or wideband-fed) stream holds on the device, by absolute sample index: up to cap samples (2 int16 each) from
  * first_sample; returns the number copied - 0 outside what the stream's buffer still retains. Implies opv_push_wait + opv_sync. */
 long opv_tap_iq(opv_ctx* ctx, int stream, uint64_t first_sample, int16_t* out, size_t cap);
+/* The other direction: n soft symbols (host doubles, any values - NaN and infinities included) are appended to the stream's
+ * soft-symbol log exactly where its front-end would have written them, behind the rounds launched so far, and the next
+ * opv_process runs the tracker, the scale pre-pass and the decoder over them with the very launches it uses for pushed IQ.
+ * Test infrastructure: it lets a checker hand the back half of the receive chain a made soft log. opv_get_state,
+ * opv_pop_frames, opv_pop_events and opv_tap_soft answer for such a stream as for any other (total_symbols counts the staged
+ * symbols; the front-end's fields stay as created). Room follows the front-end's own back-pressure rule: symbols the tracker
+ * or a pending payload may still read are never overwritten - a push that does not fit is OPV_ECAPACITY and stages nothing
+ * (opv_process / opv_pop_frames make room). A stream takes EITHER IQ or staged symbols between two opv_reset_stream: this call
+ * answers OPV_ESTATE on a stream that has received IQ (pushed, attached, wideband-fed, imported) or has been flushed, and
+ * opv_push_iq*, opv_attach_device_iq, opv_flush, the wideband pushes and opv_export_streams answer OPV_ESTATE on a stream
+ * that holds staged symbols; the context stays usable either way. Null pointers, a stream out of range or n == 0: OPV_EINVAL.
+ * Waits for the rounds in flight. */
+int opv_tap_push_soft(opv_ctx* ctx, int stream, const double* soft, size_t n);
 /* per demodulate() call, starting at call number first_chunk: {freq_offset, timing_freq, mu,
  * leftover, n_symbols}. The log is a ring of the most recent calls. */
 long opv_tap_chunks(opv_ctx* ctx, int stream, uint32_t first_chunk, double* out5, size_t cap_chunks);

@@ -150,11 +150,11 @@ __device__ __forceinline__ void decode_two(const FrameIo& A, const FrameIo& B, u
     // The reference's expression per value (:864-865) is int((-soft / scale) * 3.5 + 3.5 + 0.5), four rounded operations of which
     // the IEEE division alone costs a wave ~30 fp64 instructions. Its result is decided by ONE multiply-add,
     // x = fma(soft, -3.5 / scale, 4.0), whenever x is not within 1e-6 of an integer: both expressions are within ~1e-14 of
-    // the exact value 4 - 3.5 soft / scale for |x| < 9 (|soft / scale| <= 2144 always, so nothing overflows), hence they
-    // truncate alike unless the exact value is within 1e-14 of an integer - and then x is within the guard band and the
+    // the exact value 4 - 3.5 soft / scale for |x| < 9 (|soft / scale| <= 2144 while the scale is finite: nothing overflows), hence
+    // they truncate alike unless the exact value is within 1e-14 of an integer - and then x is within the guard band and the
     // reference's own sequence is evaluated (about one value in 10^5 on noise; every value of a few-level input). Outside
-    // (-1, 9) both clamp to the same end. NaN (never produced by the front-end) converts to 0 on both paths, like
-    // the reference's cvttsd2si + clamp.
+    // (-1, 9) both clamp to the same end. An infinite scale (an Inf in the payload, a sum that overflows) gives x = 4.0, in the band,
+    // or NaN; NaN converts to 0 on both paths like the reference's cvttsd2si + clamp (tests/test_gpu_soft_log.py holds all of it).
     // All of a frame's loads of a lane (34 gathered doubles, from L2 / HBM) are requested before the first is used: a wave
     // that waited for them one trellis step at a time spent 30 000 cycles here (17 round trips), more than in the trellis.
     auto quantise_frame = [&](const FrameIo& F, int byte_of_pair) {

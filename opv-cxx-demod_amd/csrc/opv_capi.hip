@@ -195,6 +195,10 @@ struct HostStream {
     int32_t decoded = 0, perfect = 0;  // over popped frames (`decoded` / `perfect` of main(), ref :1053-1054)
     uint64_t soft_floor = 0;           // an imported stream (opv_import_streams): first soft symbol / chunk-log entry that travelled with it
     uint32_t chunk_floor = 0;
+    // opv_tap_push_soft (parity tap): a stream is fed EITHER IQ or staged soft symbols between two resets, never both
+    bool iq_seen = false;              // IQ has arrived since the last reset (push / attach / wideband / import)
+    bool soft_tapped = false;          // staged soft symbols have
+    uint64_t tap_fresh = 0;            // staged symbols no round has been launched for yet
 };
 
 }  // namespace
@@ -645,6 +649,7 @@ static int push_enqueue(opv_ctx* c, int s, const int16_t* iq, size_t n, std::vec
     HostStream& h = c->hs[s];
     if (h.attached) return fail(OPV_ESTATE, "stream has an attached device capture");
     if (h.eof) return fail(OPV_ESTATE, "push after flush");
+    if (h.soft_tapped) return fail(OPV_ESTATE, "stream holds staged soft symbols (opv_tap_push_soft; reset it first)");
     if (n == 0) return OPV_OK;
     if (!iq) return fail(OPV_EINVAL, "null IQ pointer");
     if (h.n_avail + n > c->cfg.max_samples) {
@@ -670,6 +675,7 @@ static int push_enqueue(opv_ctx* c, int s, const int16_t* iq, size_t n, std::vec
     else HIPCHK(hipMemcpyAsync(h.d_iq_owned + 2 * h.n_avail, iq, n * 4, hipMemcpyHostToDevice, c->copy_stream));
     h.n_avail += n;
     h.dirty = true;
+    h.iq_seen = true;
     return OPV_OK;
 }
 
@@ -786,6 +792,7 @@ static int push_batch(opv_ctx* c, int count, const int* streams, const int16_t* 
 
 extern "C" int opv_flush(opv_ctx* c, int s) {
     if (int r = check_stream(c, s)) return r;
+    if (c->hs[s].soft_tapped) return fail(OPV_ESTATE, "stream holds staged soft symbols (opv_tap_push_soft; reset it first)");
     c->hs[s].eof = 1;
     c->hs[s].dirty = true;
     return OPV_OK;
@@ -795,11 +802,13 @@ extern "C" int opv_attach_device_iq(opv_ctx* c, int s, const int16_t* d_iq, size
     if (int r = check_stream(c, s)) return r;
     HostStream& h = c->hs[s];
     if (h.d_iq_owned && h.n_avail && !h.attached) return fail(OPV_ESTATE, "stream already has pushed samples (reset it first)");
+    if (h.soft_tapped) return fail(OPV_ESTATE, "stream holds staged soft symbols (opv_tap_push_soft; reset it first)");
     if (!d_iq && n) return fail(OPV_EINVAL, "null device pointer");
     if (((uintptr_t)d_iq & 15u) != 0) return fail(OPV_EINVAL, "device IQ pointer must be 16-byte aligned");
     if (n > c->cfg.max_samples) return fail(OPV_ECAPACITY, "opv_cfg.max_samples exceeded");
     if (h.attached && (d_iq != h.d_iq || n < h.n_avail)) return fail(OPV_ESTATE, "attached capture may only grow");
     h.attached = true;
+    h.iq_seen = true;
     h.d_iq = d_iq;
     h.n_avail = n;
     h.eof = eof ? 1 : 0;
@@ -827,7 +836,7 @@ extern "C" int opv_process(opv_ctx* c) {
     const int slot = (int)(c->round_no % opv_ctx::kInSlots);
     if (c->round_no >= (unsigned)opv_ctx::kInSlots) HIPCHK(hipEventSynchronize(c->in_ev[slot]));  // upload of round_no-kInSlots done
     StreamIn* in = c->h_in + (size_t)slot * S;
-    uint64_t max_new = 0;
+    uint64_t max_new = 0, max_tapped = 0;
     bool any = false;
     c->search_now.clear();
     for (int i = 0; i < S; ++i) {
@@ -838,6 +847,8 @@ extern "C" int opv_process(opv_ctx* c) {
         if (!h.search_seen && (c->cfg.streaming ? h.n_avail >= (uint64_t)OPV_CHUNK : h.eof != 0)) c->search_now.push_back(i);
         const uint64_t fresh = h.n_avail - h.last_round_avail;
         if (fresh > max_new) max_new = fresh;
+        if (h.tap_fresh) any = true;                       // soft symbols staged by opv_tap_push_soft: work for the tracker and the decoder only
+        if (h.tap_fresh > max_tapped) max_tapped = h.tap_fresh;
     }
     // nothing new: still run the round while a stream may be waiting behind back-pressure (it resumes by itself once
     // the tracker has consumed soft symbols / the caller has popped frames; the cursors travel with every round).
@@ -847,7 +858,10 @@ extern "C" int opv_process(opv_ctx* c) {
         c->maybe_stalled = c->h_stall[(c->round_no - 1) % opv_ctx::kInSlots] != 0;
     if (!any && !c->maybe_stalled) return OPV_OK;
     // frames a stream can release this round: new symbols / 2168 plus what was pending (checked before anything is launched)
-    uint64_t fr = max_new / (uint64_t)(OPV_FSYMS * 38) + 4;
+    // (staged soft symbols count as what they are: one frame per 2168 of them)
+    uint64_t fr = max_new / (uint64_t)(OPV_FSYMS * 38);
+    if (max_tapped / (uint64_t)OPV_FSYMS > fr) fr = max_tapped / (uint64_t)OPV_FSYMS;
+    fr += 4;
     if (fr > c->cap_frames) fr = c->cap_frames;
     if (fr * (uint64_t)S > 0x7FFFFFFFull) return fail(OPV_EINVAL, "opv_process: streams x frames per round exceeds the grid limit");
     // the round will be launched: only now is the host's view of the streams advanced (a refused round leaves it untouched)
@@ -855,6 +869,7 @@ extern "C" int opv_process(opv_ctx* c) {
         HostStream& h = c->hs[i];
         h.last_round_avail = h.n_avail;
         h.dirty = false;
+        h.tap_fresh = 0;
     }
     for (int i : c->search_now) c->hs[i].search_seen = true;
     c->mirror_valid = false;
@@ -1156,6 +1171,39 @@ extern "C" long opv_tap_soft(opv_ctx* c, int s, uint64_t first, double* out, siz
     HIPCHK(hipMemcpy(out, st.soft + p0, sizeof(double) * run, hipMemcpyDeviceToHost));
     if (run < n) HIPCHK(hipMemcpy(out + run, st.soft, sizeof(double) * (n - run), hipMemcpyDeviceToHost));
     return (long)n;
+}
+
+// Parity tap: `n` soft symbols appended to the stream's log exactly where its front-end would have written them (symbol i at
+// soft[i & (cap_soft - 1)], n_soft advanced), in stream order behind the rounds launched so far. The next opv_process - the
+// same launches as for pushed IQ, there is no second copy of them - runs the tracker, the scale pre-pass and the decoder over
+// them. Room is the front-end's own rule (k_frontend.hip: soft_keep): nothing the tracker or a pending payload may still read
+// is overwritten.
+extern "C" int opv_tap_push_soft(opv_ctx* c, int s, const double* soft, size_t n) {
+    if (int r = check_stream(c, s)) return r;
+    if (!soft || n == 0) return fail(OPV_EINVAL, "opv_tap_push_soft: null pointer or no symbols");
+    HostStream& h = c->hs[s];
+    if (h.iq_seen || h.attached || h.n_avail) return fail(OPV_ESTATE, "opv_tap_push_soft: the stream has received IQ (reset it first)");
+    if (h.eof) return fail(OPV_ESTATE, "opv_tap_push_soft: the stream has been flushed (reset it first)");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    if (int r = settle_pushes(c)) return r;
+    if (int r = c->refresh()) return r;                    // (waits for the rounds in flight: the tracker's cursors are final)
+    OpvStream& st = c->mirror[s];
+    if (st.overflow) return fail(OPV_ESTATE, "opv_tap_push_soft: the stream is in an error state (opv_pop_frames reports it)");
+    uint64_t soft_keep = st.trk_next >= 24 ? st.trk_next - 24 : 0;
+    if (st.trk_state != OPV_HUNTING && st.trk_anchor < soft_keep) soft_keep = st.trk_anchor;
+    if (n > st.cap_soft || (st.n_soft - soft_keep) + n > st.cap_soft)
+        return fail(OPV_ECAPACITY, "opv_tap_push_soft: the soft-symbol ring has no room (unread symbols + this push do not fit; "
+                                   "call opv_process / opv_pop_frames between pushes)");
+    const uint64_t p0 = st.n_soft & (st.cap_soft - 1);
+    const uint64_t run = n < st.cap_soft - p0 ? n : st.cap_soft - p0;
+    HIPCHK(hipMemcpyAsync(st.soft + p0, soft, sizeof(double) * run, hipMemcpyHostToDevice, c->stream));
+    if (run < n) HIPCHK(hipMemcpyAsync(st.soft, soft + run, sizeof(double) * (n - run), hipMemcpyHostToDevice, c->stream));
+    st.n_soft += n;                                        // (the mirror stays valid: it is what the device holds after these copies)
+    HIPCHK(hipMemcpyAsync(&c->d_streams[s].n_soft, &st.n_soft, sizeof st.n_soft, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));               // the symbols are the caller's again
+    h.soft_tapped = true;
+    h.tap_fresh += n;
+    return OPV_OK;
 }
 
 extern "C" long opv_tap_chunks(opv_ctx* c, int s, uint32_t first, double* out5, size_t cap) {
@@ -1720,6 +1768,7 @@ int plan_export(opv_ctx* c, int count, const int* streams, std::vector<BlobEntry
         BlobEntry& e = (*ents)[i];
         OpvStream st = c->mirror[streams[i]];
         if (st.overflow) return fail(OPV_ESTATE, "opv_export_streams: the stream is in an error state (opv_pop_frames reports it)");
+        if (h.soft_tapped) return fail(OPV_ESTATE, "opv_export_streams: the stream holds staged soft symbols (opv_tap_push_soft, a parity tap)");
         if (st.n_frames - h.popped > st.cap_frames) return fail(OPV_ESTATE, "opv_export_streams: more unpopped frames than the ring holds");
         // IQ: from the point compaction keeps (compact_stream) up to everything pushed, processed or not; indices re-based like there
         const uint64_t keep = (h.d_iq && st.origin >= 16) ? ((st.origin - 16) & ~3ull) : 0;
@@ -1953,6 +2002,7 @@ extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const v
         n.decoded = e.decoded;
         n.perfect = e.perfect;
         n.soft_floor = e.soft_first;
+        n.iq_seen = true;                                  // (its soft symbols came out of a front-end)
         n.chunk_floor = e.chunks_first + (uint32_t)(e.seg_n[SEG_CHUNKS] - (e.seg_n[SEG_CHUNKS] < c->cap_chunks ? e.seg_n[SEG_CHUNKS] : c->cap_chunks));
         hs = n;
     }
@@ -1994,6 +2044,7 @@ int opv_int_push_reserve(opv_ctx* c, int count, const int* streams, const uint32
         const HostStream& h = c->hs[streams[i]];
         if (h.attached) return fail(OPV_ESTATE, "stream has an attached device capture");
         if (h.eof) return fail(OPV_ESTATE, "push after flush");
+        if (h.soft_tapped) return fail(OPV_ESTATE, "stream holds staged soft symbols (opv_tap_push_soft; reset it first)");
         if (n[i] && h.n_avail + n[i] > c->cfg.max_samples) full.push_back(streams[i]);
     }
     if (!full.empty()) {
@@ -2025,6 +2076,7 @@ int opv_int_push_reserve(opv_ctx* c, int count, const int* streams, const uint32
         if (n[i]) {
             h.n_avail += n[i];
             h.dirty = true;
+            h.iq_seen = true;
         }
     }
     return OPV_OK;

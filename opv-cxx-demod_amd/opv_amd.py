@@ -38,6 +38,7 @@ EXPORTS = [
     "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
     "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
+    "opv_tap_push_soft",
 ]
 
 
@@ -134,6 +135,7 @@ def lib():
         L.opv_gather_frames_all.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.opv_tap_soft.restype = C.c_long
         L.opv_tap_soft.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
+        L.opv_tap_push_soft.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.opv_tap_chunks.restype = C.c_long
         L.opv_tap_chunks.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t]
         L.opv_tap_offset_energies.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -530,6 +532,13 @@ class Demod:
         out = np.empty(cap, np.float64)
         n = _chk(lib().opv_tap_soft(self.h, stream, first, out.ctypes.data, cap))
         return out[:n].copy()
+
+    def push_soft(self, stream, soft):
+        """opv_tap_push_soft (parity tap): fp64 soft symbols appended to the stream's soft log as its front-end would have
+        written them; the next process() runs the tracker and the decoder over them. Raises OpvError (-4) when the ring
+        has no room, (-6) on a stream that has received IQ."""
+        soft = np.ascontiguousarray(soft, np.float64).reshape(-1)
+        _chk(lib().opv_tap_push_soft(self.h, stream, soft.ctypes.data, soft.size))
 
     def iq(self, stream, first=0, cap=None):
         """opv_tap_iq: the int16 IQ the stream's device buffer holds from absolute sample `first` on (interleaved)"""

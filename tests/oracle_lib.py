@@ -70,6 +70,36 @@ class _Coh(C.Structure):
                 ("pll_beta", C.c_double)]
 
 
+class _Tracker(C.Structure):
+    """oro_tracker (oracle/opv_oracle.h)"""
+    _fields_ = [("state", C.c_int), ("ring", C.c_double * 24), ("ring_idx", C.c_size_t), ("total_symbols", C.c_size_t),
+                ("pattern", C.c_double * 24), ("collecting", C.c_int), ("pending", C.c_double * CODED_BITS),
+                ("pending_n", C.c_size_t), ("since_sync", C.c_size_t), ("quality", C.c_double), ("misses", C.c_int),
+                ("total_frames", C.c_int)]
+
+
+def _track_result(rel, events, final_state, n_soft, decode):
+    """What receive() returns for the back half, from the released payloads `rel` = [(release symbol, quality, payload)] of a
+    tracker run and its events: EVERY released frame has an entry - metrics[k] = -1 and a zero frame for one the decoder dropped."""
+    n = len(rel)
+    frames = np.zeros((n, FRAME_BYTES), np.uint8)
+    metrics = np.zeros(n, np.int32)
+    for k, (_, _, payload) in enumerate(rel):
+        metrics[k], fr = decode(payload)
+        if metrics[k] >= 0:
+            frames[k] = fr
+    # whether a frame's sync word passed its check: the HUNTING hit (kind 1) or LOCKED check (3: passed, 4: flywheel) that
+    # started its collection, 2144 symbols in front of the release
+    sync_ok = np.zeros(n, np.int32)
+    for k, (r, _, _) in enumerate(rel):
+        for e in events:
+            if int(e["sym_idx"]) < r and int(e["kind"]) in (1, 3, 4):
+                sync_ok[k] = int(e["kind"]) != 4
+    return dict(frames=frames, metrics=metrics, frame_sym=np.array([r[0] for r in rel], np.uint64),
+                quality=np.array([r[1] for r in rel], np.float64), sync_ok=sync_ok, payloads=[r[2] for r in rel],
+                events=events, final_state=int(final_state), n_soft=int(n_soft))
+
+
 def _iq(a):
     a = np.ascontiguousarray(a, dtype=np.int16).reshape(-1)
     assert a.size % 2 == 0
@@ -103,6 +133,10 @@ class Oracle:
         L.oro_frame_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.oro_receive.restype = C.c_int
         L.oro_receive.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.oro_tracker_init.argtypes = [C.c_void_p]
+        L.oro_tracker_process.restype = C.c_int
+        L.oro_tracker_process.argtypes = [C.c_void_p, C.c_double, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_size_t]
 
     # ---- transmit ----
     def bert_frames(self, n, callsign="W5NYV", token=0xBBAADD, first=0):
@@ -191,6 +225,32 @@ class Oracle:
         m = self.lib.oro_frame_decode(soft.ctypes.data, out.ctypes.data, q.ctypes.data, de.ctypes.data,
                                       bits.ctypes.data)
         return dict(metric=m, frame=out, q=q, deint=de, bits=bits)
+
+    def track(self, soft):
+        """The back half over a whole soft log: oro_tracker_process symbol by symbol (SyncTracker::process, ref :615-736), then
+        oro_frame_decode per released payload. Returns what receive() returns for the back half, with an entry for EVERY
+        released frame: frames, metrics (-1: dropped by the decoder, its frame is zeros), frame_sym (release symbols), quality,
+        sync_ok, payloads, events (EVENT_DTYPE), final_state, n_soft."""
+        soft = np.ascontiguousarray(soft, np.float64).reshape(-1)
+        L = self.lib
+        trk = _Tracker()
+        L.oro_tracker_init(C.byref(trk))
+        events = np.zeros(4 * (soft.size // FRAME_SYMBOLS + 8) + 64, EVENT_DTYPE)
+        n_ev = C.c_size_t(0)
+        payload = np.zeros(CODED_BITS, np.float64)
+        q = C.c_double(0)
+        rel = []
+        pt, pp, pq, pe, pn = C.addressof(trk), payload.ctypes.data, C.addressof(q), events.ctypes.data, C.addressof(n_ev)
+        step = L.oro_tracker_process
+        for i, v in enumerate(soft.tolist()):
+            if step(pt, v, i, pp, pq, pe, pn, events.size):
+                rel.append((i, q.value, payload.copy()))
+        assert n_ev.value <= events.size
+
+        def decode(p):
+            r = self.frame_decode(p)
+            return r["metric"], r["frame"]
+        return _track_result(rel, events[:n_ev.value].copy(), trk.state, soft.size, decode)
 
     # ---- whole receiver ----
     def receive(self, iq, streaming=True, init_offset=None, afc_alpha=0.001, want_soft=True,
@@ -318,6 +378,53 @@ class Reference:
 
     def deinterleave_perm(self):
         return np.array([self.lib.ref_deinterleave_addr(i) for i in range(CODED_BITS)], np.uint16)
+
+    def track(self, soft):
+        """Oracle.track over the compiled SyncTracker and FrameDecoder. The reference says what its tracker did on stderr only,
+        so the events are its log lines parsed back (kind, count and sym_idx exact; corr / raw as printed, to 3 / 0 decimals,
+        `-nan` read as NaN); `log` holds the lines themselves, with glibc's `-nan` written `nan` as Python prints it."""
+        import re
+        soft = np.ascontiguousarray(soft, np.float64).reshape(-1)
+        L = self.lib
+        self.take_log()
+        tr = L.ref_tracker_create()
+        payload = np.zeros(CODED_BITS, np.float64)
+        q = C.c_double(0)
+        rel = []
+        step, pp, pq = L.ref_tracker_process, payload.ctypes.data, C.addressof(q)
+        for i, v in enumerate(soft.tolist()):
+            if step(tr, v, i, pp, pq):
+                rel.append((i, q.value, payload.copy()))
+        state = L.ref_tracker_state(tr)
+        L.ref_tracker_destroy(tr)
+        lines = [ln.replace("-nan", "nan") for ln in self.take_log().splitlines() if ln.startswith("[")]
+        pats = [(1, re.compile(r"\[(\d+)\] HUNTING→VERIFYING \(corr=(\S+), raw=(\S+)\)$")),
+                (2, re.compile(r"\[(\d+)\] VERIFYING→LOCKED \(frame (-?\d+)\)$")),
+                (3, re.compile(r"\[(\d+)\] LOCKED: sync OK \(corr=(\S+)\)$")),
+                (4, re.compile(r"\[(\d+)\] LOCKED: sync MISS #(\d+) \(corr=(\S+)\)$")),
+                (5, re.compile(r"\[(\d+)\] LOCKED→HUNTING \(lost lock\)$"))]
+        events = np.zeros(len(lines), EVENT_DTYPE)
+        for e, ln in zip(events, lines):
+            for kind, pat in pats:
+                m = pat.match(ln)
+                if m:
+                    break
+            assert m, ln
+            e["kind"], e["sym_idx"] = kind, int(m.group(1))
+            if kind == 1:
+                e["corr"], e["raw"] = float(m.group(2)), float(m.group(3))
+            elif kind == 2:
+                e["count"] = int(m.group(2))
+            elif kind == 3:
+                e["corr"] = float(m.group(2))
+            elif kind == 4:
+                e["count"], e["corr"] = int(m.group(2)), float(m.group(3))
+
+        def decode(p):
+            return self.frame_decode(p)
+        res = _track_result(rel, events, state, soft.size, decode)
+        res["log"] = lines
+        return res
 
     def receive(self, iq, streaming=True, init_offset=None, afc_alpha=0.001, coherent=False, pll_bw=50.0):
         """Drive the reference classes the way the reference's main() does

@@ -732,7 +732,9 @@ def test_api_misuse_returns_errors_and_leaves_the_context_usable(amd):
            ("opv_tx_modulate_device", (ctx, p, 1, C.c_void_p(4))), ("opv_tx_modulate_device_to_host", (ctx, None, 0, None)),
            ("opv_gather_frames", (ctx, None, 0, None, None)), ("opv_gather_frames", (None, None, 0, None, None)), ("opv_gather_frames_all", (None, None, 0, 0, None, None)),
            ("opv_comm_init", (None, 1, 0, None, 0)), ("opv_comm_init_all", (None, 0, None)), ("opv_comm_unique_id", (None,)), ("opv_kernel_times", (ctx, None)),
-           ("opv_enable_timing", (None, 1))]
+           ("opv_enable_timing", (None, 1)),
+           ("opv_tap_push_soft", (None, 0, p, 10)), ("opv_tap_push_soft", (ctx, 7, p, 10)), ("opv_tap_push_soft", (ctx, -1, p, 10)),
+           ("opv_tap_push_soft", (ctx, 0, None, 10)), ("opv_tap_push_soft", (ctx, 0, p, 0)), ("opv_tap_push_soft", (ctx, 0, p, 10 ** 9))]
     noop = [("opv_push_iq", (ctx, 0, p, 0)), ("opv_push_iq", (ctx, 0, None, 0)), ("opv_push_iq_batch", (ctx, 0, None, None, None)),
             ("opv_pop_frames", (ctx, 0, None, 10, None)), ("opv_pop_frames", (ctx, 0, p, 0, None)), ("opv_pop_events", (ctx, 0, None, 5)),
             ("opv_tap_soft", (ctx, 0, 0, None, 10)), ("opv_decode_payloads", (ctx, p, 0, p, p, None, None, None))]

@@ -23,22 +23,17 @@
 //     three per-lane groups (q < 5, q < 10, q < 15); a gate is a 0/1-weighted sum of groups (the five segments [0,10) [10,20)
 //     [20,40) [40,50) [50,60) of the sample axis meet lane boundaries at 15, 30, 45), reduced over the quad by two
 //     quad_perm steps;
-//   * every stream-level quantity (pos, fo, tf, previous sums, chunk bookkeeping) lives in VGPRs, replicated over the 4
-//     lanes of its quad; quads run their own chunk schedule under exec masks, batches as in k_frontend_x4.hip;
+//   * every stream-level quantity lives in VGPRs, replicated over the 4 lanes of its quad (k_frontend_rows.h: RowStream);
 //   * int16 IQ: a 256-sample ring per quad in LDS (+ a 16-sample guard mirroring its head). Every second symbol each
 //     quad requests the 16-sample blocks (64 B: one 16-byte load per lane, all sixteen quads in ONE instruction) that the two
 //     symbols AFTER the next refill point will need, holds them in registers, and writes them into its ring at that next
 //     point: two symbols of latency budget, no scalar bookkeeping per block, the HBM stream of a quad stays sequential.
 //
-// Differences from the reference are of the same kind and size as the other mappings' (shared interpolation fraction,
-// factored LO, FMA, table atan2, and here one rotation-free re-association of the early / late sums): soft symbols agree to
-// ~1e-14 of their mean, every decision downstream is identical (tests/test_gpu_parity.py runs every mapping).
-#include <hip/hip_runtime.h>
-#include <math.h>
-
+// Differences from the reference: as k_frontend_x4.hip states, and here one rotation-free re-association of the early /
+// late sums.
 #include <type_traits>
 
-#include "k_frontend_common.h"
+#include "k_frontend_rows.h"
 
 namespace {
 
@@ -109,37 +104,15 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
     const double kf0 = (double)(15 * t - 10);
     const double kfs0 = kf0 * kDeltaPerHz;
     const double kgain = st.afc_alpha * (kSymRate / kTwoPi);
-    // ---- carry (row-uniform, in VGPRs) ----------------------------------------------------------
-    double fo = st.freq_offset, tf = st.timing_freq, mu = st.mu, fo_sum = st.fo_sum;
-    PrevSums pv{st.p1r, st.p1i, st.p2r, st.p2i, st.x40c, st.x40s};
-    uint32_t origin = (uint32_t)st.origin;
-    const uint32_t n_avail = (uint32_t)st.n_avail;
-    uint64_t n_soft = st.n_soft, total_samples = st.total_samples;
-    uint32_t n_chunks = st.n_chunks;
-    int tail_done = st.tail_done, overflow = st.overflow, stalled = 0;
-    uint32_t edge_ties = st.edge_ties;
-    const int eof = st.eof;
-    const uint64_t cap_soft = st.cap_soft;
-    if (cap_soft > (1ull << 28)) overflow = 1;
-    uint64_t soft_keep = st.trk_next >= 24 ? st.trk_next - 24 : 0;
-    if (st.trk_state != 0 && st.trk_anchor < soft_keep) soft_keep = st.trk_anchor;
-    const uint32_t soft_bmask = (uint32_t)(cap_soft * 8u - 1u) & ~7u;
-    gbyte* const soft_base = (gbyte*)st.soft;
-    const gbyte* const iq_bytes = (const gbyte*)st.iq;
-    const uint64_t n_bytes = (uint64_t)n_avail * 4u;
-    double* const chunk_log = st.chunk_log;
-    const uint32_t cap_chunks = st.cap_chunks;
-
-    // ---- call state ---------------------------------------------------------------------------------
-    bool done = !have, in_call = false, first = false, last = false;
-    uint32_t N = 0, soft_off = 0, soft_off0 = 0;
-    double Nd = 0.0, pos = 0.0;
+    // ---- carry and call state (row-uniform, in VGPRs: k_frontend_rows.h) ------------------------------
+    RowStream rs;
+    rs.load(st, have);
 
     // ---- ring refill (see the rule at kAhead) --------------------------------------------------------------------
     // hi: the quad's ring holds (or has in flight) absolute samples [.., hi); blocks of 16 samples, 64 B aligned in the capture.
     uint32_t hi;
     {
-        const uint32_t g0 = origin + (uint32_t)(int)mu;
+        const uint32_t g0 = rs.origin + (uint32_t)(int)rs.mu;
         hi = (g0 >= 11u ? g0 - 11u : 0u) & ~(kBlk - 1u);
     }
     v4i blkv[kBlocksPerPoint];
@@ -147,11 +120,11 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
     auto load_block = [&](uint32_t h) -> v4i {           // this lane's 16 bytes of block [h, h + 16)
         const uint64_t off = (uint64_t)h * 4u + (uint32_t)t * 16u;
         v4i v = {0, 0, 0, 0};
-        if (off + 16u <= n_bytes) v = *reinterpret_cast<const __attribute__((address_space(1))) v4i*>(iq_bytes + off);
-        else if (off < n_bytes) {                         // the capture's last, incomplete 16 bytes: nothing past n_avail is read
+        if (off + 16u <= rs.n_bytes) v = *reinterpret_cast<const __attribute__((address_space(1))) v4i*>(rs.iq_bytes + off);
+        else if (off < rs.n_bytes) {                         // the capture's last, incomplete 16 bytes: nothing past n_avail is read
             int e[4] = {0, 0, 0, 0};
-            for (uint32_t j = 0; j < 4u && off + 4u * j < n_bytes; ++j)
-                e[j] = *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + off + 4u * j);
+            for (uint32_t j = 0; j < 4u && off + 4u * j < rs.n_bytes; ++j)
+                e[j] = *reinterpret_cast<const __attribute__((address_space(1))) int*>(rs.iq_bytes + off + 4u * j);
             v = v4i{e[0], e[1], e[2], e[3]};
         }
         return v;
@@ -170,7 +143,7 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
     auto request = [&](bool wants, uint32_t g) {          // at most kBlocksPerPoint blocks towards hi >= g + kAhead
         blk_hi0 = hi;
         uint32_t n = 0;
-        if (wants && hi < g + kAhead && (uint64_t)hi * 4u < n_bytes) {
+        if (wants && hi < g + kAhead && (uint64_t)hi * 4u < rs.n_bytes) {
             n = (g + kAhead - hi + kBlk - 1u) / kBlk;
             if (n > (uint32_t)kBlocksPerPoint) n = (uint32_t)kBlocksPerPoint;
         }
@@ -180,29 +153,16 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
         blk_n = n;
         hi += kBlk * n;
     };
-    // Soft symbols are written four at a time: lane t < 4 of a row keeps the value of the symbol with
-    // iter % 4 == t and stores it at the next refill point, right AFTER that point's s_waitcnt - a store
-    // per symbol would put a fresh store in front of every vmcnt(0) and make the wave wait out its latency.
-    double held = 0.0;
-    uint32_t held_off = 0;
-    bool held_valid = false;
-    auto flush_soft = [&]() {
-        if (held_valid) *(gdouble*)(soft_base + held_off) = held;
-        held_valid = false;
-    };
     // One symbol of every quad that executes this (exec = the quads inside a demodulate() call whose next symbol exists).
-    // Generic: with the tests the first symbols of a call need (early gate before the chunk, no AFC on the first symbol,
-    // an out-of-range -o still in force). Fast: the same statements without them - bit-identical where both apply
-    // (no contraction, no re-association) - for the batches below. `slot`: which of a quad's four lanes keeps
-    // this symbol's soft value until the next flush.
+    // Generic / fast: RowStream::finish_symbol. `slot`: which of a quad's four lanes keeps this symbol's soft value.
     auto symbol_body = [&](auto generic_tag, uint32_t slot) {
         constexpr bool kGeneric = decltype(generic_tag)::value;
         // ---- taps (ref :122-128, :232-238): sixteen consecutive samples -> fifteen interpolations ---------------
-        const double pf = pos + kf0;
+        const double pf = rs.pos + kf0;
         const double fl = floor(pf);
         const double f = pf - fl;
         const int i0 = (int)fl;
-        const uint32_t byte0 = (((uint32_t)(i0 + (int)origin)) << 2) & (kRingBytes - 1u);
+        const uint32_t byte0 = (((uint32_t)(i0 + (int)rs.origin)) << 2) & (kRingBytes - 1u);
         int w[16];
         {
             const int* tap = reinterpret_cast<const int*>(ring + byte0);
@@ -212,16 +172,16 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
         __builtin_amdgcn_sched_barrier(0);                              // taps requested FIRST, the LO seed under their latency
         // ---- LO: X[m] for m = 15 t - 10 + q: seed and step ---------------------------------------------------------
         double xs, xc, s1, c1;
-        expj_small10(kfs0 * fo, xs, xc);
-        expj_small10(kDeltaPerHz * fo, s1, c1);
-        if (kGeneric && fabs(fo) > 2000.0) {
+        expj_small10(kfs0 * rs.fo, xs, xc);
+        expj_small10(kDeltaPerHz * rs.fo, s1, c1);
+        if (kGeneric && fabs(rs.fo) > 2000.0) {
             // -o takes any value (ref :1004-1005) and the AFC clamp (:303) first acts at the END of the
             // call's second symbol: outside the polynomial's range those symbols take the full-range routine
-            sincos(kfs0 * fo, &xs, &xc);
-            sincos(kDeltaPerHz * fo, &s1, &c1);
+            sincos(kfs0 * rs.fo, &xs, &xc);
+            sincos(kDeltaPerHz * rs.fo, &s1, &c1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        const int s0_first = (kGeneric && first) ? *reinterpret_cast<const int*>(ring + ((origin << 2) & (kRingBytes - 1u))) : 0;
+        const int s0_first = (kGeneric && rs.first) ? *reinterpret_cast<const int*>(ring + ((rs.origin << 2) & (kRingBytes - 1u))) : 0;
 
         double g0A = 0, g0B = 0, g0C = 0, g0D = 0, g1A = 0, g1B = 0, g1C = 0, g1D = 0, g2A = 0, g2B = 0, g2C = 0, g2D = 0;
         double x40c_l = 0.0, x40s_l = 0.0;
@@ -233,7 +193,7 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
             asm("" : "+v"(nr), "+v"(ni));                          // (opaque: hipcc otherwise subtracts the int16 values and widens the difference too - 60 conversions instead of 32)
             double lr = fma(f, nr - pr, pr);                       // (differences of int16 values are exact in fp64)
             double li = fma(f, ni - pi_, pi_);
-            if (kGeneric && first && pf + (double)q < 0.0) {        // early gate before the chunk: s[0] (ref :237)
+            if (kGeneric && rs.first && pf + (double)q < 0.0) {        // early gate before the chunk: s[0] (ref :237)
                 lr = (double)(int)(short)(s0_first & 0xFFFF);
                 li = (double)(s0_first >> 16);
             }
@@ -256,14 +216,8 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
         double o1 = fma(wO2, g2A, fma(wO1, g1A, wO0 * g0A)), o2 = fma(wO2, g2B, fma(wO1, g1B, wO0 * g0B));
         double o3 = fma(wO2, g2C, fma(wO1, g1C, wO0 * g0C)), o4 = fma(wO2, g2D, fma(wO1, g1D, wO0 * g0D));
         quad_sum4(o1, o2, o3, o4);
-        const double P1o = o1, P2o = o2, P3o = o3, P4o = o4;
-        const double s1r_ = P1o + P2o, s1i_ = P3o - P4o;
-        const double s2r_ = P1o - P2o, s2i_ = P3o + P4o;
-        const double en1 = fma(s1r_, s1r_, s1i_ * s1i_);
-        const double en2 = fma(s2r_, s2r_, s2i_ * s2i_);
-        const double soft = en2 - en1;                      // ref :268
-        const double nsg = mkd((dhi(soft) & (int)0x80000000) | 0x3ff00000, 0);  // -1 iff tone 1 dominates
-        const double sg = -nsg;
+        const RowTone tn = RowStream::tone(o1, o2, o3, o4);
+        const double sg = -tn.nsg;
         // ---- early / late gates of the dominant tone (ref :271-280): rotated by a constant, only their norms are used ----
         const double r0 = fma(sg, g0B, g0A), i0_ = fma(-sg, g0D, g0C);
         const double r1 = fma(sg, g1B, g1A), i1_ = fma(-sg, g1D, g1C);
@@ -271,74 +225,13 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
         double Ere = fma(wE2, r2, fma(wE1, r1, wE0 * r0)), Eim = fma(wE2, i2_, fma(wE1, i1_, wE0 * i0_));
         double Lre = fma(wL2, r2, fma(wL1, r1, wL0 * r0)), Lim = fma(wL2, i2_, fma(wL1, i1_, wL0 * i0_));
         quad_sum4(Ere, Eim, Lre, Lim);
-        const double ee = fma(Ere, Ere, Eim * Eim), el = fma(Lre, Lre, Lim * Lim);
-        const double num = el - ee, den = el + ee + 1e-10;
-        // ---- phase detector operands: dom * conj(prev) (ref :289-299, see k_frontend.hip) -----
-        const double dr = fma(sg, P2o, P1o), di = fma(-sg, P4o, P3o);
-        const double prs = fma(sg, pv.a, pv.b), pis = fma(sg, pv.c, -pv.d);
-        const double ar = fma(dr, prs, di * pis), ai = fma(di, prs, -(dr * pis));
-        const double cy = fma(ar, pv.x40c, ai * pv.x40s);   // Im z
-        const double cx = fma(ar, pv.x40s, -(ai * pv.x40c)); // Re z
-        // the angle without an octant fix-up (opv_atan2.h: opv_atan2_q): atan(|cy| / |cx|) = pi/4 + atan(q),
-        // q = (|cy| - |cx|) / (|cy| + |cx|) in [-1, 1]
-        const double sum = fabs(cx) + fabs(cy), dif = fabs(cy) - fabs(cx);
-        // ---- the two divides on one reciprocal ------------------------------------------------
-        const double dm = sum + 1e-100;                     // the guard against digital silence: IS sum unless sum is 0 (k_frontend.hip)
-        const double tt = den * dm;
-        double y = __builtin_amdgcn_rcp(tt);
-        y = fma(fma(-tt, y, 1.0), y, y);                    // one Newton step (2^-24.4 -> 2^-48.7, scripts/microbench/rcp_accuracy.hip)
-        const double iden = y * dm, idm = y * den;
-        const double ratio = dif * idm;                     // good to 2^-48: 3.5e-15 rad on the angle
-        // the angle's table row is requested here and used after the timing loop: with one wave per SIMD nothing else
-        // covers the LDS round trip (the row index is in range on every path: |ratio| <= 1)
-        // nearest expansion point k/128 by the 1.5 * 2^52 trick: the sum's low word is the row index k + 128
-        const double kt = fma(ratio, 128.0, 6755399441055744.0 + 128.0);
-        const double h = fma(kt - (6755399441055744.0 + 128.0), -1.0 / 128.0, ratio);   // |h| <= 1/256
-        const double2* trow = reinterpret_cast<const double2*>(atab + (unsigned)dlo(kt) * 6u);
-        const double2 c45 = trow[2], c23 = trow[1], c01 = trow[0];
-        __builtin_amdgcn_sched_barrier(0);
-        double ted = num * iden;
-        ted = fma(fma(-den, ted, num), iden, ted);
-        // ---- timing loop (ref :283-286, :313) ------------------------------------------------
-        tf = clampd(fma(0.00001, ted, tf), -0.1, 0.1);
-        const double adj = fma(0.005, ted, tf);   // |adj| <= 0.105: the reference's clamp to +/-2 (:286) cannot act, see k_frontend.hip
-        double pos_next = pos + (40.0 + adj);
-        if ((uint32_t)t == slot) { held = soft; held_off = soft_off; held_valid = true; }
-        asm volatile("" : "+v"(pos_next), "+v"(tf), "+v"(held));   // (keeps these statements HERE: hipcc otherwise sinks them below the AFC block)
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- AFC (ref :289-306): not on the first symbol of a call -------------------------------
-        if (!kGeneric || !first) {
-            double pd = fma(c45.y, h, c45.x);                   // degree 5: pi/4 + atan(q)
-            pd = fma(pd, h, c23.y);
-            pd = fma(pd, h, c23.x);
-            pd = fma(pd, h, c01.y);
-            pd = fma(pd, h, c01.x);
-            const double sx = mkd((dhi(cx) & (int)0x80000000) | 0x3ff00000, 0);
-            pd = fma(sx, pd, fma(-sx, 1.57079632679489661923, 1.57079632679489661923));
-            pd = mkd((dhi(pd) & 0x7fffffff) | (dhi(cy) & (int)0x80000000), dlo(pd));
-            if (sum == 0.0) {                                // digital silence on either side
-                const double2 sp = silence_pd(dr, di, pv, soft < 0.0, fo_sum,
-                                              (uint32_t)n_soft + (((soft_off - soft_off0) & soft_bmask) >> 3),
-                                              P1o, P2o, P3o, P4o);
-                pd = sp.x;
-                edge_ties += (uint32_t)sp.y;
-            }
-            const double fo_used = fo;
-            fo = clampd(fma(kgain, pd, fo), -2000.0, 2000.0);
-            fo_sum += fo_used;
-        } else {
-            fo_sum += fo;
-        }
-        soft_off = (soft_off + 8u) & soft_bmask;
-        pv.a = P1o; pv.b = P2o; pv.c = P3o; pv.d = P4o; pv.x40c = x40c; pv.x40s = x40s;
-        pos = pos_next;
-        first = false;
+        rs.finish_symbol<kGeneric>(o1, o2, o3, o4, tn.soft, sg, Ere, Eim, Lre, Lim, x40c, x40s, atab, kgain, (uint32_t)t == slot);
     };
     // ---- initial fill: everything the first two symbols can read, synchronously ---------------------------------
     {
-        const uint32_t g = origin + (uint32_t)(int)mu;
+        const uint32_t g = rs.origin + (uint32_t)(int)rs.mu;
         for (int rep = 0; rep < 3; ++rep) {                // (198 samples = 13 blocks at most)
-            request(!done, g);
+            request(!rs.done, g);
             __builtin_amdgcn_s_waitcnt(0x0F70);            // vmcnt(0)
             write_held();
         }
@@ -350,103 +243,40 @@ __device__ __forceinline__ void msk_frontend_x16_body(OpvStream* __restrict__ st
     auto refill_point = [&](bool flush) {
         __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): blocks and stores issued two symbols ago
         write_held();
-        if (flush) flush_soft();
-        request(in_call, origin + (uint32_t)(int)pos);
+        if (flush) rs.flush_soft();
+        request(rs.in_call, rs.origin + (uint32_t)(int)rs.pos);
     };
 
     for (uint32_t iter = 0;; ++iter) {
-        // ---- which demodulate() call comes next (ref :1026 / :1088 / :1173) ---------------------
-        if (!in_call && !done) {
-            const uint32_t remaining = n_avail - origin;
-            bool go = true;
-            last = false;
-            if (cfg.streaming) {
-                if (remaining >= OPV_CHUNK) N = OPV_CHUNK;
-                else if (eof && !tail_done && remaining > 0) { N = remaining; last = true; }
-                else { if (eof) tail_done = 1; go = false; }
-            } else {
-                if (!eof || tail_done) go = false;
-                else { N = n_avail; last = true; }
-            }
-            if (go && overflow) go = false;
-            if (go && (n_soft - soft_keep) + (uint64_t)(N / 38u + 2u) > cap_soft) { stalled = 1; go = false; }  // back-pressure, see k_frontend.hip
-            if (go) {
-                in_call = true;
-                first = true;
-                Nd = (double)N;
-                pos = mu;                                          // ref :217
-                soft_off0 = ((uint32_t)n_soft * 8u) & soft_bmask;
-                soft_off = soft_off0;
-            } else {
-                done = true;
-            }
-        }
-        if (__ballot(in_call) == 0ull) break;
+        if (!rs.in_call && !rs.done) rs.begin_call(cfg);
+        if (__ballot(rs.in_call) == 0ull) break;
 
-        // ---- batches: as many symbols as EVERY quad inside a call can take without its end-of-call test, its first-symbol
-        // rules or an out-of-range -o (pos advances by at most 42 samples per symbol), in groups of four (the soft-log
-        // lanes and the refill points keep their rhythm). Quads outside a call are finished streams here: they sit the
-        // batch out under the exec mask.
+        // ---- batches: as many symbols as EVERY quad inside a call can take (RowStream::quota), in groups of four (the
+        // soft-log lanes and the refill points keep their rhythm)
         if ((iter & 3u) == 0u) {
-            int krow = 0x7fffffff;
-            if (in_call) {
-                krow = 0;
-                const double room = Nd - 51.0 - pos;
-                if (!first && !(fabs(fo) > 2000.0) && room > 0.0) krow = (int)(room * (1.0 / 42.0));
-            }
+            int krow = rs.quota();
 #pragma unroll
             for (int off = 32; off >= 4; off >>= 1) { const int o = __shfl_xor(krow, off, 64); krow = o < krow ? o : krow; }
             const int kmin = __builtin_amdgcn_readfirstlane(krow);
             for (uint32_t quads = (uint32_t)kmin >> 2; quads != 0u; --quads) {
                 refill_point(true);
-                if (in_call) { symbol_body(std::false_type{}, 0u); symbol_body(std::false_type{}, 1u); }
+                if (rs.in_call) { symbol_body(std::false_type{}, 0u); symbol_body(std::false_type{}, 1u); }
                 refill_point(false);
-                if (in_call) { symbol_body(std::false_type{}, 2u); symbol_body(std::false_type{}, 3u); }
+                if (rs.in_call) { symbol_body(std::false_type{}, 2u); symbol_body(std::false_type{}, 3u); }
                 iter += 4u;
             }
         }
 
         if ((iter & 1u) == 0u) refill_point((iter & 3u) == 0u);
 
-        if (in_call) {
-            if (pos + 40.0 + 10.0 < Nd) {                          // ref :221
-                symbol_body(std::true_type{}, iter & 3u);
-            } else {
-                // ---- end of this demodulate() call (ref :318-328, :1067-1076) ---------------------
-                const uint32_t nsym_call = ((soft_off - soft_off0) & soft_bmask) >> 3;
-                const uint32_t used = (uint32_t)pos;
-                mu = pos - (double)used;
-                const uint32_t leftover = N - used;
-                if (t == 0) {
-                    double* c = chunk_log + 5 * (size_t)(n_chunks % cap_chunks);
-                    c[0] = fo; c[1] = tf; c[2] = mu; c[3] = (double)leftover; c[4] = (double)nsym_call;
-                }
-                ++n_chunks;
-                n_soft += nsym_call;
-                total_samples += N;
-                origin += (leftover > 0u && leftover < N) ? used : N;
-                in_call = false;
-                if (last) { tail_done = 1; done = true; }
-            }
+        if (rs.in_call) {
+            if (rs.has_symbol()) symbol_body(std::true_type{}, iter & 3u);
+            else rs.end_call(t == 0);
         }
     }
 
-    flush_soft();
-    if (have && t == 0) {
-        st.freq_offset = fo; st.timing_freq = tf; st.mu = mu;
-        st.p1r = pv.a; st.p1i = pv.b; st.p2r = pv.c; st.p2i = pv.d; st.x40c = pv.x40c; st.x40s = pv.x40s;
-        st.fo_sum = fo_sum;
-        st.origin = origin; st.n_soft = n_soft; st.total_samples = total_samples;
-        st.n_chunks = n_chunks; st.tail_done = tail_done; st.overflow = overflow;
-        st.stalled = stalled; st.edge_ties = edge_ties;
-        // where and at which clock the wave that carried this stream (and fifteen others) ran (opv_tap_wave_info)
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        st.dbg_hw_id = hw; st.dbg_xcc_id = xcc;
-        st.dbg_cycles = __builtin_amdgcn_s_memtime() - dbg_t0;
-        st.dbg_ticks = __builtin_amdgcn_s_memrealtime() - dbg_r0;
-    }
+    rs.flush_soft();
+    if (have && t == 0) rs.store(st, dbg_t0, dbg_r0);
 }
 
 extern "C" __global__ __launch_bounds__(64) void k_msk_frontend_x16(OpvStream* __restrict__ streams, OpvGlobalCfg cfg,

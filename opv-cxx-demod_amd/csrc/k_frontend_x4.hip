@@ -26,8 +26,7 @@
 //     outside the window, so a lane accumulates its (up to) four taps per gate in registers;
 //   * X[m] = exp(j m d) for m = t - 10 by the same polynomial, X[m+16 q] by three complex multiplies
 //     with X[16];
-//   * every stream-level quantity (pos, fo, tf, previous sums, chunk bookkeeping) lives in VGPRs,
-//     replicated over the 16 lanes of its row; rows run their own chunk schedule under exec masks;
+//   * every stream-level quantity lives in VGPRs, replicated over the 16 lanes of its row (k_frontend_rows.h: RowStream);
 //   * int16 IQ: a 1024-sample ring per row in LDS (+ 60-sample guard mirroring its head), refilled in
 //     256-sample blocks (one direct-to-LDS 16 B/lane load of the WHOLE wave per row and block), requested
 //     one refill point (four symbols) before their first use and awaited with one s_waitcnt vmcnt(0) there.
@@ -35,12 +34,9 @@
 // Differences from the reference are of the same kind and size as k_frontend.hip's (shared
 // interpolation fraction, factored LO, FMA, table atan2): soft symbols agree to ~1e-14 of their mean,
 // every decision downstream is identical (tests/test_gpu_parity.py runs both mappings).
-#include <hip/hip_runtime.h>
-#include <math.h>
-
 #include <type_traits>
 
-#include "k_frontend_common.h"
+#include "k_frontend_rows.h"
 
 namespace {
 
@@ -85,7 +81,7 @@ __device__ inline void row_sum4(double& a, double& b, double& c, double& d, doub
 }  // namespace
 
 // this translation unit's own image of the angle table (opv_atan2.h: kOpvAtanTabQ): every .hip file is compiled to a
-// code object of its own (no relocatable device code), so that the two front-end files can go through tools/align_vop3.py
+// code object of its own (no relocatable device code), so that the front-end files can go through tools/align_vop3.py
 __constant__ double kOpvAtanTabQx4[257][6] = {
 #include "opv_atan_table_q.inc"
 };
@@ -126,31 +122,9 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
     double kc_one = 1.0;                                // the broadcast FMACs' second factor has to be a VGPR
     asm volatile("" : "+v"(kc_one));
 
-    // ---- carry (row-uniform, in VGPRs) ----------------------------------------------------------
-    double fo = st.freq_offset, tf = st.timing_freq, mu = st.mu, fo_sum = st.fo_sum;
-    PrevSums pv{st.p1r, st.p1i, st.p2r, st.p2i, st.x40c, st.x40s};
-    uint32_t origin = (uint32_t)st.origin;
-    const uint32_t n_avail = (uint32_t)st.n_avail;
-    uint64_t n_soft = st.n_soft, total_samples = st.total_samples;
-    uint32_t n_chunks = st.n_chunks;
-    int tail_done = st.tail_done, overflow = st.overflow, stalled = 0;
-    uint32_t edge_ties = st.edge_ties;
-    const int eof = st.eof;
-    const uint64_t cap_soft = st.cap_soft;
-    if (cap_soft > (1ull << 28)) overflow = 1;
-    uint64_t soft_keep = st.trk_next >= 24 ? st.trk_next - 24 : 0;
-    if (st.trk_state != 0 && st.trk_anchor < soft_keep) soft_keep = st.trk_anchor;
-    const uint32_t soft_bmask = (uint32_t)(cap_soft * 8u - 1u) & ~7u;
-    gbyte* const soft_base = (gbyte*)st.soft;
-    const gbyte* const iq_bytes = (const gbyte*)st.iq;
-    const uint64_t n_bytes = (uint64_t)n_avail * 4u;
-    double* const chunk_log = st.chunk_log;
-    const uint32_t cap_chunks = st.cap_chunks;
-
-    // ---- call state ---------------------------------------------------------------------------------
-    bool done = !have, in_call = false, first = false, last = false;
-    uint32_t N = 0, soft_off = 0, soft_off0 = 0;
-    double Nd = 0.0, pos = 0.0;
+    // ---- carry and call state (row-uniform, in VGPRs: k_frontend_rows.h) ------------------------------
+    RowStream rs;
+    rs.load(st, have);
 
     // ---- ring refill ------------------------------------------------------------------------------
     // hi: the row's ring holds absolute samples [hi - 1024, hi) (as far as the capture reaches); blocks of 256 samples,
@@ -166,24 +140,24 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
     };
     uint32_t hi;
     {
-        const uint32_t g0 = origin + (uint32_t)(int)mu;
+        const uint32_t g0 = rs.origin + (uint32_t)(int)rs.mu;
         hi = (g0 >= 11u ? g0 - 11u : 0u) & ~(kBlock - 1u);
     }
     auto issue_block = [&](uint32_t dst_off) {   // the calling lanes are the 16 lanes of ONE row
         const uint64_t off = (uint64_t)hi * 4u + (uint32_t)t * 16u;
         const uint32_t m0v = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ring_lds + dst_off - 256u * (uint32_t)row));
-        if (off + 16u <= n_bytes) glds16(iq_bytes + off, m0v);
-        else if (off < n_bytes) {   // the capture's last, incomplete 16 bytes: nothing past n_avail is read
-            for (uint32_t j = 0; off + 4u * j < n_bytes; ++j)
+        if (off + 16u <= rs.n_bytes) glds16(rs.iq_bytes + off, m0v);
+        else if (off < rs.n_bytes) {   // the capture's last, incomplete 16 bytes: nothing past n_avail is read
+            for (uint32_t j = 0; off + 4u * j < rs.n_bytes; ++j)
                 *reinterpret_cast<int*>(lds + (uint32_t)row * kRowBytes + dst_off + (uint32_t)t * 16u + 4u * j) =
-                    *reinterpret_cast<const __attribute__((address_space(1))) int*>(iq_bytes + off + 4u * j);
+                    *reinterpret_cast<const __attribute__((address_space(1))) int*>(rs.iq_bytes + off + 4u * j);
         }
     };
     auto issue_wide = [&](int r, uint32_t hi_r) {   // all 64 lanes; r is a constant after unrolling
-        const uint32_t nb_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)n_bytes, 16 * r);
-        const uint32_t nb_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(n_bytes >> 32), 16 * r);
+        const uint32_t nb_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)rs.n_bytes, 16 * r);
+        const uint32_t nb_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(rs.n_bytes >> 32), 16 * r);
         const uint64_t nb = ((uint64_t)nb_hi << 32) | nb_lo;
-        const uint64_t pb = (uint64_t)(uintptr_t)iq_bytes;
+        const uint64_t pb = (uint64_t)(uintptr_t)rs.iq_bytes;
         const uint32_t p_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pb, 16 * r);
         const uint32_t p_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(pb >> 32), 16 * r);
         const gbyte* src = (const gbyte*)(uintptr_t)(((uint64_t)p_hi << 32) | p_lo);
@@ -198,7 +172,7 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
     };
     auto refill = [&](bool wants, uint32_t g, int max_rounds) {
         for (int rep = 0; rep < max_rounds; ++rep) {
-            const bool need = wants && hi < g + kAheadMin && (uint64_t)hi * 4u < n_bytes;
+            const bool need = wants && hi < g + kAheadMin && (uint64_t)hi * 4u < rs.n_bytes;
             const uint64_t m = __ballot(need);
             if (m == 0ull) break;
 #pragma unroll
@@ -214,29 +188,16 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
             if (need) hi += kBlock;
         }
     };
-    // Soft symbols are written four at a time: lane t < 4 of a row keeps the value of the symbol with
-    // iter % 4 == t and stores it at the next refill point, right AFTER that point's s_waitcnt - a store
-    // per symbol would put a fresh store in front of every vmcnt(0) and make the wave wait out its latency.
-    double held = 0.0;
-    uint32_t held_off = 0;
-    bool held_valid = false;
-    auto flush_soft = [&]() {
-        if (held_valid) *(gdouble*)(soft_base + held_off) = held;
-        held_valid = false;
-    };
     // One symbol of every row that executes this (exec = the rows inside a demodulate() call whose next symbol exists).
-    // Generic: with the tests the first symbols of a call need (early gate before the chunk, no AFC on the first symbol,
-    // an out-of-range -o still in force). Fast: the same statements without them - bit-identical where both apply
-    // (no contraction, no re-association) - for the batches below. `slot`: which of a row's four soft-log lanes keeps
-    // this symbol's value until the next flush.
+    // Generic / fast: RowStream::finish_symbol. `slot`: which of a row's four soft-log lanes keeps this symbol's value.
     auto symbol_body = [&](auto generic_tag, uint32_t slot) {
         constexpr bool kGeneric = decltype(generic_tag)::value;
         // ---- taps (ref :122-128, :232-238) --------------------------------------------------
-        const double pf = pos + kf0;
+        const double pf = rs.pos + kf0;
         const double fl = floor(pf);
         const double f = pf - fl;
         const int i0 = (int)fl;
-        const uint32_t byte0 = (((uint32_t)(i0 + (int)origin)) << 2) & (kRingBytes - 1u);
+        const uint32_t byte0 = (((uint32_t)(i0 + (int)rs.origin)) << 2) & (kRingBytes - 1u);
         int w0[4], w1[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -245,25 +206,25 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
             w1[q] = tap[1];
         }
         __builtin_amdgcn_sched_barrier(0);                              // taps requested FIRST, the LO under their latency
-        if (kGeneric && first && pf < 0.0) {                           // early gate before the chunk: s[0] (ref :237)
-            const int s0 = *reinterpret_cast<const int*>(ring + ((origin << 2) & (kRingBytes - 1u)));
+        if (kGeneric && rs.first && pf < 0.0) {                           // early gate before the chunk: s[0] (ref :237)
+            const int s0 = *reinterpret_cast<const int*>(ring + ((rs.origin << 2) & (kRingBytes - 1u)));
             w0[0] = s0;
             w1[0] = s0;
         }
         // ---- LO: X[m] for m = t - 10 + 16 q ---------------------------------------------------
         double xs[4], xc[4], s16, c16;
-        expj_small10(kfs0 * fo, xs[0], xc[0]);
-        expj_small10((16.0 * kDeltaPerHz) * fo, s16, c16);
+        expj_small10(kfs0 * rs.fo, xs[0], xc[0]);
+        expj_small10((16.0 * kDeltaPerHz) * rs.fo, s16, c16);
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
             xc[q] = fma(xc[q - 1], c16, -(xs[q - 1] * s16));
             xs[q] = fma(xc[q - 1], s16, xs[q - 1] * c16);
         }
-        if (kGeneric && fabs(fo) > 2000.0) {
+        if (kGeneric && fabs(rs.fo) > 2000.0) {
             // -o takes any value (ref :1004-1005) and the AFC clamp (:303) first acts at the END of the
             // call's second symbol: outside the polynomial's range those symbols take the full-range routine
 #pragma unroll
-            for (int q = 0; q < 4; ++q) sincos((kfs0 + (16.0 * q) * kDeltaPerHz) * fo, &xs[q], &xc[q]);
+            for (int q = 0; q < 4; ++q) sincos((kfs0 + (16.0 * q) * kDeltaPerHz) * rs.fo, &xs[q], &xc[q]);
         }
         // X[40] = exp(j 40 d), needed by the NEXT symbol's phase detector: it is lane 2's fourth tap (m = 2 - 10 + 48),
         // handed to the row by v_mov_b64_dpp row_newbcast:2 (`old` operands: the two dead X[16] registers)
@@ -290,134 +251,35 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
         }
         // ---- on-time gate: soft value, dominant tone (ref :264-272) --------------------------
         row_sum4(o1, o2, o3, o4, kc_one);
-        const double P1o = o1, P2o = o2, P3o = o3, P4o = o4;
-        const double s1r_ = P1o + P2o, s1i_ = P3o - P4o;
-        const double s2r_ = P1o - P2o, s2i_ = P3o + P4o;
-        const double en1 = fma(s1r_, s1r_, s1i_ * s1i_);
-        const double en2 = fma(s2r_, s2r_, s2i_ * s2i_);
-        const double soft = en2 - en1;                      // ref :268
-        const double nsg = mkd((dhi(soft) & (int)0x80000000) | 0x3ff00000, 0);  // -1 iff tone 1 dominates
-        const double sg = -nsg;
+        const RowTone tn = RowStream::tone(o1, o2, o3, o4);
+        const double sg = -tn.nsg;
         // ---- early / late gates of the dominant tone (ref :271-280) ---------------------------
         double Ere = fma(sg, eC, eA), Eim = fma(-sg, eD, eB), Lre = fma(sg, lC, lA), Lim = fma(-sg, lD, lB);
         row_sum4(Ere, Eim, Lre, Lim, kc_one);
-        const double ee = fma(Ere, Ere, Eim * Eim), el = fma(Lre, Lre, Lim * Lim);
-        const double num = el - ee, den = el + ee + 1e-10;
-        // ---- phase detector operands: dom * conj(prev) (ref :289-299, see k_frontend.hip) -----
-        const double dr = fma(sg, P2o, P1o), di = fma(-sg, P4o, P3o);
-        const double prs = fma(sg, pv.a, pv.b), pis = fma(sg, pv.c, -pv.d);
-        const double ar = fma(dr, prs, di * pis), ai = fma(di, prs, -(dr * pis));
-        const double cy = fma(ar, pv.x40c, ai * pv.x40s);   // Im z
-        const double cx = fma(ar, pv.x40s, -(ai * pv.x40c)); // Re z
-        // the angle without an octant fix-up (opv_atan2.h: opv_atan2_q): atan(|cy| / |cx|) = pi/4 + atan(q),
-        // q = (|cy| - |cx|) / (|cy| + |cx|) in [-1, 1]
-        const double sum = fabs(cx) + fabs(cy), dif = fabs(cy) - fabs(cx);
-        // ---- the two divides on one reciprocal ------------------------------------------------
-        const double dm = sum + 1e-100;                     // the guard against digital silence: IS sum unless sum is 0 (k_frontend.hip)
-        const double tt = den * dm;
-        double y = __builtin_amdgcn_rcp(tt);
-        y = fma(fma(-tt, y, 1.0), y, y);                    // one Newton step (2^-24.4 -> 2^-48.7, scripts/microbench/rcp_accuracy.hip)
-        const double iden = y * dm, idm = y * den;
-        const double ratio = dif * idm;                     // good to 2^-48: 3.5e-15 rad on the angle
-        // the angle's table row is requested here and used after the timing loop: with one wave per SIMD nothing else
-        // covers the LDS round trip (the row index is in range on every path: |ratio| <= 1)
-        // nearest expansion point k/128 by the 1.5 * 2^52 trick: the sum's low word is the row index k + 128
-        const double kt = fma(ratio, 128.0, 6755399441055744.0 + 128.0);
-        const double h = fma(kt - (6755399441055744.0 + 128.0), -1.0 / 128.0, ratio);   // |h| <= 1/256
-        const double2* trow = reinterpret_cast<const double2*>(atab + (unsigned)dlo(kt) * 6u);
-        const double2 c45 = trow[2], c23 = trow[1], c01 = trow[0];
-        __builtin_amdgcn_sched_barrier(0);
-        double ted = num * iden;
-        ted = fma(fma(-den, ted, num), iden, ted);
-        // ---- timing loop (ref :283-286, :313) ------------------------------------------------
-        tf = clampd(fma(0.00001, ted, tf), -0.1, 0.1);
-        const double adj = fma(0.005, ted, tf);   // |adj| <= 0.105: the reference's clamp to +/-2 (:286) cannot act, see k_frontend.hip
-        double pos_next = pos + (40.0 + adj);
-        if ((uint32_t)t == slot) { held = soft; held_off = soft_off; held_valid = true; }
-        asm volatile("" : "+v"(pos_next), "+v"(tf), "+v"(held));   // (keeps these statements HERE: hipcc otherwise sinks them below the AFC block)
-        __builtin_amdgcn_sched_barrier(0);
-        // ---- AFC (ref :289-306): not on the first symbol of a call -------------------------------
-        if (!kGeneric || !first) {
-            double pd = fma(c45.y, h, c45.x);                   // degree 5: pi/4 + atan(q)
-            pd = fma(pd, h, c23.y);
-            pd = fma(pd, h, c23.x);
-            pd = fma(pd, h, c01.y);
-            pd = fma(pd, h, c01.x);
-            const double sx = mkd((dhi(cx) & (int)0x80000000) | 0x3ff00000, 0);
-            pd = fma(sx, pd, fma(-sx, 1.57079632679489661923, 1.57079632679489661923));
-            pd = mkd((dhi(pd) & 0x7fffffff) | (dhi(cy) & (int)0x80000000), dlo(pd));
-            if (sum == 0.0) {                                // digital silence on either side
-                const double2 sp = silence_pd(dr, di, pv, soft < 0.0, fo_sum,
-                                              (uint32_t)n_soft + (((soft_off - soft_off0) & soft_bmask) >> 3),
-                                              P1o, P2o, P3o, P4o);
-                pd = sp.x;
-                edge_ties += (uint32_t)sp.y;
-            }
-            const double fo_used = fo;
-            fo = clampd(fma(kgain, pd, fo), -2000.0, 2000.0);
-            fo_sum += fo_used;
-        } else {
-            fo_sum += fo;
-        }
-        soft_off = (soft_off + 8u) & soft_bmask;
-        pv.a = P1o; pv.b = P2o; pv.c = P3o; pv.d = P4o; pv.x40c = x40c; pv.x40s = x40s;
-        pos = pos_next;
-        first = false;
+        rs.finish_symbol<kGeneric>(o1, o2, o3, o4, tn.soft, sg, Ere, Eim, Lre, Lim, x40c, x40s, atab, kgain, (uint32_t)t == slot);
     };
-    refill(!done, origin + (uint32_t)(int)mu, 4);
+    refill(!rs.done, rs.origin + (uint32_t)(int)rs.mu, 4);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     __syncthreads();                     // atan table visible (single wave: LDS ordering only)
 
     for (uint32_t iter = 0;; ++iter) {
-        // ---- which demodulate() call comes next (ref :1026 / :1088 / :1173) ---------------------
-        if (!in_call && !done) {
-            const uint32_t remaining = n_avail - origin;
-            bool go = true;
-            last = false;
-            if (cfg.streaming) {
-                if (remaining >= OPV_CHUNK) N = OPV_CHUNK;
-                else if (eof && !tail_done && remaining > 0) { N = remaining; last = true; }
-                else { if (eof) tail_done = 1; go = false; }
-            } else {
-                if (!eof || tail_done) go = false;
-                else { N = n_avail; last = true; }
-            }
-            if (go && overflow) go = false;
-            if (go && (n_soft - soft_keep) + (uint64_t)(N / 38u + 2u) > cap_soft) { stalled = 1; go = false; }  // back-pressure, see k_frontend.hip
-            if (go) {
-                in_call = true;
-                first = true;
-                Nd = (double)N;
-                pos = mu;                                          // ref :217
-                soft_off0 = ((uint32_t)n_soft * 8u) & soft_bmask;
-                soft_off = soft_off0;
-            } else {
-                done = true;
-            }
-        }
-        if (__ballot(in_call) == 0ull) break;
+        if (!rs.in_call && !rs.done) rs.begin_call(cfg);
+        if (__ballot(rs.in_call) == 0ull) break;
 
-        // ---- batches: as many symbols as EVERY row inside a call can take without its end-of-call test, its first-symbol
-        // rules or an out-of-range -o (pos advances by at most 42 samples per symbol), in groups of four (the soft-log
-        // lanes and the refill points keep their rhythm); the per-symbol bookkeeping of the loop below - what makes up a
-        // third of its instructions - is then paid once per batch. Rows outside a call are finished streams here (a row
-        // that could start a call has just done so and asks for 0): they sit the batch out under the exec mask.
+        // ---- batches: as many symbols as EVERY row inside a call can take (RowStream::quota), in groups of four (the
+        // soft-log lanes and the refill points keep their rhythm); the per-symbol bookkeeping of the loop below - what makes
+        // up a third of its instructions - is then paid once per batch.
         if ((iter & 3u) == 0u) {
-            int krow = 0x7fffffff;
-            if (in_call) {
-                krow = 0;
-                const double room = Nd - 51.0 - pos;
-                if (!first && !(fabs(fo) > 2000.0) && room > 0.0) krow = (int)(room * (1.0 / 42.0));
-            }
+            const int krow = rs.quota();
             int kmin = __builtin_amdgcn_readlane(krow, 0);
             { const int k1 = __builtin_amdgcn_readlane(krow, 16); kmin = k1 < kmin ? k1 : kmin; }
             { const int k2 = __builtin_amdgcn_readlane(krow, 32); kmin = k2 < kmin ? k2 : kmin; }
             { const int k3 = __builtin_amdgcn_readlane(krow, 48); kmin = k3 < kmin ? k3 : kmin; }
             for (uint32_t quads = (uint32_t)kmin >> 2; quads != 0u; --quads) {
                 __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): blocks and stores issued 4 symbols ago
-                flush_soft();
-                refill(in_call, origin + (uint32_t)(int)pos, 4);
-                if (in_call) {
+                rs.flush_soft();
+                refill(rs.in_call, rs.origin + (uint32_t)(int)rs.pos, 4);
+                if (rs.in_call) {
                     symbol_body(std::false_type{}, 0u);
                     symbol_body(std::false_type{}, 1u);
                     symbol_body(std::false_type{}, 2u);
@@ -429,49 +291,18 @@ __device__ __forceinline__ void msk_frontend_x4_body(OpvStream* __restrict__ str
 
         if ((iter & 3u) == 0u) {
             __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0): blocks and stores issued 4 symbols ago
-            flush_soft();
-            refill(in_call, origin + (uint32_t)(int)pos, 4);
+            rs.flush_soft();
+            refill(rs.in_call, rs.origin + (uint32_t)(int)rs.pos, 4);
         }
 
-        if (in_call) {
-            if (pos + 40.0 + 10.0 < Nd) {                          // ref :221
-                symbol_body(std::true_type{}, iter & 3u);
-            } else {
-                // ---- end of this demodulate() call (ref :318-328, :1067-1076) ---------------------
-                const uint32_t nsym_call = ((soft_off - soft_off0) & soft_bmask) >> 3;
-                const uint32_t used = (uint32_t)pos;
-                mu = pos - (double)used;
-                const uint32_t leftover = N - used;
-                if (t == 0) {
-                    double* c = chunk_log + 5 * (size_t)(n_chunks % cap_chunks);
-                    c[0] = fo; c[1] = tf; c[2] = mu; c[3] = (double)leftover; c[4] = (double)nsym_call;
-                }
-                ++n_chunks;
-                n_soft += nsym_call;
-                total_samples += N;
-                origin += (leftover > 0u && leftover < N) ? used : N;
-                in_call = false;
-                if (last) { tail_done = 1; done = true; }
-            }
+        if (rs.in_call) {
+            if (rs.has_symbol()) symbol_body(std::true_type{}, iter & 3u);
+            else rs.end_call(t == 0);
         }
     }
 
-    flush_soft();
-    if (have && t == 0) {
-        st.freq_offset = fo; st.timing_freq = tf; st.mu = mu;
-        st.p1r = pv.a; st.p1i = pv.b; st.p2r = pv.c; st.p2i = pv.d; st.x40c = pv.x40c; st.x40s = pv.x40s;
-        st.fo_sum = fo_sum;
-        st.origin = origin; st.n_soft = n_soft; st.total_samples = total_samples;
-        st.n_chunks = n_chunks; st.tail_done = tail_done; st.overflow = overflow;
-        st.stalled = stalled; st.edge_ties = edge_ties;
-        // where and at which clock the wave that carried this stream (and three others) ran (opv_tap_wave_info)
-        unsigned hw, xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        st.dbg_hw_id = hw; st.dbg_xcc_id = xcc;
-        st.dbg_cycles = __builtin_amdgcn_s_memtime() - dbg_t0;
-        st.dbg_ticks = __builtin_amdgcn_s_memrealtime() - dbg_r0;
-    }
+    rs.flush_soft();
+    if (have && t == 0) rs.store(st, dbg_t0, dbg_r0);
 }
 
 // sixteen streams per workgroup: one wave per SIMD of a CU by construction. (A one-wave workgroup shape of this body existed

@@ -140,12 +140,12 @@ def test_bench_starts_its_own_ranks_and_fails_loudly_without_gpus():
 
 
 def test_alignment_pass_changes_encodings_only(amd):
-    """tools/align_vop3.py (the pass between `hipcc -S` and the assembler for the two front-end files): its output is its
+    """tools/align_vop3.py (the pass between `hipcc -S` and the assembler for the three front-end files): its output is its
     input line for line, except that some instructions carry `_e64` where they carried `_e32` or no suffix - nothing
     added, nothing moved, no operand touched - and the shipped library was built from that output."""
     import subprocess
     pkg = ROOT / "opv-cxx-demod_amd"
-    for stem in ("k_frontend", "k_frontend_x4"):
+    for stem in ("k_frontend", "k_frontend_x4", "k_frontend_x16"):
         subprocess.run(["make", "-s", "-C", str(pkg), f"build/{stem}.al.s"], check=True, capture_output=True)
         a = (pkg / "build" / f"{stem}.dev.s").read_text().split("\n")
         b = (pkg / "build" / f"{stem}.al.s").read_text().split("\n")

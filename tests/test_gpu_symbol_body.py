@@ -3,7 +3,8 @@ instruction diet - X[40] handed out from the spare lane of every row, the domina
 advanced once per loop trip with the ring mask at batch boundaries only, the fp64 ring's tap address as one 16-bit multiply-add.
 None of these may move a rounding, so:
 
- 1. the three launch shapes reproduce, bit for bit, what the PARENT build computed on a fixed capture set (sha256 digests recorded by
+ 1. its three launch shapes - and the four of the several-streams-per-wave kernels, which share their scheduler and symbol tail in
+    csrc/k_frontend_rows.h - reproduce, bit for bit, what the PARENT build computed on a fixed capture set (sha256 digests recorded by
     scripts/symbol_body_record.py in tests/golden/symbol_body_parent.json);
  2. the soft ring wraps three times per stream in the middle of demodulate() calls (the smallest ring a context can have, four
     streams whose starts are staggered by 0 .. 3 symbols, fed in odd pieces with frames popped between rounds), held to the oracle
@@ -93,10 +94,17 @@ def parent_set(amd):
     return rec, names, caps, golden
 
 
-@pytest.mark.parametrize("shape", ["fp64", "int16", "wg4"])
+@pytest.mark.parametrize("shape", ["fp64", "int16", "wg4", "x4_wg4", "x16", "x16_wg4", "x16_wg8"])
 def test_equals_the_parent(amd, parent_set, shape):
-    """every digest of the recorded set on this launch shape: soft log, chunk log, final state (edge_ties included), frames"""
+    """every digest of the recorded set on this launch shape: soft log, chunk log, final state (edge_ties included), frames. The
+    shapes of the several-streams-per-wave kernels (csrc/k_frontend_x4.hip, k_frontend_x16.hip, recorded on the parent of the commit
+    that moved their shared statements into csrc/k_frontend_rows.h): x4_wg4 and x16 carry the 14 captures whole in one context
+    (two idle rows / quads), x16_wg4 is 70 streams (two workgroups), x16_wg8 is 16 400 streams attached to the 14 device-resident
+    3-frame cuts. Every stream is held to its capture's digest; of x16_wg8's, the ones that are read back: the first and the last
+    workgroup and every 64th stream (symbol_body_record.X16_WG8_READ - all 16 400 would not fit a few seconds). record_shape asserts
+    frontend_kernel() on every shape."""
     rec, names, caps, golden = parent_set
+    assert tuple(golden["shapes"]) == rec.SHAPES
     got = rec.record_shape(amd, names, caps, shape)
     for name, g, e in zip(names, got, golden["shapes"][shape]):
         assert g == e, f"{shape} {name}: {[k for k in e if g[k] != e[k]]} differ from the parent build"

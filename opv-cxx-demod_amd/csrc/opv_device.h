@@ -134,7 +134,7 @@ struct OpvTieStage {
     OpvTieSlot slot[1];       // [slots]
 };
 
-// ---- stream migration (k_stream_pack.hip; opv_capi.hip: opv_export_streams / opv_import_streams) ----
+// ---- stream migration (k_stream_pack.hip; opv_migrate.hip: opv_export_streams / opv_import_streams) ----
 // Both kernels run off tables in PINNED host memory that the host has checked entry by entry. A move is one contiguous run of at
 // most OPV_MOVE_PIECE bytes: the host un-wraps every ring segment into runs and cuts long runs (the IQ tail) into pieces, so that
 // one stream's 347 KB already spread over a dozen workgroups and a drain of thousands of streams is still one launch.

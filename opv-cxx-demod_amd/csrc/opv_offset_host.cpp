@@ -8,7 +8,7 @@
 // (hipLaunchHostFunc; opv_capi.hip: opv_process - the caller does not wait) repeats the decision here, the contenders
 // evaluated by the reference's own loop (phases accumulated sample by sample from zero, one sin and one cos per LO and
 // sample, sums in its order) with the host's sin / cos. Nothing in this file calls HIP. Same idea as the transmit chain's
-// ambiguous samples (opv_capi.hip: opv_tx_modulate_device). Compiled with the host compiler, -ffp-contract=off (Makefile: CXXFLAGS).
+// ambiguous samples (opv_tx_device.hip: opv_tx_modulate_device). Compiled with the host compiler, -ffp-contract=off (Makefile: CXXFLAGS).
 //
 // This is product code: a few candidates of a few streams (the guard fires on <= 4 of 512 ordinary captures), never the
 // whole search and never the receive chain - there is no CPU implementation of the hot path in this library.

@@ -1,5 +1,5 @@
 // opv_tx_internal.h — pieces of the host transmit chain (opv_tx.cpp) reused by the device
-// modulator in opv_capi.hip / k_tx_modulate.hip. Not part of the public ABI.
+// modulator in opv_tx_device.hip / k_tx_modulate.hip. Not part of the public ABI.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

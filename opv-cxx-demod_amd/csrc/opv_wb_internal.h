@@ -1,4 +1,4 @@
-// opv_wb_internal.h — the door between the context (opv_capi.hip) and the wideband front door (opv_wideband.hip, k_wideband.hip).
+// opv_wb_internal.h — the door between the context (opv_ctx.h, opv_push.hip) and the wideband front door (opv_wideband.hip, k_wideband.hip).
 // The wideband object never sees opv_ctx's fields: it asks the context to reserve room in its streams' device buffers under
 // the rules of push_enqueue, launches its own kernel on the copy stream, and tells the context when it has.
 #ifndef OPV_WB_INTERNAL_H
@@ -37,7 +37,7 @@ constexpr uint32_t OPV_WB_THREADS = 256;
 
 extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
 
-// ---- what the context offers (defined at the end of opv_capi.hip)
+// ---- what the context offers (defined at the end of opv_push.hip; opv_int_fail in opv_capi.hip)
 int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code
 // What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
 // (or used) after its context finds ctx_alive false and touches nothing of the context.

@@ -30,7 +30,7 @@ ANCHORS = [
     ("csrc/k_frame_decode.hip", r"uint32_t deint_addr\(", "`csrc/k_frame_decode.hip:{n}` `deint_addr`"),
     ("csrc/k_frame_decode.hip", r"void k_frame_decode\(", "`k_frame_decode` `:{n}`"),
     ("csrc/k_frame_decode.hip", r"LfsrTable kLfsr = ", "`kLfsr` `:{n}`"),
-    ("csrc/opv_capi.hip", r"^extern \"C\" int opv_gather_frames\(", "`opv_gather_frames` `csrc/opv_capi.hip:{n}`"),
+    ("csrc/opv_rccl.hip", r"^extern \"C\" int opv_gather_frames\(", "`opv_gather_frames` `csrc/opv_rccl.hip:{n}`"),
     ("csrc/opv_capi.hip", r"^extern \"C\" int opv_process\(", "(`csrc/opv_capi.hip:{n}`)"),
     ("csrc/opv_capi.hip", r"^static void tie_host_fn\(", "(`tie_host_fn` `:{n}`"),
     ("csrc/k_tx_modulate.hip", r"void k_tx_encode\(", "`csrc/k_tx_modulate.hip:{n}-"),

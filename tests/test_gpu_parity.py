@@ -867,6 +867,84 @@ def test_long_stream_through_a_small_device_buffer(amd, oracle, iq100):
     d.close()
 
 
+def compaction_plan(chunks, total, sizes, cap):
+    """What the pushes of one stream make of its device buffer, on the CPU: the oracle's chunk log gives the chunk origins (a
+    call of 86720 samples that leaves 0 < leftover < 86720 behind advances by what it used), a round takes every whole chunk
+    that has arrived, and a push that does not fit drops what lies in front of iq_keep(origin) = (origin - 16) & ~3 (csrc/opv_stream_rules.h).
+    Returns per push (first, n, origin after its round, retained tail if the push compacted else None, iq_base after the push)."""
+    origins = [0]
+    for c in chunks:
+        left = int(c[3])
+        origins.append(origins[-1] + (86720 - left if 0 < left < 86720 else 86720))
+    plan, pushed, base, origin, k, j = [], 0, 0, 0, 0, 0
+    while pushed < total:
+        n = min(sizes[j % len(sizes)], total - pushed)
+        tail = None
+        if pushed - base + n > cap:
+            keep = ((origin - base - 16) & ~3) if origin - base >= 16 else 0
+            base += keep
+            tail = pushed - base
+            assert keep and tail + n <= cap
+        while k + 1 < len(origins) and origins[k] + 86720 <= pushed + n:
+            k += 1
+        origin = origins[k]
+        plan.append((pushed, n, origin, tail, base))
+        pushed += n
+        j += 1
+    return plan
+
+
+def test_single_stream_compaction_at_every_tail_length(amd, oracle, iq100):
+    """The compaction of ONE stream goes through the table-driven kernel too (a list of one: csrc/opv_push.hip, compact_streams).
+    A capture through a 3-chunk buffer in pushes of 4097, 1, 86723 and 40001 samples with a round after each: the retained tail
+    takes every length mod 4 (whole 16-byte moves + 0..3 samples) and once is shorter than 1024 samples (one slice), all of
+    which is checked on the CPU first. It takes the 100-frame capture for that (267 pushes, 42 of them compacting, the
+    shortest tail 72 samples): the 10-frame one compacts three times, with tails of 5718, 7322 and 4828 samples. Around every compacting push the last 64 samples read the same, the samples in front of
+    the keep point are gone, and at the end frames, metrics, release symbols, events and every soft symbol are the oracle's.
+    Stream 1 holds half a chunk and is never full: compaction leaves it alone."""
+    x = iq100
+    total = x.size // 2
+    exp = oracle.receive(x, streaming=True)
+    cap = 3 * 86720 + 8192
+    plan = compaction_plan(exp["chunks"], total, (4097, 1, 86723, 40001), cap)
+    tails = [t for _, _, _, t, _ in plan if t is not None]
+    assert {t & 3 for t in tails} == {0, 1, 2, 3} and any(t < 1024 for t in tails) and any(t >= 1024 for t in tails), tails
+    d = amd.Demod(2, max_samples=cap, streaming=True)
+    other = np.ascontiguousarray(x[: 2 * 43360])
+    d.push(1, other)
+    frames, metas, events, softs, seen = [], [], [], [], 0
+    for first, n, origin, tail, base in plan:
+        before = d.iq(0, first=first - 64, cap=64) if tail is not None else None
+        d.push(0, x[2 * first: 2 * (first + n)])
+        if tail is not None:
+            assert np.array_equal(before, x[2 * (first - 64): 2 * first]) and np.array_equal(d.iq(0, first=first - 64, cap=64), before), first
+            assert d.iq(0, first=base - 1, cap=1).size == 0 and np.array_equal(d.iq(0, first=base, cap=1), x[2 * base: 2 * base + 2]), first
+        d.process()
+        assert d.state(0).chunk_origin == origin, (first, n)
+        f, m = d.pop_frames(0)
+        frames.append(f)
+        metas.append(m)
+        events.append(d.pop_events(0))
+        softs.append(d.soft(0, first=seen))
+        seen += len(softs[-1])
+    d.flush(0)
+    d.process()
+    f, m = d.pop_frames(0)
+    frames, metas, events = np.concatenate(frames + [f]), np.concatenate(metas + [m]), np.concatenate(events + [d.pop_events(0)])
+    soft = np.concatenate(softs + [d.soft(0, first=seen)])
+    assert len(frames) == len(exp["frames"]) == 100 and np.array_equal(frames, exp["frames"])
+    assert np.array_equal(metas["viterbi_metric"], exp["metrics"])
+    assert np.array_equal(metas["release_symbol"], exp["frame_sym"])
+    events_match(amd, events, exp["events"])
+    st = d.state(0)
+    assert st.total_symbols == exp["n_soft"] == len(soft) and st.n_chunks == len(exp["chunks"])
+    assert abs(st.freq_offset_hz - exp["final_freq_offset"]) < 1e-6
+    a, _ = soft_err(soft, exp["soft"])
+    assert a < SOFT_TIGHT
+    assert d.state(1).chunk_origin == 0 and np.array_equal(d.iq(1, first=0), other)
+    d.close()
+
+
 def test_device_modulator_is_bit_identical_to_host_and_reference(amd, golden):
     """the TX chain writing straight into HBM. Same bytes as the host
     modulator, hence (sha256 pins) as the reference `opv-mod`."""
@@ -958,8 +1036,8 @@ def test_device_transmit_chain_past_the_flat_top_flip(amd):
 
 
 def test_device_transmit_chain_with_a_distrusted_libm():
-    """The flat-top zones are a statement about the process's libm; the library probes it once (libm_flat_tops_as_assumed,
-    opv_capi.hip) and, if it answers differently, takes every symbol's flat-top bits from libm itself. That path, forced
+    """The flat-top zones are a statement about the process's libm; the library probes it once (opv_tx_libm_flat_tops_as_assumed,
+    opv_tx_device.hip) and, if it answers differently, takes every symbol's flat-top bits from libm itself. That path, forced
     through OPV_TX_DISTRUST_LIBM in a child process (the probe's result is per process): runs shorter and longer than the
     1563-frame flip still equal the host modulator sample for sample."""
     import subprocess
@@ -1957,7 +2035,7 @@ def test_push_batch_and_pooled_pops(amd, oracle, iq10):
 
 @pytest.mark.parametrize("mode", ["gather", "copies", "async"])
 def test_push_batch_from_pinned_memory_and_batched_compaction(amd, oracle, iq10, iq100, mode, monkeypatch):
-    """The serving path's bulk moves (csrc/opv_capi.hip: k_push_gather, k_compact). Blocks that lie in PINNED host memory cross
+    """The serving path's bulk moves (csrc/opv_push.hip: k_push_gather, k_compact). Blocks that lie in PINNED host memory cross
     PCIe through one gather kernel per opv_push_iq_batch (read through their device-visible addresses) instead of one copy per
     stream, and staging buffers that fill in the same round are compacted by one launch. 14 streams with a staging buffer of
     about three chunks (so every stream compacts every few rounds, most of them together), blocks of ragged sizes: 16-byte

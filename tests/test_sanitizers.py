@@ -293,3 +293,22 @@ int main() {
     assert outs[0] == outs[1], outs
     e0, e1, em, est, ties, probe, same = outs[0]
     assert e0 == e1 and float.fromhex(e0) > float.fromhex(em) and est == "-1530.0" and int(ties) >= 2 and probe == "1" and same == "1"
+
+
+def test_stream_rules_under_sanitizers(tmp_path):
+    """csrc/opv_stream_rules.{h,cpp} - the host code that reads a caller's bytes (parse_blob: an imported stream blob) and all the
+    index arithmetic of rings, segment tables and launch shapes - as a stand-alone program (tests/stream_rules_probe.cpp, its own
+    main) under ASan + UBSan: a valid blob, every prefix of it in an allocation of exactly that length, every header and index
+    byte poked, rings around the wrap, the segment moves of an export and of imports into smaller rings. The sanitized build
+    reports nothing and prints the line of the unsanitized build of the same files."""
+    pkg = PKG / "csrc"
+    outs = []
+    for extra, exe in ((["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], tmp_path / "san"), ([], tmp_path / "plain")):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-DPROBE_MAIN", "-I", str(pkg)] + extra +
+                       ["-o", str(exe), str(ROOT / "tests" / "stream_rules_probe.cpp"), str(pkg / "opv_stream_rules.cpp")], check=True)
+        p = run([str(exe)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs.append(p.stdout.decode().split())
+    assert outs[0] == outs[1] and len(outs[0]) == 3, outs
+    accepted, refused = int(outs[0][0]), int(outs[0][1])
+    assert accepted >= 2 and refused > 1000, outs                             # (the good blob and pokes of unread fields pass; the rest is refused)

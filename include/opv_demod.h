@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
+                               still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
                                still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
                                still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
                                7: opv_process never waits on the host again - the host-libm decision of offset-search near-ties runs as a host
@@ -318,6 +319,51 @@ int opv_get_state(opv_ctx* ctx, int stream, opv_stream_state* out);
 int opv_device_frames(opv_ctx* ctx, const uint8_t** d_frames, const int32_t** d_metrics,
                       const int32_t** d_counts, size_t* frame_capacity);
 void* opv_hip_stream(opv_ctx* ctx);
+
+/* ---- per-frame link report: corrected channel bits and soft-symbol moments (opt-in, OFF by default) -------------------
+ * Replaces nothing in the reference, which prints the Viterbi metric and the sync quality of a frame and discards the rest. When
+ * the decoder returns, the frame's 2144 soft symbols are still in the soft log and the decoded bytes say what they should have
+ * been: re-encoding the frame and holding it against what was received gives the channel bits the decoder corrected (a raw BER
+ * in front of the decoder, with no knowledge of the transmitted data) and a decision-directed amplitude and noise power.
+ * Definitions, in on-air order i = 0 .. 2143 over the frame's payload soft[payload_symbol + i]:
+ *   q_i    the 3-bit value the decoder used for symbol i (src/opv-demod.cpp:862-866; 0 = confident bit 0 .. 7 = confident bit 1);
+ *   enc_i  bit i of the transmit chain (randomise, K=7 r=1/2 encode, interleave: opv_tap_tx_frame's interleaved2144) applied to
+ *          the 134 decoded bytes - on the receive side the trellis of :815-822 from state 0, read through deinterleave_addr;
+ *   bit_errors = #{ i : (q_i >= 4) != enc_i },  weak = #{ i : q_i == 3 or q_i == 4 },  nonfinite = #{ i : soft_i is NaN or +-Inf };
+ *   m1 = the decoder's scale (the sequential sum of |soft_i| of :856-858, / 2144),  m2 = sum soft_i^2 / 2144,
+ *   ma = sum soft_i e_i / 2144 with e_i = +1 where enc_i == 0 and -1 where enc_i == 1.
+ * The four integers are exact. m2 and ma are fp64 sums in a fixed order: the same bits from run to run and from the in-context and
+ * the stand-alone form, within 2146 x 2^-53 x (m2, resp. m1) of the exact sums. A frame with nonfinite > 0 leaves m1 / m2 / ma
+ * unspecified. A frame the decoder drops (metric -1, :859) has valid = 0, and so has every frame the report did not see (below);
+ * every other field of such a record is 0.
+ * opv_enable_link_report: the first enable allocates a device ring [n_streams][frame_capacity] of opv_link, zero-filled, indexed
+ * like the frame ring (frame f at slot f % frame_capacity); while the report is on, opv_process computes the record of every frame
+ * it decodes, with one more launch behind the decoder (opv_kernel_times[3] still brackets the decoder alone). Every later
+ * off -> on transition zero-fills the ring again, in stream order: frames decoded while the report was off read valid = 0, never a
+ * stale record. An enabling call waits for that zero-fill (it implies opv_sync): a pop may follow it with no round in between.
+ * A context that never enables the report allocates and launches nothing for it.
+ * opv_pop_frames_link: opv_pop_frames plus the records of the same frames in the same order (dropped frames skipped alike);
+ * OPV_ESTATE while the report is off, OPV_EINVAL for a null `link`.
+ * opv_device_link: the ring's device view for zero-copy / gather consumers, beside opv_device_frames; OPV_ESTATE if the report was
+ * never enabled.
+ * opv_link_payloads: the stand-alone form, like opv_decode_payloads and independent of opv_enable_link_report: n_frames payloads
+ * of 2144 host doubles each, one record per payload (valid = 0 for payloads the decoder drops). n_frames == 0 is OPV_EINVAL.
+ * Reset and migration: opv_reset_stream clears the records of the streams it resets. LINK RECORDS DO NOT MIGRATE:
+ * opv_import_streams clears the records of its destination slots like a reset - unpopped frames that arrive by import read
+ * valid = 0, frames decoded after the import are reported normally (the blob and the carry of a stream know nothing of the report). */
+typedef struct opv_link {
+    int32_t valid;       /* 1: computed for this frame; 0: not (see above) - every other field is then 0 */
+    int32_t bit_errors;  /* 0..2144 channel bits the decoder corrected */
+    int32_t weak;        /* received values with q == 3 or q == 4 */
+    int32_t nonfinite;   /* payload values that are NaN or +-Inf */
+    double  m1;          /* the decoder's scale: mean |soft|, the SEQUENTIAL sum of ref :856-858 */
+    double  m2;          /* mean soft^2 */
+    double  ma;          /* mean soft_i * e_i, e_i = +1 where the re-encoded bit is 0, -1 where it is 1 */
+} opv_link;              /* 40 bytes */
+int opv_enable_link_report(opv_ctx* ctx, int enable);
+long opv_pop_frames_link(opv_ctx* ctx, int stream, uint8_t* out134, size_t cap_frames, opv_frame_meta* meta, opv_link* link);
+int opv_device_link(opv_ctx* ctx, const opv_link** d_link);
+int opv_link_payloads(opv_ctx* ctx, const double* soft, size_t n_frames, opv_link* out);
 
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference, whose streams are separate processes) -----------
  * Streams shard contiguously over GPUs - one context per GPU, no data-path collective - and the decoded frames return to one

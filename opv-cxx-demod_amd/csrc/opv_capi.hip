@@ -1,5 +1,5 @@
 // opv_capi.hip — the thin C-ABI HIP shim behind include/opv_demod.h: a context's life, opv_process, pops, state and taps.
-// (opv_push.hip: the serving path; opv_migrate.hip; opv_tx_device.hip; opv_rccl.hip; opv_ctx.h: what they share.)
+// (opv_push.hip: the serving path; opv_migrate.hip; opv_link.hip: the link report; opv_tx_device.hip; opv_rccl.hip; opv_ctx.h: what they share.)
 //
 // Owns device memory and the per-stream device contexts and launches the four hot-path kernels on one HIP stream. There is
 // NO CPU implementation of the hot path in this library: without a usable HIP device opv_create fails with OPV_ENODEV.
@@ -226,7 +226,7 @@ extern "C" void opv_destroy(opv_ctx* c) {
     for (auto& h : c->hs) { (void)hipFree(h.d_iq_owned); (void)hipFree(h.d_iq_alt); }   // (a null pointer is a no-op)
     for (auto& e : c->ev)
         if (e) (void)hipEventDestroy(e);
-    void* ptrs[] = {c->d_streams, c->d_in, c->d_soft, c->d_frec, c->d_events, c->d_chunks, c->d_frames, c->d_metrics, c->d_fscale, c->d_counts, c->d_offs_wtab, c->d_tx_cnt, c->d_tx_list, c->d_tie_list};
+    void* ptrs[] = {c->d_streams, c->d_in, c->d_soft, c->d_frec, c->d_events, c->d_chunks, c->d_frames, c->d_metrics, c->d_fscale, c->d_counts, c->d_link, c->d_offs_wtab, c->d_tx_cnt, c->d_tx_list, c->d_tie_list};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -374,6 +374,7 @@ extern "C" int opv_process(opv_ctx* c) {
     else k_frame_scale<<<(unsigned)((fr * (uint64_t)S + 63) / 64), 64, 0, c->stream>>>(c->d_streams, (uint32_t)fr, (uint32_t)S);
     k_frame_decode<<<(unsigned)(((fr + 1) / 2) * (uint64_t)S), 64, 0, c->stream>>>(c->d_streams, (uint32_t)((fr + 1) / 2));   // two frames per wave
     if (tm) { HIPCHK(hipEventRecord(c->ev[7], c->stream)); c->timing_valid = true; }
+    link_launch(c, fr);            // the opt-in fifth stage (opv_link.hip): behind the decoder's bracket, nothing while it is off
     k_collect_counts<<<(S + 63) / 64, 64, 0, c->stream>>>(c->d_streams, c->d_counts, S, c->h_stall + slot);
     HIPCHK(hipEventRecord(c->done_ev, c->stream));
     HIPCHK(hipGetLastError());
@@ -406,6 +407,7 @@ extern "C" int opv_reset_stream(opv_ctx* c, int s) {
     HIPCHK(hipMemcpyAsync(c->d_streams + lo, &c->initial[lo], sizeof(OpvStream) * (hi - lo), hipMemcpyHostToDevice, c->stream));
     k_fill_i32<<<256, 256, 0, c->stream>>>(c->d_metrics + (size_t)c->cap_frames * lo, INT32_MIN,
                                           (size_t)c->cap_frames * (hi - lo));
+    if (int r = link_clear(c, lo, hi)) return r;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->mirror_valid = false;
     return OPV_OK;

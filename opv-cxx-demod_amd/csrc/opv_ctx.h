@@ -1,5 +1,5 @@
 // opv_ctx.h — the context behind include/opv_demod.h as the files of the C-ABI shim see it (opv_capi.hip: life, opv_process, pops,
-// taps; opv_push.hip: the serving path; opv_migrate.hip; opv_tx_device.hip; opv_rccl.hip). Internal: the wideband object does
+// taps; opv_push.hip: the serving path; opv_migrate.hip; opv_link.hip; opv_tx_device.hip; opv_rccl.hip). Internal: the wideband object does
 // not see it (opv_wb_internal.h is its door).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,6 +29,8 @@ extern "C" __global__ void k_frame_scale_wave(OpvStream*, uint32_t);
 extern "C" __global__ void k_frame_decode(OpvStream*, uint32_t);
 extern "C" __global__ void k_payload_scale(const double*, uint32_t, double*);
 extern "C" __global__ void k_decode_payloads(const double*, uint32_t, const double*, uint8_t*, int32_t*, int8_t*, int8_t*, uint8_t*);
+extern "C" __global__ void k_frame_link(OpvStream*, opv_link*, uint32_t, uint32_t);
+extern "C" __global__ void k_link_payloads(const double*, uint32_t, const double*, const uint8_t*, const int32_t*, opv_link*);
 extern "C" __global__ void k_stream_pack(const OpvMove*, uint32_t);
 extern "C" __global__ void k_stream_unpack(OpvStream*, int32_t*, const OpvUnpackItem*, uint32_t, const OpvMove*, uint32_t);
 extern "C" __global__ void k_channel(const int4*, int4*, uint64_t, double, double, double, uint64_t);
@@ -140,6 +142,10 @@ struct opv_ctx {
     int32_t* d_metrics = nullptr;
     double* d_fscale = nullptr;
     int32_t* d_counts = nullptr;
+    // the per-frame link report (opv_link.hip): [n_streams][cap_frames] records, allocated by the first opv_enable_link_report;
+    // reaches k_frame_link as a kernel argument - a stream's carry (OpvStream) does not know it, so it does not migrate
+    opv_link* d_link = nullptr;
+    bool link_on = false;
     double* d_offs_wtab = nullptr;      // k_offset_search's moment weights: [40 taps][cos, sin][OPV_OFFS_TERMS]
     // offset-search ties are decided with the HOST's libm (opv_offset_host.cpp), in stream order: streams whose search could not
     // decide put themselves on d_tie_list ([0] = count, then indices); behind the search opv_process enqueues, per pass of
@@ -203,6 +209,8 @@ struct opv_ctx {
     std::vector<OpvFrameRec> m_frec;
     std::vector<OpvEventRec> m_events;
     unsigned mirror_epoch = 0, pools_epoch = ~0u;
+    std::vector<opv_link> m_link;       // the link report's ring, fetched by opv_pop_frames_link (opv_link.hip) once per mirror_epoch
+    unsigned link_epoch = ~0u;
 
     int refresh() {
         if (mirror_valid) return OPV_OK;
@@ -266,6 +274,10 @@ inline int settle_pushes(opv_ctx* c) {
     return OPV_OK;
 }
 
+// opv_link.hip: the link report's launch behind the decoder (nothing while the report is off), and its records of streams
+// [lo, hi) zeroed in stream order (nothing while the ring does not exist) - what opv_reset_stream and opv_import_streams do to a slot
+void link_launch(opv_ctx* c, uint64_t fr);
+int link_clear(opv_ctx* c, int lo, int hi);
 bool opv_tx_libm_flat_tops_as_assumed();   // opv_tx_device.hip: the probe behind opv_ctx::tx_trust_libm
 // a stream's staging buffer (which = 0) or its second one (1: compaction's target), allocated at first use: max_samples samples +
 // slack for whole-tile reads (opv_push.hip). `oom`: the refusal is OPV_ENOMEM with that text instead of OPV_EHIP.

@@ -253,6 +253,8 @@ extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const v
     }
     c->mirror_valid = false;
     c->maybe_stalled = true;
+    for (int i = 0; i < count; ++i)                        // link records do not travel: the slot's read valid = 0, as after a reset
+        if (int r = link_clear(c, dst[i], dst[i] + 1)) return r;
     HIPCHK(hipStreamSynchronize(c->stream));               // the blob is the caller's again
     return OPV_OK;
 }

@@ -39,6 +39,7 @@ EXPORTS = [
     "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
     "opv_tap_push_soft",
+    "opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads",
 ]
 
 
@@ -75,6 +76,22 @@ EVENT_DTYPE = np.dtype(
     [("kind", "<i4"), ("count", "<i4"), ("sym_idx", "<u8"), ("corr", "<f8"), ("raw", "<f8")], align=True)
 META_DTYPE = np.dtype([("viterbi_metric", "<i4"), ("sync_ok", "<i4"), ("sync_quality", "<f8"),
                        ("release_symbol", "<u8"), ("payload_symbol", "<u8")], align=True)
+LINK_DTYPE = np.dtype([("valid", "<i4"), ("bit_errors", "<i4"), ("weak", "<i4"), ("nonfinite", "<i4"),
+                       ("m1", "<f8"), ("m2", "<f8"), ("ma", "<f8")], align=True)          # opv_link, 40 bytes
+
+
+def link_esn0_db(rec):
+    """SNR in dB of the demodulator's SOFT OUTPUT from link records (LINK_DTYPE, one or an array): decision-directed amplitude
+    ma and noise power m2 - ma^2, 10 log10(ma^2 / (2 (m2 - ma^2))). +inf where m2 <= ma^2 (no noise left after rounding), nan
+    where valid == 0 or nonfinite > 0. It describes the soft symbols the decoder saw under that formula; it is NOT a
+    calibrated channel Es/N0 (the front-end's soft symbols are not a matched filter's output)."""
+    rec = np.asarray(rec)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        ma2 = rec["ma"].astype(np.float64) ** 2
+        noise = rec["m2"] - ma2
+        db = 10.0 * np.log10(ma2 / (2.0 * noise))
+    db = np.where(rec["m2"] <= ma2, np.inf, db)
+    return np.where((rec["valid"] == 0) | (rec["nonfinite"] > 0), np.nan, db)
 
 
 def build(force=False):
@@ -198,6 +215,11 @@ def lib():
         L.opv_wb_flush.argtypes = [C.c_void_p]
         L.opv_tap_iq.restype = C.c_long
         L.opv_tap_iq.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
+        L.opv_enable_link_report.argtypes = [C.c_void_p, C.c_int]
+        L.opv_pop_frames_link.restype = C.c_long
+        L.opv_pop_frames_link.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.opv_device_link.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.opv_link_payloads.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -509,12 +531,34 @@ class Demod:
         _chk(lib().opv_kernel_times(self.h, t))
         return dict(offset_search=t[0], msk_frontend=t[1], sync_track=t[2], frame_decode=t[3])
 
-    def pop_frames(self, stream, cap=None):
+    def pop_frames(self, stream, cap=None, link=False):
+        """(frames, meta); with link=True (opv_pop_frames_link; enable_link_report first) (frames, meta, link records)"""
         cap = cap or (int(self.cfg.max_samples) // (FRAME_SYMBOLS * 38) + 8)
         out = np.zeros((cap, FRAME_BYTES), np.uint8)
         meta = np.zeros(cap, META_DTYPE)
+        if link:
+            rec = np.zeros(cap, LINK_DTYPE)
+            n = _chk(lib().opv_pop_frames_link(self.h, stream, out.ctypes.data, cap, meta.ctypes.data, rec.ctypes.data))
+            return out[:n].copy(), meta[:n].copy(), rec[:n].copy()
         n = _chk(lib().opv_pop_frames(self.h, stream, out.ctypes.data, cap, meta.ctypes.data))
         return out[:n].copy(), meta[:n].copy()
+
+    def enable_link_report(self, on=True):
+        """opv_enable_link_report: per-frame link records (LINK_DTYPE) for every frame decoded from now on; off by default"""
+        _chk(lib().opv_enable_link_report(self.h, int(on)))
+
+    def device_link(self):
+        """opv_device_link: device address of the [n_streams][frame_capacity] ring of opv_link records"""
+        p = C.c_void_p()
+        _chk(lib().opv_device_link(self.h, C.byref(p)))
+        return p.value
+
+    def link_payloads(self, soft):
+        """opv_link_payloads: one link record per payload of 2144 soft symbols (stand-alone, like decode_payloads)"""
+        soft = np.ascontiguousarray(soft, np.float64).reshape(-1, ENCODED_BITS)
+        rec = np.zeros(len(soft), LINK_DTYPE)
+        _chk(lib().opv_link_payloads(self.h, soft.ctypes.data, len(soft), rec.ctypes.data))
+        return rec
 
     def pop_events(self, stream, cap=None):
         cap = cap or (4 * (int(self.cfg.max_samples) // (FRAME_SYMBOLS * 38) + 8) + 64)

@@ -3,7 +3,7 @@
 // trellis state of each (packed 16-bit path metrics).
 //
 // Replaces FrameDecoder::decode (reference src/opv-demod.cpp:854-898), deinterleave_addr
-// (:792-795) and ViterbiDecoder::decode (:800-847).
+// (:792-795: opv_interleave_addr, opv_frame_code.h) and ViterbiDecoder::decode (:800-847).
 //
 // Bit-exactness. Everything after the quantiser is integer. The quantiser itself
 // (:856-866) is reproduced operation for operation: the scale is the SEQUENTIAL fp64 sum of
@@ -13,7 +13,7 @@
 // additions in the same order), and the decoder reads the scale. The quantised value itself - one IEEE divide, one
 // multiply, two adds and a truncation per symbol in the reference, FMA contraction disabled - is decided by ONE multiply-add
 // wherever that provably gives the same integer, and by the reference's own sequence inside a guard band around the
-// quantiser's boundaries (decode_two). Given the same 2144 doubles this kernel returns the same bytes, decisions and
+// quantiser's boundaries (opv_quantise3, opv_frame_code.h). Given the same 2144 doubles this kernel returns the same bytes, decisions and
 // metric as the reference, always.
 //
 // Viterbi on a wave, TWO frames per wave (round 4): the 64 path metrics of a frame live one per lane under a ROTATING
@@ -42,32 +42,13 @@
 #include <type_traits>
 
 #include "opv_device.h"
+#include "opv_frame_code.h"
 
 namespace {
 
-struct LfsrTable { uint8_t b[OPV_FB]; };
-constexpr LfsrTable make_lfsr() {  // ref :887-893
-    LfsrTable t{};
-    uint8_t st = 0xFF;
-    for (int i = 0; i < OPV_FB; ++i) {
-        uint8_t o = 0;
-        for (int b = 7; b >= 0; --b) {
-            o = (uint8_t)(o | (((st >> 7) & 1u) << b));
-            const uint8_t fb = (uint8_t)(((st >> 7) ^ (st >> 6) ^ (st >> 4) ^ (st >> 2)) & 1u);
-            st = (uint8_t)((st << 1) | fb);
-        }
-        t.b[i] = o;
-    }
-    return t;
-}
-__constant__ LfsrTable kLfsr = make_lfsr();
+__constant__ OpvLfsrTable kLfsr = opv_make_lfsr();
 
 __device__ inline uint32_t uni32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
-__device__ inline uint32_t deint_addr(uint32_t i) {  // ref :792-795
-    const uint32_t p = (i & 31u) * 67u + (i >> 5);
-    return (p & ~7u) + (7u - (p & 7u));
-}
 
 struct DecodeTaps {
     int8_t* q;      // [n][2144] or null
@@ -145,46 +126,22 @@ __device__ __forceinline__ void decode_two(const FrameIo& A, const FrameIo& B, u
     }
     if (!liveA && !liveB) return;
     // ---- quantise (ref :862-866: q=0 confident bit 0 ... q=7 confident bit 1) straight into the deinterleaved
-    // position (ref :869-871): value i of the decoder's input is symbol deint_addr(i) of the payload; a lane does the
-    // pairs (2 t, 2 t + 1) of trellis steps t = lane, lane + 64, ... of one frame after the other.
-    // The reference's expression per value (:864-865) is int((-soft / scale) * 3.5 + 3.5 + 0.5), four rounded operations of which
-    // the IEEE division alone costs a wave ~30 fp64 instructions. Its result is decided by ONE multiply-add,
-    // x = fma(soft, -3.5 / scale, 4.0), whenever x is not within 1e-6 of an integer: both expressions are within ~1e-14 of
-    // the exact value 4 - 3.5 soft / scale for |x| < 9 (|soft / scale| <= 2144 while the scale is finite: nothing overflows), hence
-    // they truncate alike unless the exact value is within 1e-14 of an integer - and then x is within the guard band and the
-    // reference's own sequence is evaluated (about one value in 10^5 on noise; every value of a few-level input). Outside
-    // (-1, 9) both clamp to the same end. An infinite scale (an Inf in the payload, a sum that overflows) gives x = 4.0, in the band,
-    // or NaN; NaN converts to 0 on both paths like the reference's cvttsd2si + clamp (tests/test_gpu_soft_log.py holds all of it).
-    // All of a frame's loads of a lane (34 gathered doubles, from L2 / HBM) are requested before the first is used: a wave
-    // that waited for them one trellis step at a time spent 30 000 cycles here (17 round trips), more than in the trellis.
+    // position (ref :869-871): value i of the decoder's input is symbol opv_interleave_addr(i) of the payload; a lane does the
+    // pairs (2 t, 2 t + 1) of trellis steps t = lane, lane + 64, ... of one frame after the other, behind one gather of its 34
+    // doubles. Gather and quantiser are the link report's too (opv_frame_code.h, with the reason why one multiply-add decides).
     auto quantise_frame = [&](const FrameIo& F, int byte_of_pair) {
-        constexpr int kIter = (OPV_FBITS + 63) / 64;              // 17 steps per lane (the last one for lanes < 48 only)
-        double sv[2 * kIter];
-#pragma unroll
-        for (int k = 0; k < kIter; ++k) {
-            const int t = lane + 64 * k;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t a = deint_addr(2u * (uint32_t)(t < OPV_FBITS ? t : 0) + (uint32_t)h);
-                sv[2 * k + h] = F.soft[(F.first + a) & F.mask];
-            }
-        }
+        double sv[2 * kLaneSteps];
+        opv_gather_payload(F.soft, F.first, F.mask, lane, sv);
         const double inv = -3.5 / F.scale;
 #pragma unroll
-        for (int k = 0; k < kIter; ++k) {
+        for (int k = 0; k < kLaneSteps; ++k) {
             const int t = lane + 64 * k;
             if (t < OPV_FBITS) {
                 unsigned pair = 0;
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    const uint32_t i = 2u * (uint32_t)t + (uint32_t)h, a = deint_addr(i);
-                    const double x = fma(sv[2 * k + h], inv, 4.0);
-                    int v = (int)x;
-                    if (__builtin_expect(fabs(x - rint(x)) < 1.0e-6 && x > -1.0 && x < 9.0, 0)) {
-                        const double nrm = (-sv[2 * k + h] / F.scale) * 3.5 + 3.5;         // contraction is off for this TU
-                        v = (int)(nrm + 0.5);                                              // C truncation toward zero
-                    }
-                    v = v < 0 ? 0 : (v > 7 ? 7 : v);
+                    const uint32_t i = 2u * (uint32_t)t + (uint32_t)h, a = opv_interleave_addr(i);
+                    const int v = opv_quantise3(sv[2 * k + h], F.scale, inv);
                     pair |= (unsigned)v << (4 * h);
                     if (F.tq) F.tq[a] = (int8_t)v;
                     if (F.td) F.td[i] = (int8_t)v;

@@ -3,11 +3,11 @@
 //
 // No counterpart in the reference, which discards both sides of the comparison when FrameDecoder::decode returns
 // (src/opv-demod.cpp:854-898). What is compared:
-//   received: q_i, the 3-bit value of payload symbol i (:862-866) - the quantiser of k_frame_decode.hip (decode_two) restated
-//             operation for operation, behind the same scale (st.fscale[], never re-summed): the integers are the decoder's;
+//   received: q_i, the 3-bit value of payload symbol i (:862-866) - the decoder's own quantiser (opv_frame_code.h, one
+//             definition for both kernels) behind the same scale (st.fscale[], never re-summed): the integers are the decoder's;
 //   expected: enc_i, bit i of randomise -> K=7 r=1/2 encode -> interleave (src/opv-mod.cpp:158-213) applied to the 134 decoded
 //             bytes: the decoder's own trellis (:815-822: start state 0, G1 0x4F, G2 0x6D) run forwards over the decoded bits,
-//             code bit j of it at payload symbol deinterleave_addr(j) (:792-795).
+//             code bit j of it at payload symbol opv_interleave_addr(j) (:792-795).
 // Trellis step t reads decoded bit t and its six predecessors: bit t is bit (1071 - t) & 7 of byte (1071 - t) >> 3 of the frame
 // XOR the LFSR table (the packer, :878-884, backwards), so the seven bits t .. t - 6 are seven CONSECUTIVE bits of that byte
 // string read as a little-endian number - one 16-bit LDS window and a shift; two zero bytes behind byte 133 are the zeros in
@@ -15,7 +15,7 @@
 // oracle's encoder in a numpy model before the kernel was written (scripts/models/frame_link_model.py).
 //
 // A lane takes steps t = lane, lane + 64, ... (17 trips, the last for lanes < 48) and both code bits of each; its 34 gathered
-// doubles are requested before the first is used, as in decode_two and for its reason (one round trip instead of 17). Three
+// doubles are requested before the first is used - the decoder's gather, opv_gather_payload (one round trip instead of 17). Three
 // counts and two fp64 sums per lane, then an XOR butterfly over the wave in a fixed order: no atomics, so a frame's record is
 // the same bits in every run and in both kernels below. Lane 0 stores the 40 bytes.
 // Bytes: 17 152 B of soft symbols in (from L2 where the decoder has just read them; from HBM in bulk rounds), 134 B of frame in,
@@ -26,32 +26,13 @@
 
 #include "../../include/opv_demod.h"
 #include "opv_device.h"
+#include "opv_frame_code.h"
 
 static_assert(sizeof(opv_link) == 40, "opv_link is 40 bytes");
 
 namespace {
 
-struct LinkLfsr { uint8_t b[OPV_FB]; };
-constexpr LinkLfsr make_link_lfsr() {  // ref :887-893
-    LinkLfsr t{};
-    uint8_t st = 0xFF;
-    for (int i = 0; i < OPV_FB; ++i) {
-        uint8_t o = 0;
-        for (int b = 7; b >= 0; --b) {
-            o = (uint8_t)(o | (((st >> 7) & 1u) << b));
-            const uint8_t fb = (uint8_t)(((st >> 7) ^ (st >> 6) ^ (st >> 4) ^ (st >> 2)) & 1u);
-            st = (uint8_t)((st << 1) | fb);
-        }
-        t.b[i] = o;
-    }
-    return t;
-}
-__constant__ LinkLfsr kLinkLfsr = make_link_lfsr();
-
-__device__ inline uint32_t link_deint_addr(uint32_t i) {  // ref :792-795
-    const uint32_t p = (i & 31u) * 67u + (i >> 5);
-    return (p & ~7u) + (7u - (p & 7u));
-}
+__constant__ OpvLfsrTable kLinkLfsr = opv_make_lfsr();
 
 constexpr int kLinkLds = OPV_FB + 2;                              // the randomised frame + the zeros in front of t = 0
 
@@ -72,23 +53,14 @@ __device__ __forceinline__ void link_one(const double* __restrict__ soft, uint32
         return;
     }
     for (int q = lane; q < kLinkLds; q += 64) s_bits[q] = q < OPV_FB ? (uint8_t)(frame[q] ^ kLinkLfsr.b[q]) : (uint8_t)0;
-    constexpr int kIter = (OPV_FBITS + 63) / 64;                  // 17 steps per lane (the last one for lanes < 48 only)
-    double sv[2 * kIter];
-#pragma unroll
-    for (int k = 0; k < kIter; ++k) {
-        const int t = lane + 64 * k;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const uint32_t a = link_deint_addr(2u * (uint32_t)(t < OPV_FBITS ? t : 0) + (uint32_t)h);
-            sv[2 * k + h] = soft[(first + a) & mask];
-        }
-    }
+    double sv[2 * kLaneSteps];
+    opv_gather_payload(soft, first, mask, lane, sv);
     __syncthreads();
     const double inv = -3.5 / scale;
     int n_err = 0, n_weak = 0, n_nonf = 0;
     double s2 = 0.0, sa = 0.0;
 #pragma unroll
-    for (int k = 0; k < kIter; ++k) {
+    for (int k = 0; k < kLaneSteps; ++k) {
         const int t = lane + 64 * k;
         if (t < OPV_FBITS) {
             // decoded bits t .. t - 6 = bits p .. p + 6 of the byte string, p = 1071 - t; f as the reference forms it (:819): the step's
@@ -97,19 +69,11 @@ __device__ __forceinline__ void link_one(const double* __restrict__ soft, uint32
             const uint32_t w = (uint32_t)s_bits[p >> 3] | ((uint32_t)s_bits[(p >> 3) + 1] << 8);
             const uint32_t v = (w >> (p & 7u)) & 0x7Fu;
             const uint32_t f = ((v & 1u) << 6) | (v >> 1);
-            const int e[2] = {__builtin_parity(f & 0x4Fu), __builtin_parity(f & 0x6Du)};   // G1 -> code bit 2 t, G2 -> 2 t + 1 (:820-824)
+            const int e[2] = {(int)opv_code_g1(f), (int)opv_code_g2(f)};                   // code bits 2 t and 2 t + 1 (:820-824)
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const double s = sv[2 * k + h];
-                // the decoder's quantiser (k_frame_decode.hip: decode_two - one multiply-add outside the guard band around the
-                // boundaries, the reference's sequence inside it)
-                const double x = fma(s, inv, 4.0);
-                int qv = (int)x;
-                if (__builtin_expect(fabs(x - rint(x)) < 1.0e-6 && x > -1.0 && x < 9.0, 0)) {
-                    const double nrm = (-s / scale) * 3.5 + 3.5;                           // contraction is off for this TU
-                    qv = (int)(nrm + 0.5);                                                 // C truncation toward zero
-                }
-                qv = qv < 0 ? 0 : (qv > 7 ? 7 : qv);
+                const int qv = opv_quantise3_unclamped(s, scale, inv);                         // the decoder's value; both tests below hold with or without its clamp
                 n_err += ((qv >= 4) ? 1 : 0) != e[h];
                 n_weak += (qv == 3 || qv == 4);
                 n_nonf += !(fabs(s) <= 1.7976931348623157e308);                            // NaN or +-Inf

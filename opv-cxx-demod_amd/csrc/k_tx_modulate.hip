@@ -35,38 +35,13 @@
 #include <math.h>
 
 #include "opv_device.h"
+#include "opv_frame_code.h"
 #include "opv_tx_internal.h"
 
 namespace {
-constexpr double kPi = 3.14159265358979323846;  // opv-mod.cpp:43
-constexpr double kTwoPi = 2.0 * kPi;
-constexpr double kFs = 2168000.0;
-constexpr double kDev = 54200.0 / 4.0;
 static_assert(((OPV_SYNC_WORD >> 23) & 1u) == 0u, "symbol 0 of a run (first sync bit) is taken to be 0: it never enters the sign product");
 static_assert(OPV_FSYMS % 2 == 0, "b_n toggles per symbol: a frame's first symbol always sees b_n = 1");
-
-__device__ inline void advance(double& ph, double inc) {  // opv-mod.cpp:274-279
-    ph += inc;
-    while (ph > kPi) ph -= kTwoPi;
-    while (ph < -kPi) ph += kTwoPi;
-}
-
-// the randomiser's byte sequence (opv-mod.cpp:97-113: state 0xFF, taps 7 6 4 2, reset per frame): a constant table
-struct LfsrTable { uint8_t b[OPV_FB]; };
-constexpr LfsrTable make_lfsr() {
-    LfsrTable t{};
-    unsigned st = 0xFF;
-    for (int i = 0; i < OPV_FB; ++i) {
-        unsigned v = 0;
-        for (int k = 0; k < 8; ++k) {
-            v = (v << 1) | ((st >> 7) & 1u);
-            st = ((st << 1) | (((st >> 7) ^ (st >> 6) ^ (st >> 4) ^ (st >> 2)) & 1u)) & 0xFFu;
-        }
-        t.b[i] = (uint8_t)v;
-    }
-    return t;
-}
-__constant__ LfsrTable kTxLfsr = make_lfsr();
+__constant__ OpvLfsrTable kTxLfsr = opv_make_lfsr();
 }  // namespace
 
 // frames: [n_frames][134]; codes: [n_frames * 2168] (bit 0: symbol bit, bit 1: parity of the frame's bits before it);
@@ -95,13 +70,10 @@ extern "C" __global__ __launch_bounds__(256) void k_tx_encode(const uint8_t* __r
 #pragma unroll
         for (int k = 0; k < 6; ++k)
             if (t - 1 - k >= 0) reg |= (unsigned)u[t - 1 - k] << k;
-        const unsigned g1 = __popc(reg & 0x4Fu) & 1u, g2 = __popc(reg & 0x6Du) & 1u;   // opv-mod.cpp:124-128
+        const unsigned g1 = opv_code_g1(reg), g2 = opv_code_g2(reg);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const unsigned i = 2u * (unsigned)t + (unsigned)h;                        // coded bit index, order g1, g2
-            const unsigned q = (i % 32u) * 67u + i / 32u;                            // opv-mod.cpp:145-149
-            sym[OPV_SYNC_BITS + ((q & ~7u) | (7u - (q & 7u)))] = (uint8_t)(h ? g2 : g1);
-        }
+        for (int h = 0; h < 2; ++h)                                                  // coded bit 2 t + h, order g1, g2
+            sym[OPV_SYNC_BITS + opv_interleave_addr(2u * (uint32_t)t + (uint32_t)h)] = (uint8_t)(h ? g2 : g1);
     }
     __syncthreads();
     // exclusive parity prefix over the frame's 2168 bits: 9 consecutive symbols per thread, scan of the 256 partials
@@ -158,12 +130,11 @@ extern "C" __global__ __launch_bounds__(64) void k_tx_expand_phases(const double
                                                                      double2* __restrict__ phases) {
     const uint64_t j = first_ckpt + (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (j >= n_ckpt) return;
-    const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;  // opv-mod.cpp:259-260
     double2 p = ckpt[j];
     const uint64_t s0 = j * OPV_TX_CKPT_SYMS;
     for (uint32_t s = 0; s < OPV_TX_CKPT_SYMS && s0 + s < nsym; ++s) {
         phases[s0 + s] = p;
-        for (int i = 0; i < OPV_SPS; ++i) { advance(p.x, inc1); advance(p.y, inc2); }
+        for (int i = 0; i < OPV_SPS; ++i) { advance(p.x, kInc1); advance(p.y, kInc2); }
     }
 }
 
@@ -180,7 +151,6 @@ extern "C" __global__ __launch_bounds__(64) void k_tx_modulate(const uint8_t* __
     __shared__ __attribute__((aligned(16))) int stage[64 * OPV_SPS];
     const uint64_t sym0 = (uint64_t)blockIdx.x * 64u;
     const uint64_t sym = sym0 + threadIdx.x;
-    const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;  // opv-mod.cpp:259-260
     int a = 0;                                      // +/-1: tone 1 with that sign, +/-2: tone 2, 0: silent
     double ph1 = 0.0, ph2 = 0.0;
     if (sym < nsym && sym != 0) {                   // (symbol 0: T = 0 right after the modulator's reset, :221-226 - silent)
@@ -222,8 +192,8 @@ extern "C" __global__ __launch_bounds__(64) void k_tx_modulate(const uint8_t* __
                 const uint32_t k = atomicAdd(amb_count, 1u);
                 if (k < amb_cap) amb_list[k] = sym * OPV_SPS + (uint64_t)i;
             }
-            advance(ph1, inc1);
-            advance(ph2, inc2);
+            advance(ph1, kInc1);
+            advance(ph2, kInc2);
         }
     }
     __syncthreads();

@@ -26,58 +26,27 @@
 
 namespace {
 
-constexpr double kPi = 3.14159265358979323846;  // opv-mod.cpp:43
-constexpr double kTwoPi = 2.0 * kPi;
-constexpr double kFs = 2168000.0;
-constexpr double kDev = 54200.0 / 4.0;  // opv-mod.cpp:36-37
-constexpr uint32_t kSync = 0x02B8DB;
 constexpr int kSps = OPV_SAMPLES_PER_SYMBOL;
-
-struct LfsrBytes {
-    uint8_t b[OPV_FRAME_BYTES];
-    LfsrBytes() {
-        unsigned st = 0xFF;
-        for (auto& o : b) {
-            unsigned v = 0;
-            for (int k = 0; k < 8; ++k) {
-                v = (v << 1) | ((st >> 7) & 1u);
-                st = ((st << 1) | (((st >> 7) ^ (st >> 6) ^ (st >> 4) ^ (st >> 2)) & 1u)) & 0xFFu;
-            }
-            o = (uint8_t)v;
-        }
-    }
-};
-const LfsrBytes kLfsr;
-
-inline size_t interleave_pos(size_t i) {  // opv-mod.cpp:145-149
-    const size_t p = (i % 32) * 67 + i / 32;
-    return (p & ~size_t(7)) | (7 - (p & 7));
-}
+constexpr OpvLfsrTable kLfsr = opv_make_lfsr();
 
 // 24 sync bits + 2144 interleaved coded bits of one frame, in on-air order; `linear` (optional): the coded bits in encoder order
 void frame_symbols(const uint8_t* payload, uint8_t* sym /*2168*/, uint8_t* linear = nullptr /*2144*/) {
-    for (int b = 0; b < 24; ++b) sym[b] = (kSync >> (23 - b)) & 1u;
-    uint8_t* coded = sym + 24;
+    for (int b = 0; b < OPV_SYNC_BITS; ++b) sym[b] = (OPV_SYNC_WORD >> (OPV_SYNC_BITS - 1 - b)) & 1u;
+    uint8_t* coded = sym + OPV_SYNC_BITS;
     unsigned sr = 0;
-    size_t o = 0;
+    uint32_t o = 0;
     for (int byte = OPV_FRAME_BYTES - 1; byte >= 0; --byte) {
         const unsigned v = payload[byte] ^ kLfsr.b[byte];
         for (int bit = 7; bit >= 0; --bit) {
             const unsigned in = (v >> bit) & 1u;
             const unsigned reg = (in << 6) | sr;
-            const uint8_t g1 = (uint8_t)__builtin_parity(reg & 0x4F), g2 = (uint8_t)__builtin_parity(reg & 0x6D);
+            const uint8_t g1 = (uint8_t)opv_code_g1(reg), g2 = (uint8_t)opv_code_g2(reg);
             if (linear) { linear[o] = g1; linear[o + 1] = g2; }
-            coded[interleave_pos(o++)] = g1;
-            coded[interleave_pos(o++)] = g2;
+            coded[opv_interleave_addr(o++)] = g1;
+            coded[opv_interleave_addr(o++)] = g2;
             sr = ((sr << 1) | in) & 0x3F;
         }
     }
-}
-
-inline void advance(double& ph, double inc) {  // opv-mod.cpp:274-279
-    ph += inc;
-    while (ph > kPi) ph -= kTwoPi;
-    while (ph < -kPi) ph += kTwoPi;
 }
 
 struct FrameStart {
@@ -117,7 +86,7 @@ extern "C" void opv_tap_tx_frame(const uint8_t* frame134, uint8_t* randomized134
         uint8_t sym[OPV_FRAME_SYMBOLS], lin[OPV_ENCODED_BITS];
         frame_symbols(frame134, sym, lin);
         if (coded2144) std::memcpy(coded2144, lin, OPV_ENCODED_BITS);
-        if (interleaved2144) std::memcpy(interleaved2144, sym + 24, OPV_ENCODED_BITS);
+        if (interleaved2144) std::memcpy(interleaved2144, sym + OPV_SYNC_BITS, OPV_ENCODED_BITS);
     }
 }
 
@@ -155,13 +124,12 @@ void opv_tx_symbol_codes(const uint8_t* frames, size_t n_frames, int8_t* amp) {
 
 void opv_tx_symbol_phases(size_t first_symbol, size_t n_symbols, double* ph1_io, double* ph2_io, double* out2) {
     // free-running NCOs, the reference's repeated addition + wrap (opv-mod.cpp:274-279); data-independent
-    const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;
     double ph1 = *ph1_io, ph2 = *ph2_io;
     (void)first_symbol;
     for (size_t k = 0; k < n_symbols; ++k) {
         out2[2 * k] = ph1;
         out2[2 * k + 1] = ph2;
-        for (int i = 0; i < kSps; ++i) { advance(ph1, inc1); advance(ph2, inc2); }
+        for (int i = 0; i < kSps; ++i) { advance(ph1, kInc1); advance(ph2, kInc2); }
     }
     *ph1_io = ph1;
     *ph2_io = ph2;
@@ -198,9 +166,8 @@ extern "C" void opv_tap_tx_checkpoints(size_t first, size_t count, double* out2)
 #endif
 
 void opv_tx_sample_exact(double ph1_sym, double ph2_sym, int a, int i, int16_t* I, int16_t* Q) {
-    const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;
     double ph1 = ph1_sym, ph2 = ph2_sym;
-    for (int k = 0; k < i; ++k) { advance(ph1, inc1); advance(ph2, inc2); }
+    for (int k = 0; k < i; ++k) { advance(ph1, kInc1); advance(ph2, kInc2); }
     double vi = 0.0, vq = 0.0;
     if (a == 1 || a == -1) { vi = a * std::sin(ph1); vq = a * std::cos(ph1); }
     else if (a == 2 || a == -2) { const int sg = a / 2; vi = sg * std::sin(ph2); vq = sg * std::cos(ph2); }
@@ -223,16 +190,12 @@ static void modulate_frames(opv_tx_stream& st, const uint8_t* frames, size_t n_f
     std::vector<int8_t> amp(nsym);  // +/-1: tone 1 active with that sign; +/-2: tone 2; 0: silent
     std::vector<FrameStart> fs(n_frames);
     symbol_codes_from(st.T, st.bn, frames, n_frames, amp.data());
-    {
-        const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;
-        for (size_t f = 0; f < n_frames; ++f) {
-            fs[f] = {st.ph1, st.ph2};
-            for (int k = 0; k < OPV_FRAME_SYMBOLS * kSps; ++k) { advance(st.ph1, inc1); advance(st.ph2, inc2); }
-        }
+    for (size_t f = 0; f < n_frames; ++f) {
+        fs[f] = {st.ph1, st.ph2};
+        for (int k = 0; k < OPV_FRAME_SYMBOLS * kSps; ++k) { advance(st.ph1, kInc1); advance(st.ph2, kInc2); }
     }
     // pass 2 (frame-parallel): samples
     auto work = [&](size_t f0, size_t f1) {
-        const double inc1 = kTwoPi * (-kDev) / kFs, inc2 = kTwoPi * (+kDev) / kFs;
         for (size_t f = f0; f < f1; ++f) {
             double ph1 = fs[f].ph1, ph2 = fs[f].ph2;
             int16_t* o = iq + f * (size_t)OPV_FRAME_SYMBOLS * kSps * 2;
@@ -244,8 +207,8 @@ static void modulate_frames(opv_tx_stream& st, const uint8_t* frames, size_t n_f
                     else if (a == 2 || a == -2) { const int s = a / 2; I = s * std::sin(ph2); Q = s * std::cos(ph2); }
                     *o++ = (int16_t)(16383.0 * I);  // truncation toward zero (opv-mod.cpp:271-272)
                     *o++ = (int16_t)(16383.0 * Q);
-                    advance(ph1, inc1);
-                    advance(ph2, inc2);
+                    advance(ph1, kInc1);
+                    advance(ph2, kInc2);
                 }
             }
         }

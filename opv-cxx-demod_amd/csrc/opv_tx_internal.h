@@ -4,6 +4,20 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "opv_frame_code.h"
+
+// ---- the modulator's numbers, host and device (opv-mod.cpp:36-43, :259-260) and the NCO's step: a rounded add, then the wrap (:274-279)
+constexpr double kPi = 3.14159265358979323846;
+constexpr double kTwoPi = 2.0 * kPi;
+constexpr double kFs = 2168000.0;
+constexpr double kDev = 54200.0 / 4.0;
+constexpr double kInc1 = kTwoPi * (-kDev) / kFs, kInc2 = kTwoPi * (+kDev) / kFs;   // phase per sample of tone 1 / tone 2
+OPV_HD inline void advance(double& ph, double inc) {
+    ph += inc;
+    while (ph > kPi) ph -= kTwoPi;
+    while (ph < -kPi) ph += kTwoPi;
+}
+
 // per-symbol tone/sign code of a whole opv-mod run: +/-1 tone 1, +/-2 tone 2, 0 silent
 void opv_tx_symbol_codes(const uint8_t* frames134, size_t n_frames, int8_t* amp);
 // NCO phases (ph1, ph2) at the start of n_symbols consecutive symbols, continuing from *ph1/*ph2

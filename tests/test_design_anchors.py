@@ -27,9 +27,9 @@ ANCHORS = [
     ("csrc/k_frame_decode.hip", r"void k_frame_scale\(", "`csrc/k_frame_decode.hip:{n},"),
     ("csrc/k_frame_decode.hip", r"void k_frame_scale_wave\(", ",:{n}` (`k_frame_scale`"),
     ("csrc/k_frame_decode.hip", r"void decode_two\(", "`decode_two` `:{n}`"),
-    ("csrc/k_frame_decode.hip", r"uint32_t deint_addr\(", "`csrc/k_frame_decode.hip:{n}` `deint_addr`"),
+    ("csrc/opv_frame_code.h", r"uint32_t opv_interleave_addr\(", "`csrc/opv_frame_code.h:{n}` `opv_interleave_addr`"),
     ("csrc/k_frame_decode.hip", r"void k_frame_decode\(", "`k_frame_decode` `:{n}`"),
-    ("csrc/k_frame_decode.hip", r"LfsrTable kLfsr = ", "`kLfsr` `:{n}`"),
+    ("csrc/opv_frame_code.h", r"constexpr OpvLfsrTable opv_make_lfsr\(", "`opv_make_lfsr` `opv_frame_code.h:{n}`"),
     ("csrc/opv_rccl.hip", r"^extern \"C\" int opv_gather_frames\(", "`opv_gather_frames` `csrc/opv_rccl.hip:{n}`"),
     ("csrc/opv_capi.hip", r"^extern \"C\" int opv_process\(", "(`csrc/opv_capi.hip:{n}`)"),
     ("csrc/opv_capi.hip", r"^static void tie_host_fn\(", "(`tie_host_fn` `:{n}`"),

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
+                               still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
                                still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
                                still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
                                still 7, additive: + opv_export_size / opv_export_streams / opv_import_streams / opv_blob_streams, stream migration)
@@ -482,6 +483,56 @@ long opv_tx_modulate_device_to_host(opv_ctx* ctx, const uint8_t* frames134, size
  * of src/opv-mod.cpp:274-279 at symbol 128 * entry of a run - from the build-time table, beyond it (4096 frames) from the host
  * continuation. Host only, needs no device. */
 void opv_tap_tx_checkpoints(size_t first, size_t count, double* out2);
+/* ---- transmit bank: N live modulators on the device, their state carried from round to round ----------------------------
+ * Replaces N HDLModulator objects (src/opv-mod.cpp:219-291), each driven frame by frame as `opv-mod -R` drives its one
+ * (:473-498): a gateway that transmits many channels hands a few frames per channel and round to ONE set of launches and gets
+ * every channel's samples in device memory - the bytes the host modulator (opv_tx_stream_frames, `opv-mod`) makes.
+ * State of a modulator: `symbols`, the symbols it has put on the air since its reset, and `sign_parity`, the parity of all on-air
+ * bits sent since then: the differential sign T (:232-239) is -1 where it is odd (T = 0 holds only for symbol 0 of a run, which is
+ * silent), and b_n (:246-257) follows from the parity of `symbols`. The NCO phases (:274-279) are no part of the state: they are
+ * a function of `symbols` alone (opv_tap_tx_checkpoints every 128 symbols, replayed from there with the same adds and wraps).
+ * The two numbers are the whole modulator, so opv_txb_get_state / opv_txb_set_state also move a stream between banks.
+ * opv_txb_create: replaces N constructions + reset() (:221-226): n_streams (1 .. OPV_TXB_MAX_STREAMS) modulators as after reset,
+ *   tied to `ctx` (its device, its HIP stream, its NCO checkpoints and flat-top bits; the bank adds a byte of device state per
+ *   stream and a scratch area sized by the largest ROUND - nothing that grows with the length of a run).
+ * opv_txb_destroy: before its context. A bank whose context went first is detached: every call that needs the device answers
+ *   OPV_ESTATE, opv_txb_get_state still answers, and destroy frees what is the bank's own.
+ * opv_txb_reset: replaces reset() (:221-226) of one modulator, or of all (stream = -1): the next frame starts with the silent symbol.
+ * opv_txb_get_state / opv_txb_set_state: no counterpart in the reference (its modulator cannot be moved). set_state refuses
+ *   (OPV_EINVAL) a sign_parity outside {0, 1}, a non-zero `reserved` and symbols beyond OPV_TXB_MAX_RUN_FRAMES frames.
+ * opv_txb_round: replaces one pass of the sending loop (:473-498) for `count` of the modulators: entry i lets stream streams[i]
+ *   modulate the n_frames[i] frames at frames134[i] (0 is allowed and changes nothing) and writes n_frames[i] x 86720 samples to
+ *   the device pointer d_iq_out[i] (16-byte aligned). Frames are read from host memory, or - frames_on_device != 0 - from
+ *   device memory in stream order on the context's HIP stream (slices of opv_device_frames: a repeater needs no host copy; a
+ *   ring wrap is two rounds). Streams not named stand still. Synchronous; returns the number of samples re-evaluated on the host
+ *   with libm (>= 0, normally 0) or a negative error. For every stream, what its rounds wrote since its last reset equals the
+ *   first F x 86720 samples of opv_tx_modulate on the same F frames, for any split into rounds and any company in the bank. The
+ *   100 silent symbols that end a run are 4000 zero samples and carry no state (opv_tx_stream_tail): the caller's to write.
+ *   Refusals are decided before anything is enqueued and change nothing: OPV_EINVAL for a null pointer, count < 0, a stream out
+ *   of range or named twice, an output that is misaligned or overlaps another entry's, a round of more than 2^31 / 34 frames;
+ *   OPV_ECAPACITY for a stream whose run would pass OPV_TXB_MAX_RUN_FRAMES frames (reset it, as `opv-mod -c` resets once per
+ *   pass, :503-524); OPV_ESTATE for a detached bank.
+ * opv_txb_plan_round: those refusals plus the launch geometry, host only (needs no device; what opv_txb_round itself calls):
+ *   states[n_streams] as opv_txb_get_state gives them, out_addr[i] the address d_iq_out[i]; first_block[count + 1]: entry i owns
+ *   workgroups [first_block[i], first_block[i + 1]) of the modulate grid (64 symbols each: ceil(n_frames[i] x 2168 / 64), the last
+ *   one partial; none for an entry of 0 frames), first_symbol[count]: the entry's first symbol as an index into its stream's run.
+ * opv_tap_txb_patch (parity tap, host only): the int16 (I, Q) of ONE sample as the round's host patch evaluates an entry of the
+ *   device's list of ambiguous samples - sample `sample` (0..39) of symbol `symbol` of a run, tone / sign `code` (+-1 tone 1,
+ *   +-2 tone 2, 0 silent) - with libm, as the reference computes it (:268-279). */
+#define OPV_TXB_MAX_RUN_FRAMES 65536   /* 43.7 minutes on the air: 17.8 MB of NCO checkpoints at the far end */
+#define OPV_TXB_MAX_STREAMS 65536
+typedef struct opv_txb opv_txb;
+typedef struct opv_txb_state { uint64_t symbols; int32_t sign_parity; int32_t reserved; } opv_txb_state;
+int opv_txb_create(opv_txb** out, opv_ctx* ctx, int n_streams);
+void opv_txb_destroy(opv_txb* txb);
+int opv_txb_reset(opv_txb* txb, int stream);
+int opv_txb_get_state(opv_txb* txb, int stream, opv_txb_state* out);
+int opv_txb_set_state(opv_txb* txb, int stream, const opv_txb_state* in);
+long opv_txb_round(opv_txb* txb, int count, const int* streams, const uint8_t* const* frames134,
+                   const size_t* n_frames, int16_t* const* d_iq_out, int frames_on_device);
+int opv_txb_plan_round(int n_streams, const opv_txb_state* states, int count, const int* streams,
+                       const size_t* n_frames, const uintptr_t* out_addr, uint32_t* first_block, uint64_t* first_symbol);
+int opv_tap_txb_patch(uint64_t symbol, int sample, int code, int16_t out_iq[2]);
 /* Device-side channel tool for synthetic multi-stream workloads:
  * d_out[n] = clip(rint(gain * d_in[n] * exp(j 2 pi f0 n / Fs) + sigma * N(0,1)+jN(0,1))),
  * noise from a counter-based generator keyed by (seed, n). d_in/d_out: device int16 IQ. */

@@ -31,71 +31,16 @@
 // host's libm.
 //
 // Roofline: HBM write, 4 B/sample (a 1000-frame run: 347 MB); the phase table adds 16 B/symbol of reads (35 MB).
-#include <hip/hip_runtime.h>
-#include <math.h>
-
-#include "opv_device.h"
-#include "opv_frame_code.h"
-#include "opv_tx_internal.h"
-
-namespace {
-static_assert(((OPV_SYNC_WORD >> 23) & 1u) == 0u, "symbol 0 of a run (first sync bit) is taken to be 0: it never enters the sign product");
-static_assert(OPV_FSYMS % 2 == 0, "b_n toggles per symbol: a frame's first symbol always sees b_n = 1");
-__constant__ OpvLfsrTable kTxLfsr = opv_make_lfsr();
-}  // namespace
+// The frame code of k_tx_encode and the sample loop of k_tx_modulate live in k_tx_common.h: the transmit bank (k_tx_bank.hip) runs the same two.
+#include "k_tx_common.h"
 
 // frames: [n_frames][134]; codes: [n_frames * 2168] (bit 0: symbol bit, bit 1: parity of the frame's bits before it);
 // frame_par: [n_frames] parity of all 2168 bits of the frame
 extern "C" __global__ __launch_bounds__(256) void k_tx_encode(const uint8_t* __restrict__ frames, uint32_t n_frames,
                                                                uint8_t* __restrict__ codes, uint8_t* __restrict__ frame_par) {
-    __shared__ uint8_t u[OPV_FBITS];                // encoder input bits in encoding order
-    __shared__ uint8_t sym[OPV_FSYMS + 8];          // on-air bits: 24 sync + 2144 interleaved coded
-    __shared__ uint32_t part[256];
     const uint32_t f = blockIdx.x;
-    const int tid = threadIdx.x;
     if (f >= n_frames) return;
-    const uint8_t* p = frames + (size_t)f * OPV_FB;
-    if (tid < OPV_FB) {
-        // byte 133 goes first, MSB first (opv-mod.cpp:186-196): input bit t = bit (7 - t % 8) of byte (133 - t / 8)
-        const unsigned v = p[tid] ^ kTxLfsr.b[tid];
-        const int t0 = 8 * (OPV_FB - 1 - tid);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) u[t0 + b] = (uint8_t)((v >> (7 - b)) & 1u);
-    }
-    if (tid < OPV_SYNC_BITS) sym[tid] = (uint8_t)((OPV_SYNC_WORD >> (23 - tid)) & 1u);
-    __syncthreads();
-    for (int t = tid; t < OPV_FBITS; t += 256) {
-        // reg = (in << 6) | sr, sr bit k = input bit t - 1 - k (zero before the frame: the encoder is reset per frame, :161)
-        unsigned reg = (unsigned)u[t] << 6;
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-            if (t - 1 - k >= 0) reg |= (unsigned)u[t - 1 - k] << k;
-        const unsigned g1 = opv_code_g1(reg), g2 = opv_code_g2(reg);
-#pragma unroll
-        for (int h = 0; h < 2; ++h)                                                  // coded bit 2 t + h, order g1, g2
-            sym[OPV_SYNC_BITS + opv_interleave_addr(2u * (uint32_t)t + (uint32_t)h)] = (uint8_t)(h ? g2 : g1);
-    }
-    __syncthreads();
-    // exclusive parity prefix over the frame's 2168 bits: 9 consecutive symbols per thread, scan of the 256 partials
-    constexpr int kPer = (OPV_FSYMS + 255) / 256;
-    const int k0 = tid * kPer;
-    uint32_t mine = 0;
-    for (int k = k0; k < k0 + kPer && k < OPV_FSYMS; ++k) mine ^= sym[k];
-    part[tid] = mine;
-    __syncthreads();
-    for (int off = 1; off < 256; off <<= 1) {
-        const uint32_t v = tid >= off ? part[tid - off] : 0u;
-        __syncthreads();
-        part[tid] ^= v;
-        __syncthreads();
-    }
-    uint32_t run = part[tid] ^ mine;                // exclusive prefix of this thread's first symbol
-    uint8_t* out = codes + (size_t)f * OPV_FSYMS;
-    for (int k = k0; k < k0 + kPer && k < OPV_FSYMS; ++k) {
-        out[k] = (uint8_t)(sym[k] | (run << 1));
-        run ^= sym[k];
-    }
-    if (tid == 255) frame_par[f] = (uint8_t)part[255];
+    tx_encode_frame(frames + (size_t)f * OPV_FB, codes + (size_t)f * OPV_FSYMS, frame_par + f);
 }
 
 // in place: frame_par[f] <- XOR of the parities of frames 0..f-1 (one workgroup; runs of any length in slices of 1024)
@@ -154,48 +99,14 @@ extern "C" __global__ __launch_bounds__(64) void k_tx_modulate(const uint8_t* __
     int a = 0;                                      // +/-1: tone 1 with that sign, +/-2: tone 2, 0: silent
     double ph1 = 0.0, ph2 = 0.0;
     if (sym < nsym && sym != 0) {                   // (symbol 0: T = 0 right after the modulator's reset, :221-226 - silent)
-        const unsigned c = codes[sym];
-        // T(k) = prod_{0<j<k} d_j, d = -1 for a 1 bit (:232-239): its sign is the parity of the bits in front of the symbol
-        const int T = ((frame_pre[sym / OPV_FSYMS] ^ (c >> 1)) & 1u) ? -1 : 1;
-        if ((c & 1u) == 0u) a = T;                                          // bit 0: d_s1 = T (:241-245)
-        else a = 2 * ((sym & 1u) ? -T : T);                                 // bit 1: d_s2 = -/+T by b_n (:246-257); b_n = 0 on odd symbols
+        a = tx_symbol_code(codes[sym], frame_pre[sym / OPV_FSYMS], sym);
         const double2 p = phases[sym];
         ph1 = p.x; ph2 = p.y;
     }
-    int* mine = stage + threadIdx.x * OPV_SPS;
-    if (a == 0) {
-        for (int i = 0; i < OPV_SPS; ++i) mine[i] = 0;
-    } else {
-        const bool tone1 = (a == 1 || a == -1);
-        const double sgn = (a > 0) ? 1.0 : -1.0;
-        for (int i = 0; i < OPV_SPS; ++i) {
-            double sn, cs;
-            sincos(tone1 ? ph1 : ph2, &sn, &cs);
-            const double vi = 16383.0 * (sgn * sn), vq = 16383.0 * (sgn * cs);  // opv-mod.cpp:268-272
-            int I = (int)vi, Q = (int)vq;                                         // truncation toward zero
-            // a flat top (see the file comment): |sin| or |cos| = 1 - eps^2/2; whether libm's value IS 1.0 is a function
-            // of the symbol index
-            const bool top_i = fabs(vi) > 16382.5, top_q = fabs(vq) > 16382.5;
-            if (top_i | top_q) {
-                int mag = 16383;
-                if (sym >= flat_hi) mag = 16382;
-                else if (sym >= flat_lo) mag = ((flat_bits[sym - flat_lo] >> (tone1 ? 0 : 1)) & 1u) ? 16383 : 16382;
-                if (top_i) I = vi < 0.0 ? -mag : mag;
-                else Q = vq < 0.0 ? -mag : mag;
-            }
-            mine[i] = (I & 0xFFFF) | (Q << 16);
-            // Could libm's value truncate differently? Only if v sits within the two libraries' ~1e-11
-            // disagreement of a NON-ZERO integer without being exactly on it (|v| < 1 truncates to 0
-            // from either side); the flat tops are decided above.
-            const double ri = rint(vi), rq = rint(vq);
-            if ((!top_i && ri != 0.0 && vi != ri && fabs(vi - ri) < 1e-9) || (!top_q && rq != 0.0 && vq != rq && fabs(vq - rq) < 1e-9)) {
-                const uint32_t k = atomicAdd(amb_count, 1u);
-                if (k < amb_cap) amb_list[k] = sym * OPV_SPS + (uint64_t)i;
-            }
-            advance(ph1, kInc1);
-            advance(ph2, kInc2);
-        }
-    }
+    tx_symbol_samples(a, ph1, ph2, sym, flat_lo, flat_hi, flat_bits, stage + threadIdx.x * OPV_SPS, [&](int i) {
+        const uint32_t k = atomicAdd(amb_count, 1u);
+        if (k < amb_cap) amb_list[k] = sym * OPV_SPS + (uint64_t)i;
+    });
     __syncthreads();
     // 64 symbols x 40 samples = 2560 dwords = 10 x (64 lanes x 16 B)
     const uint64_t base = sym0 * OPV_SPS;

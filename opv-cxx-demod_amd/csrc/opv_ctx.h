@@ -1,5 +1,5 @@
 // opv_ctx.h — the context behind include/opv_demod.h as the files of the C-ABI shim see it (opv_capi.hip: life, opv_process, pops,
-// taps; opv_push.hip: the serving path; opv_migrate.hip; opv_link.hip; opv_tx_device.hip; opv_rccl.hip). Internal: the wideband object does
+// taps; opv_push.hip: the serving path; opv_migrate.hip; opv_link.hip; opv_tx_device.hip; opv_tx_bank.hip; opv_rccl.hip). Internal: the wideband object does
 // not see it (opv_wb_internal.h is its door).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -39,6 +39,12 @@ extern "C" __global__ void k_tx_encode(const uint8_t*, uint32_t, uint8_t*, uint8
 extern "C" __global__ void k_tx_scan_frames(uint8_t*, uint32_t);
 extern "C" __global__ void k_tx_expand_phases(const double2*, uint32_t, uint64_t, uint64_t, double2*);
 extern "C" __global__ void k_tx_modulate(const uint8_t*, const uint8_t*, const double2*, uint64_t, uint64_t, int*, uint32_t*, uint64_t*, uint32_t, uint64_t, uint64_t, const uint8_t*);
+struct OpvTxbEntry;
+struct OpvTxbAmb;
+extern "C" __global__ void k_txb_encode(const OpvTxbEntry*, uint32_t, uint32_t, uint8_t*, uint8_t*);
+extern "C" __global__ void k_txb_scan(const OpvTxbEntry*, uint32_t, uint8_t*, uint8_t*);
+extern "C" __global__ void k_txb_phases(const OpvTxbEntry*, uint32_t, uint32_t, const double2*, double2*);
+extern "C" __global__ void k_txb_modulate(const OpvTxbEntry*, uint32_t, const uint8_t*, const uint8_t*, const double2*, uint32_t*, OpvTxbAmb*, uint32_t, uint64_t, uint64_t, const uint8_t*);
 
 inline int fail(int code, const char* what, hipError_t e = hipSuccess) { return opv_int_fail(code, what, e); }   // sets opv_last_error, returns code
 
@@ -279,6 +285,9 @@ inline int settle_pushes(opv_ctx* c) {
 void link_launch(opv_ctx* c, uint64_t fr);
 int link_clear(opv_ctx* c, int lo, int hi);
 bool opv_tx_libm_flat_tops_as_assumed();   // opv_tx_device.hip: the probe behind opv_ctx::tx_trust_libm
+// opv_tx_device.hip: the context's NCO checkpoints, flat-top zone limits and flat bits brought up to a run of nsym symbols (the
+// context's device current); what opv_tx_modulate_device and a transmit bank's round (opv_tx_bank.hip) both start with
+int opv_tx_prepare_run(opv_ctx* c, size_t nsym);
 // a stream's staging buffer (which = 0) or its second one (1: compaction's target), allocated at first use: max_samples samples +
 // slack for whole-tile reads (opv_push.hip). `oom`: the refusal is OPV_ENOMEM with that text instead of OPV_EHIP.
 int ensure_iq_buffer(opv_ctx* c, HostStream& h, int which, const char* oom = nullptr);

@@ -64,34 +64,22 @@ extern "C" long opv_resample_device(opv_ctx* c, const int16_t* d_in, size_t n_in
     return (long)n_out;
 }
 
-extern "C" long opv_tx_modulate_device(opv_ctx* c, const uint8_t* frames, size_t n_frames, int16_t* d_iq_out) {
-    if (!c || !d_iq_out || (!frames && n_frames)) return fail(OPV_EINVAL, "null argument");
-    if (((uintptr_t)d_iq_out & 15u) != 0) return fail(OPV_EINVAL, "device IQ pointer must be 16-byte aligned");
-    if (n_frames > 0x7FFFFFFFull / OPV_FSYMS) return fail(OPV_EINVAL, "opv_tx_modulate_device: too many frames for one call");
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const size_t nsym = n_frames * OPV_FSYMS, nsym_total = nsym + 100;  // + 100 silent symbols (opv-mod.cpp:528-529)
-    constexpr uint32_t kAmbCap = 4096;
-    // ---- symbol-start phases: from the checkpoint table, expanded on the device, once per context and run length
-    if (c->tx_phases_have < nsym) {
-        const size_t need_ck = (nsym + OPV_TX_CKPT_SYMS - 1) / OPV_TX_CKPT_SYMS;
-        if (c->tx_ckpt_have < need_ck) {
-            const size_t ck_bytes = sizeof(double) * 2 * need_ck;           // (grow-only, exact; nothing on the stream reads it between calls)
-            if (c->tx_ckpt.cap < ck_bytes) c->tx_ckpt_have = 0;
-            if (int r = c->tx_ckpt.grow(ck_bytes, ck_bytes, {})) return r;
-            std::vector<double> ck(2 * (need_ck - c->tx_ckpt_have));
-            opv_tx_checkpoint_range(c->tx_ckpt_have, need_ck - c->tx_ckpt_have, ck.data());
-            HIPCHK(hipMemcpy(c->tx_ckpt.p + 2 * c->tx_ckpt_have, ck.data(), sizeof(double) * ck.size(), hipMemcpyHostToDevice));
-            c->tx_ckpt_have = need_ck;
-        }
-        size_t first_ck = c->tx_phases_have / OPV_TX_CKPT_SYMS;            // whole intervals already expanded stay
-        const size_t ph_bytes = sizeof(double) * 2 * nsym;
-        if (c->tx_phases.cap < ph_bytes) c->tx_phases_have = first_ck = 0;
-        if (int r = c->tx_phases.grow(ph_bytes, ph_bytes, {c->stream})) return r;   // (an earlier modulation may still read the old table)
-        const size_t n_new = need_ck - first_ck;
-        k_tx_expand_phases<<<(unsigned)((n_new + 63) / 64), 64, 0, c->stream>>>((const double2*)c->tx_ckpt.p, (uint32_t)need_ck, first_ck,
-                                                                                 nsym, (double2*)c->tx_phases.p);
-        HIPCHK(hipGetLastError());
-        c->tx_phases_have = nsym;
+// What a run of nsym symbols needs on the device besides its frames - the NCO checkpoints under it, the flat-top zone limits and
+// the flat bits up to its end - for whoever modulates it: opv_tx_modulate_device (one run from a reset) and a transmit bank's
+// round (opv_tx_bank.hip: nsym = the largest symbol any of its streams reaches). Grow-only, per context; both are synchronous
+// on the context's stream, so nothing on it reads these tables while they are extended.
+int opv_tx_prepare_run(opv_ctx* c, size_t nsym) {
+    // ---- checkpoints: from the build-time table (beyond it from the host continuation)
+    const size_t need_ck = (nsym + OPV_TX_CKPT_SYMS - 1) / OPV_TX_CKPT_SYMS;
+    if (c->tx_ckpt_have < need_ck) {
+        // (grow-only, by half again: a bank's streams lengthen their runs a frame per round, and a new buffer is filled from entry 0)
+        const size_t ck_bytes = sizeof(double) * 2 * need_ck;
+        if (c->tx_ckpt.cap < ck_bytes) c->tx_ckpt_have = 0;
+        if (int r = c->tx_ckpt.grow(ck_bytes, ck_bytes + ck_bytes / 2, {c->stream})) return r;
+        std::vector<double> ck(2 * (need_ck - c->tx_ckpt_have));
+        opv_tx_checkpoint_range(c->tx_ckpt_have, need_ck - c->tx_ckpt_have, ck.data());
+        HIPCHK(hipMemcpy(c->tx_ckpt.p + 2 * c->tx_ckpt_have, ck.data(), sizeof(double) * ck.size(), hipMemcpyHostToDevice));
+        c->tx_ckpt_have = need_ck;
     }
     // ---- flat tops: the zone limits from the checkpoint sequence (the drift is monotone), the bits in between from libm.
     // Both zone limits are statements about THIS process's libm (glibc: exactly 1.0 while eps < 1.05e-8); they are probed once
@@ -99,7 +87,7 @@ extern "C" long opv_tx_modulate_device(opv_ctx* c, const uint8_t* frames, size_t
     // another libm, a drift that is not monotone - every symbol's bits come from libm (flat_lo = 0, no upper zone): slower to
     // set up (two sincos per symbol of the run on the host), identical to `opv-mod` on this machine by construction.
     if (c->tx_flat_hi == ~0ull) {                            // (both limits found: final - the sequence is data-independent)
-        const size_t n_ck = (nsym + OPV_TX_CKPT_SYMS - 1) / OPV_TX_CKPT_SYMS;
+        const size_t n_ck = need_ck;
         auto drift = [](size_t j) {                          // distance of checkpoint j's phases from a multiple of pi/2
             double p[2];
             opv_tx_checkpoint_range(j, 1, p);
@@ -130,33 +118,70 @@ extern "C" long opv_tx_modulate_device(opv_ctx* c, const uint8_t* frames, size_t
     if (c->tx_flat_lo != ~0ull && nsym > c->tx_flat_lo) {
         const uint64_t want = c->tx_flat_hi < (uint64_t)nsym ? c->tx_flat_hi : (uint64_t)nsym;   // bits for [flat_lo, want)
         if (c->tx_flat_have < want) {
+            // The symbol-start phases of the zone, replayed on the host from the checkpoints (flat_lo is one: the adds and wraps
+            // the device makes), and libm's answer at each. Bits already made stay; a bank's streams cross the zone a frame per
+            // round, so the buffer grows by half again and only the new symbols are asked.
             const size_t cnt = (size_t)(want - c->tx_flat_lo);
-            if (c->tx_flat.cap < cnt) c->tx_flat_have = 0;
-            if (int r = c->tx_flat.grow(cnt, cnt, {c->stream})) return r;
-            std::vector<double> ph(2 * cnt);
-            HIPCHK(hipStreamSynchronize(c->stream));                        // the expansion above
-            HIPCHK(hipMemcpy(ph.data(), c->tx_phases.p + 2 * c->tx_flat_lo, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost));
-            std::vector<uint8_t> bits(cnt);
-            auto work = [&](size_t a, size_t b) {
-                for (size_t k = a; k < b; ++k) {
-                    const double p1 = ph[2 * k], p2 = ph[2 * k + 1];
-                    const bool e1 = std::fabs(std::sin(p1)) == 1.0 || std::fabs(std::cos(p1)) == 1.0;
-                    const bool e2 = std::fabs(std::sin(p2)) == 1.0 || std::fabs(std::cos(p2)) == 1.0;
-                    bits[k] = (uint8_t)((e1 ? 1 : 0) | (e2 ? 2 : 0));
+            size_t from = c->tx_flat_have > c->tx_flat_lo ? (size_t)(c->tx_flat_have - c->tx_flat_lo) : 0;
+            if (c->tx_flat.cap < cnt) {
+                from = 0;
+                c->tx_flat_have = 0;
+                if (int r = c->tx_flat.grow(cnt, cnt + cnt / 2, {c->stream})) return r;
+            }
+            from -= from % OPV_TX_CKPT_SYMS;                                 // (whole intervals: each starts at a checkpoint)
+            std::vector<uint8_t> bits(cnt - from);
+            const size_t iv0 = from / OPV_TX_CKPT_SYMS, iv1 = (cnt + OPV_TX_CKPT_SYMS - 1) / OPV_TX_CKPT_SYMS, ck0 = (size_t)(c->tx_flat_lo / OPV_TX_CKPT_SYMS);
+            auto work = [&](size_t a, size_t b) {                            // checkpoint intervals [a, b) of the zone
+                double ph[2 * OPV_TX_CKPT_SYMS];
+                for (size_t iv = a; iv < b; ++iv) {
+                    const size_t k0 = iv * OPV_TX_CKPT_SYMS, n = cnt - k0 < OPV_TX_CKPT_SYMS ? cnt - k0 : OPV_TX_CKPT_SYMS;
+                    double p[2];
+                    opv_tx_checkpoint_range(ck0 + iv, 1, p);
+                    opv_tx_symbol_phases(0, n, &p[0], &p[1], ph);
+                    for (size_t k = 0; k < n; ++k) {
+                        const double p1 = ph[2 * k], p2 = ph[2 * k + 1];
+                        const bool e1 = std::fabs(std::sin(p1)) == 1.0 || std::fabs(std::cos(p1)) == 1.0;
+                        const bool e2 = std::fabs(std::sin(p2)) == 1.0 || std::fabs(std::cos(p2)) == 1.0;
+                        bits[k0 + k - from] = (uint8_t)((e1 ? 1 : 0) | (e2 ? 2 : 0));
+                    }
                 }
             };
             unsigned nt = std::thread::hardware_concurrency();
             if (nt == 0) nt = 1;
             if (nt > 16) nt = 16;
-            if (cnt < 65536) nt = 1;
+            if (cnt - from < 65536) nt = 1;
             std::vector<std::thread> pool;
-            const size_t per = (cnt + nt - 1) / nt;
-            for (unsigned t = 1; t < nt; ++t) { const size_t a = t * per, b = a + per < cnt ? a + per : cnt; if (a < b) pool.emplace_back(work, a, b); }
-            work(0, per < cnt ? per : cnt);
+            const size_t per = (iv1 - iv0 + nt - 1) / nt;
+            for (unsigned t = 1; t < nt; ++t) { const size_t a = iv0 + t * per, b = a + per < iv1 ? a + per : iv1; if (a < b) pool.emplace_back(work, a, b); }
+            work(iv0, iv0 + per < iv1 ? iv0 + per : iv1);
             for (auto& th : pool) th.join();
-            HIPCHK(hipMemcpy(c->tx_flat.p, bits.data(), cnt, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(c->tx_flat.p + from, bits.data(), bits.size(), hipMemcpyHostToDevice));
             c->tx_flat_have = want;
         }
+    }
+    return OPV_OK;
+}
+
+extern "C" long opv_tx_modulate_device(opv_ctx* c, const uint8_t* frames, size_t n_frames, int16_t* d_iq_out) {
+    if (!c || !d_iq_out || (!frames && n_frames)) return fail(OPV_EINVAL, "null argument");
+    if (((uintptr_t)d_iq_out & 15u) != 0) return fail(OPV_EINVAL, "device IQ pointer must be 16-byte aligned");
+    if (n_frames > 0x7FFFFFFFull / OPV_FSYMS) return fail(OPV_EINVAL, "opv_tx_modulate_device: too many frames for one call");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const size_t nsym = n_frames * OPV_FSYMS, nsym_total = nsym + 100;  // + 100 silent symbols (opv-mod.cpp:528-529)
+    constexpr uint32_t kAmbCap = 4096;
+    if (int r = opv_tx_prepare_run(c, nsym)) return r;
+    // ---- symbol-start phases: from the checkpoints, expanded on the device, once per context and run length
+    if (c->tx_phases_have < nsym) {
+        const size_t need_ck = (nsym + OPV_TX_CKPT_SYMS - 1) / OPV_TX_CKPT_SYMS;
+        size_t first_ck = c->tx_phases_have / OPV_TX_CKPT_SYMS;            // whole intervals already expanded stay
+        const size_t ph_bytes = sizeof(double) * 2 * nsym;
+        if (c->tx_phases.cap < ph_bytes) c->tx_phases_have = first_ck = 0;
+        if (int r = c->tx_phases.grow(ph_bytes, ph_bytes, {c->stream})) return r;   // (an earlier modulation may still read the old table)
+        const size_t n_new = need_ck - first_ck;
+        k_tx_expand_phases<<<(unsigned)((n_new + 63) / 64), 64, 0, c->stream>>>((const double2*)c->tx_ckpt.p, (uint32_t)need_ck, first_ck,
+                                                                                 nsym, (double2*)c->tx_phases.p);
+        HIPCHK(hipGetLastError());
+        c->tx_phases_have = nsym;
     }
     // ---- scratch (grow-only)
     // three parts of one allocation, each on a 256-byte boundary: [frames][134], one code byte per symbol, a byte per frame

@@ -17,6 +17,19 @@ OPV_HD inline void advance(double& ph, double inc) {
     while (ph > kPi) ph -= kTwoPi;
     while (ph < -kPi) ph += kTwoPi;
 }
+// The same step without loops, for a phase that is in [-pi, pi] before it: tone 1 only ever falls (kInc1 < 0: it can pass -pi, never
+// pi) and tone 2 only ever rises, and |inc| < pi, so of the two loops above one never runs and the other at most once - the same
+// adds on the same values, the wrapped one chosen by a select (k_txb_phases replays 128 x 40 of these in a row per thread, and a
+// lone wave pays for every instruction of them)
+static_assert(kInc1 > -kPi && kInc1 < 0.0 && kInc2 < kPi && kInc2 > 0.0, "advance_tone1 / advance_tone2: one wrap per step at most, each to its side");
+OPV_HD inline void advance_tone1(double& ph) {
+    const double t = ph + kInc1, up = t + kTwoPi;
+    ph = t < -kPi ? up : t;
+}
+OPV_HD inline void advance_tone2(double& ph) {
+    const double t = ph + kInc2, down = t - kTwoPi;
+    ph = t > kPi ? down : t;
+}
 
 // per-symbol tone/sign code of a whole opv-mod run: +/-1 tone 1, +/-2 tone 2, 0 silent
 void opv_tx_symbol_codes(const uint8_t* frames134, size_t n_frames, int8_t* amp);

@@ -40,6 +40,8 @@ EXPORTS = [
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
     "opv_tap_push_soft",
     "opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads",
+    "opv_txb_create", "opv_txb_destroy", "opv_txb_reset", "opv_txb_get_state", "opv_txb_set_state", "opv_txb_round", "opv_txb_plan_round",
+    "opv_tap_txb_patch",
 ]
 
 
@@ -56,6 +58,13 @@ class Cfg(C.Structure):
 class WbCfg(C.Structure):
     _fields_ = [("decim", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("first_sample", C.c_uint64)]
+
+
+class TxbState(C.Structure):
+    _fields_ = [("symbols", C.c_uint64), ("sign_parity", C.c_int32), ("reserved", C.c_int32)]
+
+
+TXB_MAX_RUN_FRAMES = 65536
 
 
 class FrameMeta(C.Structure):
@@ -220,6 +229,16 @@ def lib():
         L.opv_pop_frames_link.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.opv_device_link.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.opv_link_payloads.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.opv_txb_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.c_int]
+        L.opv_txb_destroy.restype = None
+        L.opv_txb_destroy.argtypes = [C.c_void_p]
+        L.opv_txb_reset.argtypes = [C.c_void_p, C.c_int]
+        L.opv_txb_get_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(TxbState)]
+        L.opv_txb_set_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(TxbState)]
+        L.opv_txb_round.restype = C.c_long
+        L.opv_txb_round.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.opv_txb_plan_round.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_tap_txb_patch.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -334,6 +353,79 @@ class TxStream:
         if self.h:
             lib().opv_tx_stream_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- transmit bank (opv_txb_*)
+def txb_plan_round(states, streams, n_frames, out_addr):
+    """opv_txb_plan_round: what a round of a bank in `states` ((symbols, sign_parity) or (symbols, sign_parity, reserved) per
+    stream) refuses (raises OpvError) or, if it holds, (first_block[count + 1], first_symbol[count]); host only, needs no device"""
+    st = (TxbState * max(len(states), 1))(*[TxbState(*[int(v) for v in s]) for s in states])
+    n = len(streams)
+    ids = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+    nf = (C.c_size_t * max(n, 1))(*[int(v) for v in n_frames])
+    addr = (C.c_size_t * max(n, 1))(*[int(v) for v in out_addr])                 # (uintptr_t)
+    fb, fs = np.zeros(n + 1, np.uint32), np.zeros(max(n, 1), np.uint64)
+    _chk(lib().opv_txb_plan_round(len(states), st, n, ids, nf, addr, fb.ctypes.data, fs.ctypes.data))
+    return fb, fs[:n]
+
+
+def txb_patch(symbol, sample, code):
+    """opv_tap_txb_patch: int16 (I, Q) of one sample as a round's host patch evaluates it (libm); host only"""
+    out = np.zeros(2, np.int16)
+    _chk(lib().opv_tap_txb_patch(int(symbol), int(sample), int(code), out.ctypes.data))
+    return out
+
+
+class TxBank:
+    """n_streams live modulators on the device of `demod`, their state carried from round to round (opv_txb_*,
+    include/opv_demod.h). Close it before its Demod."""
+
+    def __init__(self, demod, n_streams):
+        self.demod = demod
+        self.n_streams = int(n_streams)
+        self.h = C.c_void_p()
+        _chk(lib().opv_txb_create(C.byref(self.h), demod.h, self.n_streams))
+
+    def round(self, streams, frames_list, d_out_ptrs, on_device=False):
+        """opv_txb_round: stream streams[i] modulates frames_list[i] into the device pointer d_out_ptrs[i]. frames_list[i] is an
+        array of 134-byte frames (host), or with on_device=True a pair (device pointer, number of frames). Returns the number
+        of samples the host re-evaluated."""
+        n = len(streams)
+        keep = []
+        if on_device:
+            ptrs, counts = [int(p) for p, _ in frames_list], [int(k) for _, k in frames_list]
+        else:
+            keep = [np.ascontiguousarray(f, np.uint8).reshape(-1, FRAME_BYTES) for f in frames_list]
+            ptrs, counts = [f.ctypes.data if len(f) else 0 for f in keep], [len(f) for f in keep]
+        ids = (C.c_int * max(n, 1))(*[int(s) for s in streams])
+        fp = (C.c_void_p * max(n, 1))(*ptrs)
+        nf = (C.c_size_t * max(n, 1))(*counts)
+        out = (C.c_void_p * max(n, 1))(*[int(p) for p in d_out_ptrs])
+        return _chk(lib().opv_txb_round(self.h, n, ids, fp, nf, out, int(bool(on_device))))
+
+    def state(self, stream):
+        """(symbols, sign_parity) of one modulator"""
+        s = TxbState()
+        _chk(lib().opv_txb_get_state(self.h, int(stream), C.byref(s)))
+        return int(s.symbols), int(s.sign_parity)
+
+    def set_state(self, stream, symbols, sign_parity, reserved=0):
+        s = TxbState(int(symbols), int(sign_parity), int(reserved))
+        _chk(lib().opv_txb_set_state(self.h, int(stream), C.byref(s)))
+
+    def reset(self, stream=-1):
+        _chk(lib().opv_txb_reset(self.h, int(stream)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().opv_txb_destroy(self.h)
+            self.h = C.c_void_p()
 
     def __del__(self):
         try:

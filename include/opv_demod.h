@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
+                               still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
                                still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
                                still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
                                still 7, additive: + opv_wb_* (the wideband front door: an exact integer DDC bank feeding a context's streams), opv_tap_iq;
@@ -533,6 +534,52 @@ long opv_txb_round(opv_txb* txb, int count, const int* streams, const uint8_t* c
 int opv_txb_plan_round(int n_streams, const opv_txb_state* states, int count, const int* streams,
                        const size_t* n_frames, const uintptr_t* out_addr, uint32_t* first_block, uint64_t* first_symbol);
 int opv_tap_txb_patch(uint64_t symbol, int sample, int code, int16_t out_iq[2]);
+/* ---- wideband transmit: K per-channel captures in, ONE wide capture out --------------------------------------------------
+ * The mirror image of opv_wb_*, and the stage behind the transmit bank: opv_txb_round leaves per-channel int16 captures at
+ * 2 168 000 S/s in device memory; an opv_wbtx object is a bank of K digital up-converters on the device that puts them on one
+ * carrier raster at interp x 2 168 000 S/s. The arithmetic is integer-exact and independent of summation order
+ * (tests/test_gpu_wideband_tx.py holds the device to a numpy int64 model with ==):
+ *   every channel delivers the same number of input samples x_k[m] = (I, Q) int16 per push, m = 0 at the first sample pushed into the
+ *   object, x_k[m] = 0 for m < 0; after N input samples per channel the object has written exactly N x interp wide samples.
+ *   Wide sample n = q interp + p (0 <= p < interp) has the absolute index a = first_sample + n. Per channel k and component:
+ *     y_k[n] = sum over j >= 0 with p + j interp < n_taps and q - j >= 0 of taps[p + j interp] x_k[q - j] (zero-stuffing, then an FIR; int32);
+ *     inc_k, phi = (uint32)(a x inc_k), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095] are the DDC's above with decim = interp:
+ *     one increment rule and one table (opv_wb_lo_table) serve both banks; the channel goes UP to +centre_hz, the conjugate of the DDC's mix:
+ *     wr += yr c - yi s, wi += yi c + yr s (int64, summed over k);
+ *   output per component clamp(floor((w + 2^(out_shift - 1)) / 2^out_shift), -32768, 32767) (out_shift = 0: no rounding term), packed
+ *   I | Q << 16 like every capture here.
+ *   Limits (anything else is OPV_EINVAL from opv_wbtx_plan / opv_wbtx_create): 1 <= interp <= 16, 1 <= n_taps <= 1024, 1 <= n_channels <= 256,
+ *     0 <= out_shift <= 40, for every phase p sum_j |taps[p + j interp]| <= 65535 (so |y| < 2^31: exact in int32; and
+ *     |sum_k w| < 256 x 2 x 2^31 x 2^15 = 2^55: exact in int64), finite centres.
+ * The only state between pushes is the last ceil((n_taps - 1) / interp) input samples of every channel and the count N: any split of
+ * the inputs into pushes gives the bytes of one push. The object does NOT migrate: rebuild it at the destination with
+ * first_sample + N x interp as its first_sample - and mind that its n = 0 then starts with an empty filter history.
+ * opv_wbtx_plan (host only, no device): validates cfg, centres and taps and writes the K increments.
+ * opv_wbtx_create: tied to ctx (its device and the HIP stream its transmit bank uses). Destroy the object before its context;
+ *   one that outlives it is detached: pushes and opv_wbtx_reset answer OPV_ESTATE, opv_wbtx_samples still answers, and
+ *   opv_wbtx_destroy frees only what is the object's own.
+ * opv_wbtx_push: d_in[k] is a device pointer to n_in packed samples (4-byte aligned), or null: an absent channel contributes zeros
+ *   for that push - its earlier samples still ring out through the filter, and zeros enter its history (a transmit-bank stream that
+ *   stands still in a round; an all-null push of 4000 samples is the silent tail of a run). The same buffer may serve several
+ *   channels. d_wide_out: device pointer to n_in x interp packed samples (4-byte aligned). One k_wbtx_duc launch in stream order
+ *   on the context's HIP stream (behind the opv_txb_round that made the inputs); synchronous like opv_txb_round. Refusals are
+ *   decided before anything is enqueued and change nothing: OPV_EINVAL for a null table or output, a misaligned pointer, an output
+ *   that overlaps an input, n_in x interp >= 2^31; OPV_ESTATE for a detached object. n_in = 0 is allowed and changes nothing.
+ * opv_wbtx_samples: N. opv_wbtx_reset: empties the history, sets N = 0 and first_sample. */
+typedef struct opv_wbtx_cfg {
+    int32_t interp;           /* U: wide samples per input sample */
+    int32_t n_channels;       /* K */
+    int32_t n_taps;           /* L */
+    int32_t out_shift;        /* S */
+    uint64_t first_sample;    /* absolute index of the first wide sample written (the LO phase is a function of it) */
+} opv_wbtx_cfg;
+typedef struct opv_wbtx opv_wbtx;
+int opv_wbtx_plan(const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
+int opv_wbtx_create(opv_wbtx** out, opv_ctx* ctx, const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* taps);
+void opv_wbtx_destroy(opv_wbtx* wbtx);
+int opv_wbtx_push(opv_wbtx* wbtx, const int16_t* const* d_in, size_t n_in, int16_t* d_wide_out);
+uint64_t opv_wbtx_samples(const opv_wbtx* wbtx);
+int opv_wbtx_reset(opv_wbtx* wbtx, uint64_t first_sample);
 /* Device-side channel tool for synthetic multi-stream workloads:
  * d_out[n] = clip(rint(gain * d_in[n] * exp(j 2 pi f0 n / Fs) + sigma * N(0,1)+jN(0,1))),
  * noise from a counter-based generator keyed by (seed, n). d_in/d_out: device int16 IQ. */

@@ -39,6 +39,9 @@ extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
 
 // ---- what the context offers (defined at the end of opv_push.hip; opv_int_fail in opv_capi.hip)
 int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code
+// inc_k = (uint32) llrint(centre_hz[k] / (rate_factor x 2 168 000) x 2^32) for both banks, defined once (opv_wideband.hip, beside
+// opv_wb_lo_table, the one LO table); OPV_EINVAL for a centre that is not finite
+int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_hz, uint32_t* inc_out);
 // What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
 // (or used) after its context finds ctx_alive false and touches nothing of the context.
 struct OpvWbShared {

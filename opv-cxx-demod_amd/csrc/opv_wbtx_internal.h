@@ -1,0 +1,31 @@
+// opv_wbtx_internal.h — what the host half of the wideband transmit bank (opv_wideband_tx.hip) hands to its kernel (k_wideband_tx.hip).
+// The door to the context, the increment rule and the LO table are the receive bank's (opv_wb_internal.h): one definition each.
+#ifndef OPV_WBTX_INTERNAL_H
+#define OPV_WBTX_INTERNAL_H
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// Arguments of k_wbtx_duc, by value. Input sample m of a channel (0 = its first sample ever pushed) feeds wide samples
+// [m U, (m + 1) U) of the object; this push holds input samples [N, N + n_in) and writes wide samples [N U, (N + n_in) U).
+struct OpvWbtxArgs {
+    const int* const* in;    // in[K]: n_in packed (I | Q << 16) samples per channel in device memory, or null for an absent channel (zeros)
+    const int* hist_in;      // [K][H]: the H input samples in front of this push, zeros where the channel had none yet
+    int* hist_out;           // the other carry buffer: the last H samples of (hist_in, this push), channel k by workgroup k % gridDim.x
+    const int16_t* lo;       // T[4096]
+    const int16_t* taps;     // h[L]
+    const uint32_t* inc;     // inc[K]
+    int* out;                // n_out = n_in U packed wide samples
+    uint32_t a0_lo;          // low 32 bits of first_sample + N U: all the closed-form phase needs
+    uint32_t n_in, n_out;
+    uint32_t U, L, K, S;
+    uint32_t H;              // ceil((L - 1) / U): input samples carried per channel
+    uint32_t J;              // floor((L - 1) / U) + 1: taps of the longest phase (p = 0)
+};
+constexpr uint32_t OPV_WBTX_THREADS = 256;                                  // = wide outputs per workgroup, one per thread
+constexpr uint32_t OPV_WBTX_SPAN = OPV_WBTX_THREADS + 1024;                 // input samples a workgroup holds per channel: <= 256 / U + 1 new ones + J - 1 <= 1023 in front
+constexpr uint32_t OPV_WBTX_TAPS = 1024 + 16;                               // J U <= L - 1 + U entries, zeros from L on
+
+extern "C" __global__ void k_wbtx_duc(OpvWbtxArgs a);
+
+#endif

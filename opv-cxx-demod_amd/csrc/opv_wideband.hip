@@ -39,18 +39,23 @@ int plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, ui
     int64_t gain = 0;
     for (int t = 0; t < cfg->n_taps; ++t) gain += taps[t] < 0 ? -(int64_t)taps[t] : (int64_t)taps[t];
     if (gain > (1ll << 21)) return opv_int_fail(OPV_EINVAL, "opv_wb: sum of |taps| exceeds 2^21");
-    const double fs = (double)cfg->decim * kWideRate;
-    for (int k = 0; k < cfg->n_channels; ++k) {
+    return opv_int_wb_increments(cfg->decim, cfg->n_channels, centre_hz, inc_out);
+}
+
+}  // namespace
+
+// the increment rule of both banks (the DDCs here, the up-converters of opv_wideband_tx.hip): the wide rate is rate_factor x 2 168 000 S/s
+int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_hz, uint32_t* inc_out) {
+    const double fs = (double)rate_factor * kWideRate;
+    for (int k = 0; k < n_channels; ++k) {
         const double f = centre_hz[k];
-        if (!std::isfinite(f)) return opv_int_fail(OPV_EINVAL, "opv_wb: non-finite centre frequency");
+        if (!std::isfinite(f)) return opv_int_fail(OPV_EINVAL, "opv_wb / opv_wbtx: non-finite centre frequency");
         const double turns = f / fs * 4294967296.0;
-        if (!(std::fabs(turns) < 9.0e18)) return opv_int_fail(OPV_EINVAL, "opv_wb: centre frequency out of range");
+        if (!(std::fabs(turns) < 9.0e18)) return opv_int_fail(OPV_EINVAL, "opv_wb / opv_wbtx: centre frequency out of range");
         inc_out[k] = (uint32_t)(uint64_t)std::llrint(turns);          // modulo 2^32: a negative centre wraps
     }
     return OPV_OK;
 }
-
-}  // namespace
 
 struct opv_wb {
     opv_ctx* ctx = nullptr;

@@ -42,6 +42,7 @@ EXPORTS = [
     "opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads",
     "opv_txb_create", "opv_txb_destroy", "opv_txb_reset", "opv_txb_get_state", "opv_txb_set_state", "opv_txb_round", "opv_txb_plan_round",
     "opv_tap_txb_patch",
+    "opv_wbtx_plan", "opv_wbtx_create", "opv_wbtx_destroy", "opv_wbtx_push", "opv_wbtx_samples", "opv_wbtx_reset",
 ]
 
 
@@ -57,6 +58,11 @@ class Cfg(C.Structure):
 
 class WbCfg(C.Structure):
     _fields_ = [("decim", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
+                ("first_sample", C.c_uint64)]
+
+
+class WbtxCfg(C.Structure):
+    _fields_ = [("interp", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("first_sample", C.c_uint64)]
 
 
@@ -239,6 +245,14 @@ def lib():
         L.opv_txb_round.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.opv_txb_plan_round.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.opv_tap_txb_patch.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+        L.opv_wbtx_plan.argtypes = [C.POINTER(WbtxCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wbtx_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbtxCfg), C.c_void_p, C.c_void_p]
+        L.opv_wbtx_destroy.restype = None
+        L.opv_wbtx_destroy.argtypes = [C.c_void_p]
+        L.opv_wbtx_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.opv_wbtx_samples.restype = C.c_uint64
+        L.opv_wbtx_samples.argtypes = [C.c_void_p]
+        L.opv_wbtx_reset.argtypes = [C.c_void_p, C.c_uint64]
         _lib = L
     return _lib
 
@@ -514,6 +528,58 @@ class Wideband:
             lib().opv_wb_destroy(self.h)                                     # (waits for the copy stream: nothing reads the blocks any more)
             self.h = C.c_void_p()
         self._inflight = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- wideband transmit (opv_wbtx_*)
+def _wbtx_args(interp, centre_hz, taps, out_shift, first_sample):
+    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
+    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
+    return WbtxCfg(int(interp), centre.size, taps.size, int(out_shift), int(first_sample)), centre, taps
+
+
+def wbtx_plan(interp, centre_hz, taps, out_shift, first_sample=0):
+    """opv_wbtx_plan: validates a plan and returns its K phase increments (uint32); host only, needs no device"""
+    cfg, centre, taps = _wbtx_args(interp, centre_hz, taps, out_shift, first_sample)
+    inc = np.zeros(max(centre.size, 1), np.uint32)
+    _chk(lib().opv_wbtx_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
+    return inc[:centre.size]
+
+
+class WidebandTx:
+    """A bank of up-converters on the device of `demod` that puts K per-channel captures (a TxBank's outputs) at centre_hz[k] of one
+    wide capture (opv_wbtx_*, include/opv_demod.h). Close it before its Demod."""
+
+    def __init__(self, demod, interp, centre_hz, taps, out_shift, first_sample=0):
+        self.demod = demod
+        self.cfg, centre, taps = _wbtx_args(interp, centre_hz, taps, out_shift, first_sample)
+        self.h = C.c_void_p()
+        _chk(lib().opv_wbtx_create(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
+
+    def push(self, d_in_ptrs, n_in, d_out_ptr):
+        """opv_wbtx_push: d_in_ptrs[k] is channel k's device pointer to n_in samples, or None for a channel absent from this push;
+        n_in x interp wide samples go to the device pointer d_out_ptr"""
+        if len(d_in_ptrs) != self.cfg.n_channels:
+            raise OpvError("WidebandTx: one input pointer (or None) per channel")
+        tab = (C.c_void_p * len(d_in_ptrs))(*[None if p is None else int(p) for p in d_in_ptrs])
+        _chk(lib().opv_wbtx_push(self.h, tab, int(n_in), C.c_void_p(d_out_ptr)))
+
+    def samples(self):
+        """N: input samples per channel pushed since the object's creation or last reset"""
+        return int(lib().opv_wbtx_samples(self.h))
+
+    def reset(self, first_sample=0):
+        _chk(lib().opv_wbtx_reset(self.h, int(first_sample)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().opv_wbtx_destroy(self.h)
+            self.h = C.c_void_p()
 
     def __del__(self):
         try:

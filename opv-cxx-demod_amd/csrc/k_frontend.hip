@@ -48,6 +48,11 @@
 //     multipliers and bit-field inserts, one shared reciprocal for the two divides, symbols
 //     processed in pairs with alternating "previous" registers, the first symbol of a call (no
 //     AFC) as its own instantiation, hazard slots of swaps / DPP reads filled with useful work.
+//     Between two batches of whole four-symbol trips the wave goes from the trip loop straight to the
+//     bookkeeping and back (fp64 ring: 35 instructions, 2 taken branches, the flag read's latency
+//     partly covered by scalar work; the remainder path - pairs, a last symbol, settle, copy, a
+//     second tap fetch, the `while` test - stood at ~82 and 6-7 and now serves only the first and
+//     last symbols of a call and a batch the soft ring cuts short).
 //   * int16 IQ is staged HBM -> LDS in 2048-sample tiles (8 KiB) with direct-to-LDS 16-byte
 //     loads (global_load_lds_dwordx4, 1 KiB per wave instruction), two tile slots forming a
 //     4096-sample ring (slot = sample index & 4095) plus a 4-sample guard that mirrors the head
@@ -56,7 +61,7 @@
 //     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
 //     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
 //     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
-//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, profiles/r10_bench_ab.txt).
+//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, round 13 - the batch boundary below - 652.5, profiles/r13_bench_ab.txt).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
 //     decisions on noisy input do. No MFMA: the per-symbol contraction is
 //     3x4x60 with a serial dependence between symbols.
@@ -450,16 +455,34 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
 
         // Tile bookkeeping for the symbol at `at` (wave-uniform, rare). Returns how many FOLLOWING
         // symbols need neither it nor the end-of-call test: pos advances by at most 42 samples per
-        // symbol (|adj| <= 2, ref :285-286).
-        auto housekeeping = [&](double at) {
-            const uint32_t b = uni((uint32_t)at);
+        // symbol (|adj| <= 2, ref :285-286). `adv`: NoAdvance, or the symbols of the batch just finished (the fast boundary):
+        // their soft_advance is done here, in the shadow of the flag read. A lost helper (overflow set by f64_wait) returns 0:
+        // `ready` is then short of gb + kAhead + 2, so lim1 below is negative.
+        using NoAdvance = std::integral_constant<uint32_t, 0>;
+        auto housekeeping = [&](double at, auto adv) {
+            // (the conversion on the VALU, ONE transfer to an SGPR; everything below is scalar arithmetic on it. Left alone,
+            // hipcc moves both words of `at` to SGPRs, converts from there and moves the result back a third time.)
+            uint32_t bv = (uint32_t)at;
+            asm("" : "+v"(bv));
+            const uint32_t b = uni(bv);
             const uint32_t gb = origin + b;                // global index of floor(pos)
+            [[maybe_unused]] uint32_t ready_v = 0;
             if constexpr (F64) {
                 // release the slots below the lowest tap, then take what the helper has written so far (it keeps
                 // about a ring ahead, so the wait below only ever happens at the launch's first symbol)
                 if (lane == 0) fl[0] = gb >= kBack ? gb - kBack : 0u;
-                uint32_t ready = uni(fl[1]);
-                if ((int)(ready - gb) < (int)(kAhead + 2u)) ready = f64_wait(gb + kAhead + 2u);
+                ready_v = fl[1];
+                __builtin_amdgcn_sched_barrier(0);         // the scalar work below covers part of the read's latency
+            }
+            if constexpr (std::is_same_v<decltype(adv), uint32_t>) soft_advance(adv);
+            int lim2 = (int)N - 52 - (int)b;
+            // ... and while the soft ring does not wrap: soft_off is masked, so at least one symbol fits behind it
+            uint32_t by_ring = ((soft_bmask + 8u - soft_off) >> 3) - 1u;
+            if constexpr (F64) {
+                asm volatile("" : "+s"(lim2), "+s"(by_ring));   // (formed here, not behind the wait where they are used)
+                __builtin_amdgcn_sched_barrier(0);
+                uint32_t ready = uni(ready_v);
+                if (__builtin_expect((int)(ready - gb) < (int)(kAhead + 2u), 0)) ready = f64_wait(gb + kAhead + 2u);
                 asm volatile("" ::: "memory");             // no tap read is hoisted above `ready`
                 next_evt = ready - kAhead;                 // taps of a symbol at gb' < next_evt lie below `ready`
             }
@@ -478,12 +501,10 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 }
             }
             // j more symbols are safe iff gb + 42 j + 1 < next_evt and b + 1 + 42 j + 50 <= N
-            const int lim1 = (int)(next_evt - gb) - 2, lim2 = (int)N - 52 - (int)b;
+            const int lim1 = (int)(next_evt - gb) - 2;
             int lim = lim1 < lim2 ? lim1 : lim2;
             if (lim < 0) lim = 0;
-            // ... and while the soft ring does not wrap: soft_off is masked, so at least one symbol fits behind it
             const uint32_t by_samples = ((uint32_t)lim * 1560u) >> 16;     // <= floor(lim / 42), lim < 2^17
-            const uint32_t by_ring = ((soft_bmask + 8u - soft_off) >> 3) - 1u;
             return by_samples < by_ring ? by_samples : by_ring;
         };
 
@@ -745,12 +766,12 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         auto sym = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) { symbol_r(tag, slot, cur, prv); };
 
         if (uni_lt(pos + 40.0 + 10.0, Nd)) {               // ref :221
-            (void)housekeeping(pos);
+            (void)housekeeping(pos, NoAdvance{});
             fetch(pos, true);
             sym(TagFirst{}, Slot0{}, qp, qp);
             soft_advance(1u);
             if (__builtin_expect(uni_lt(2000.0, fabs(fo)), 0) && uni_lt(pos + 40.0 + 10.0, Nd)) {
-                (void)housekeeping(pos);                   // an out-of-range -o is still in force for one more symbol
+                (void)housekeeping(pos, NoAdvance{});      // an out-of-range -o is still in force for one more symbol
                 fetch(pos, false);
                 sym(TagSecond{}, Slot0{}, qq, qp);
                 fo_settle();
@@ -758,24 +779,45 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 qp = qq;
             }
             // Batches: the end-of-call test and the tile events once, then as many symbols as are
-            // provably clear of both. Every symbol fetches its successor's taps; across a batch
-            // boundary that fetch is speculative (LDS only, harmless) and is repeated after the
-            // bookkeeping. Symbols go in pairs so that the "previous correlation" registers
-            // alternate instead of being copied.
+            // provably clear of both. Every symbol fetches its successor's taps; behind a remainder
+            // batch that fetch is speculative (LDS only, harmless) and is repeated after the
+            // bookkeeping, behind a batch of whole trips it is known good and kept (below).
             while (uni_lt(pos + 40.0 + 10.0, Nd)) {        // ref :221
-                uint32_t pairs = uni(housekeeping(pos)) >> 1;
+                uint32_t more = uni(housekeeping(pos, NoAdvance{}));   // symbols behind the one at pos that are clear of both tests
                 if (F64 && overflow != 0) break;           // the helper was lost (f64_wait)
                 fetch(pos, false);
-                const uint32_t batch = 2u * pairs + 1u;    // symbols of this batch: they fit in front of the soft ring's wrap
-                // four symbols per trip: a taken branch costs a lone wave 36 cycles (scripts/microbench/dpp64.hip, empty loop)
-                for (uint32_t quads = pairs >> 1; quads != 0u; --quads) {
-                    sym(TagSteady{}, Slot0{}, qq, qp);
-                    sym(TagSteady{}, Slot1{}, qp, qq);
-                    sym(TagSteady{}, Slot2{}, qq, qp);
-                    sym(TagSteady{}, Slot3{}, qp, qq);
-                    soft_v += 32u;
+                // The fast boundary: batches of whole four-symbol trips (a taken branch costs a lone wave 36 cycles,
+                // scripts/microbench/dpp64.hip, empty loop), from housekeeping straight back to housekeeping.
+                //  * After a whole trip the previous sums are in qp again: nothing is copied.
+                //  * fo stays unsettled: fo_raw is carried, and the next symbol clamps it as it does inside a trip. Every way
+                //    out of here settles it (the remainder path below ends in fo_settle; the overflow exit calls it).
+                //  * The symbol behind the batch has index 4 quads <= more, so housekeeping's promise covers it: it exists
+                //    (the `while` test is known true and is not evaluated), and its taps lie below `ready` / inside landed
+                //    tiles and inside the call. The batch's last symbol has already read them and they are NOT read again.
+                //    That read stays valid across the housekeeping that follows it: the new `low` is posted behind the read
+                //    in program order and one wave's LDS operations execute in order, the taps (>= floor(pos) - 10) are at or
+                //    above the new `low` as well, and the helper never writes a slot at or above `low`; on the int16 ring a
+                //    tile request refills the slot of tile t_lo only once the lowest tap has left it.
+                // (Six s_nop in front of the nest put the trip loop's top at 8 mod 32: the same loop ran 5.6 cycles per symbol
+                // slower at 16 mod 32. tools/align_vop3.py reports the address at every build and says how many to add when
+                // code in front of here has moved it. The fp64 ring only: with two waves per CU, 512 streams on the int16 ring,
+                // a loop so placed measured 1.2 % slower than where hipcc happened to put it. NOTEBOOK.md, Round 13.)
+                if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                while (more >= 4u) {
+                    for (uint32_t quads = more >> 2; quads != 0u; --quads) {
+                        sym(TagSteady{}, Slot0{}, qq, qp);
+                        sym(TagSteady{}, Slot1{}, qp, qq);
+                        sym(TagSteady{}, Slot2{}, qq, qp);
+                        sym(TagSteady{}, Slot3{}, qp, qq);
+                        soft_v += 32u;
+                    }
+                    more = uni(housekeeping(pos, more & ~3u));   // (0 once the helper is lost)
                 }
-                pairs &= 1u;
+                if (F64 && overflow != 0) { fo_settle(); break; }
+                // The remainder (more < 4: the first batches of a launch, the last symbols of a call, a batch the soft ring
+                // cuts short): symbols in pairs so that the "previous" registers alternate, one last symbol, settle, copy.
+                uint32_t pairs = more >> 1;
+                const uint32_t batch = 2u * pairs + 1u;    // symbols of this batch: they fit in front of the soft ring's wrap
                 for (; pairs != 0u; --pairs) {
                     sym(TagSteady{}, Slot0{}, qq, qp);
                     sym(TagSteady{}, Slot1{}, qp, qq);

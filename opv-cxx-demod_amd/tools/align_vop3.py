@@ -12,7 +12,8 @@ instruction's address and size (llvm-objdump). Then, function by function, runs 
 shrinkable members re-encoded as `_e64` (same operation, same operands, 8 bytes) where that lowers the number of 8-byte
 instructions on the wrong parity (a dynamic programme over the function: runs without a shrinkable member - s_nop,
 s_waitcnt, branches only - pass their parity on). No instruction is added, none is moved. The output is assembled again as a check; an `_e64` form the assembler rejects is
-blacklisted and the pass repeated.
+blacklisted and the pass repeated. Last, where the source marks a loop nest, the address of the four-symbol loop behind the mark
+is reported (report_marked_loops: it should be 8 mod 32).
 """
 import re
 import subprocess
@@ -170,6 +171,52 @@ def verify(before, after, flipped):
                      f"{a[k] if k < len(a) else None} vs {b[k] if k < len(b) else None}")
 
 
+MARK = "opv_symbol_loop_top"
+
+
+def symbol_loop_tops(ins):
+    """addresses of the innermost loops of a function that hold four symbol bodies (120 v_fmac_f64_dpp between a label and the
+    backward branch to it)"""
+    index = {x[0]: i for i, x in enumerate(ins)}
+    cands = []
+    for i, x in enumerate(ins):
+        if not x[2].startswith("s_cbranch") or not x[3].split() or not x[3].split()[0].isdigit():
+            continue
+        simm = (int(x[3].split()[0]) ^ 0x8000) - 0x8000
+        tgt = x[0] + 4 + 4 * simm
+        if tgt < x[0] and tgt in index and sum(1 for y in ins[index[tgt]:i] if y[2].startswith("v_fmac_f64_dpp")) == 120:
+            cands.append((x[0] - tgt, tgt, x[0]))
+    tops = []
+    for _, tgt, end in sorted(cands):
+        if not any(tgt <= t <= end for t in tops):
+            tops.append(tgt)
+    return sorted(tops)
+
+
+def report_marked_loops(out, where, after):
+    """A comment line holding MARK (an asm statement of the source, in front of a loop nest, followed by a few `s_nop 0`): says
+    where the top of the next four-symbol loop lies, and warns unless that is 8 mod 32. Why: the loop's speed depends on its place
+    in 32-byte windows (measured on an MI355X, a lone wave, the loop's text unchanged: fp64-ring loop 652.6 / 652.8 / 658.3 cycles
+    per symbol with its top at 8 / 0 / 16 mod 32: NOTEBOOK.md, Round 13), and that place is an accident of the code in front of
+    it. This pass adds nothing to its input, so the remedy is in the source: `s_nop 0` behind the mark, in pairs (8 bytes, so that
+    the parities chosen above stay); they execute where the mark stands, not in the loop."""
+    for m in [i for i, ln in enumerate(out) if ln.strip().startswith(";") and MARK in ln]:
+        f = next((f for f, idx in where.items() if idx and idx[0] < m < idx[-1] and f in after and len(idx) <= len(after[f])), None)
+        if f is None:
+            print(f"align_vop3: WARNING: the mark at line {m + 1} is in no function whose text matches its code", file=sys.stderr)
+            continue
+        idx, ins = where[f], after[f][:len(where[f])]
+        at = next(ins[k][0] for k, i in enumerate(idx) if i > m)
+        tops = [t for t in symbol_loop_tops(ins) if t >= at]
+        if not tops:
+            print(f"align_vop3: WARNING: {f}: no four-symbol loop behind the mark at line {m + 1}", file=sys.stderr)
+        elif tops[0] % 32 != 8:
+            print(f"align_vop3: WARNING: {f}: the marked four-symbol loop lies at {tops[0]:#x} = {tops[0] % 32} mod 32, not 8: "
+                  f"{(8 - tops[0]) % 32 // 4} more `s_nop 0` behind the mark in the source would put it there", file=sys.stderr)
+        else:
+            print(f"align_vop3: {f}: the marked four-symbol loop lies at {tops[0]:#x} = 8 mod 32")
+
+
 def stats(ins):
     eight = [x for x in ins if x[1] == 8]
     return len(eight), sum(1 for x in eight if x[0] % 8 == 4)
@@ -216,6 +263,7 @@ def main():
             sys.exit("align_vop3: no assembling output after 40 attempts")
         after = disassemble(obj)
         verify(before, after, flipped)
+        report_marked_loops(out, where, after)
         dst.write_text("\n".join(out))
         for f in before:
             if f in flipped:

@@ -250,7 +250,7 @@ int opv_sync(opv_ctx* ctx);
  * 4 = four streams per wavefront (fewer issued instructions per symbol; right when every SIMD has work),
  * 16 = sixteen streams per wavefront, one per DPP quad (fewest issued instructions per symbol and stream: 38 against 88 and 156;
  *      right from ~8 000 streams per context, where 16 per wave still put a wave on every second SIMD),
- * 0 = automatic (4 from 2049 streams per context, 16 from 8193; measured cross-overs on MI355X).
+ * 0 = automatic, by the context's stream count (csrc/opv_round_rules.h: frontend_kernel; measured cross-overs on MI355X).
  * Anything else is OPV_EINVAL. Results do not depend on the mapping beyond the fp64 re-association level of the soft symbols
  * (all decisions identical; the tests run every mapping and every launch shape against the oracle). */
 int opv_set_frontend(opv_ctx* ctx, int streams_per_wave);

@@ -2,7 +2,7 @@
 // (16 lanes), four interpolated samples per lane. Same arithmetic contract as k_frontend.hip
 // (reference src/opv-demod.cpp:206-329 + the chunker :1012-1113 / :1132-1173); selected by the shim
 // when a context carries enough streams to fill the chip without the one-wave-per-stream mapping
-// (opv_capi.hip: opv_set_frontend / automatic from 2049 streams).
+// (opv_set_frontend, or by stream count: opv_round_rules.h, frontend_kernel).
 //
 // Why: a symbol's loop filters, divides and atan2 are scalar work per STREAM. With one stream per
 // wave they are executed on 64 lanes for one result (about 65 of that kernel's 161 instructions per
@@ -17,8 +17,8 @@
 // needs for its four streams: 47 ms for 30 frames whether the context has 1025 or 4096 streams (four waves per
 // workgroup = one per SIMD of a CU by construction, see msk_frontend_x4_body), 81 ms for 8192 (two waves per SIMD):
 // front-end alone 228 GS/s at 4096 streams, 264 at 8192 (round 1: 87 / 130). The one-wave kernel runs 1024 streams at a
-// time in 23 ms per 30 frames: faster up to 2048 streams, slower from 2049 on, which is where the shim switches
-// (NOTEBOOK.md §3.1).
+// time in 23 ms per 30 frames: faster while two such rounds hold every stream, slower beyond, which is where the shim switches
+// (opv_round_rules.h: frontend_kernel; DESIGN.md §3.1, NOTEBOOK.md §3.1).
 //
 // Mapping (row r = lane / 16 serves stream 4*blockIdx.x + r, t = lane % 16):
 //   * lane t owns the interpolated samples Lam_j = L(pos + j - 10), j = t + 16 q, q = 0..3 (j < 60); the

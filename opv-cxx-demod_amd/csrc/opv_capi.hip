@@ -12,20 +12,20 @@
 
 #include "opv_ctx.h"
 #include "opv_offset_host.h"
+#include "opv_round_rules.h"
 #include "opv_stream_rules.h"
 
 namespace {
 
 thread_local std::string g_err;
 
-// one wave per stream, four of them per workgroup: from the stream count at which single-wave workgroups start to
-// double up on SIMDs (k_frontend.hip: msk_frontend_body)
-constexpr uint64_t kScaleWaveMaxFrames = 4096;    // frames (upper estimate) per round up to which the scale pre-pass runs one wave per frame
-constexpr int kFrontendWg4MinStreams = 512;
-constexpr int kFrontendX16MinStreams = 8192;      // measured on MI355X (NOTEBOOK.md §3.1): 8192 streams x 16 frames: four per wave 260 GS/s, sixteen per wave 247 (512 waves: half the SIMDs idle;
-                                                  // with 7 frames per stream, bench.py's sweep, 221 / 255: the cross-over IS about 8192); 16 384 x 8: 187 / 478; 32 768 x 8: 204 / 574
-constexpr int kFrontendX16Wg8MinStreams = 16384;  // 1024 waves of sixteen streams = one per SIMD; beyond that eight waves (two per SIMD) per workgroup
-constexpr int kFrontendX4MinStreams = 2049;      // measured on MI355X (NOTEBOOK.md §3.1): one wave per stream runs 1024 streams at a time (46 ms per 2048 x 30 frames, 69 ms from 2049 on), four per wave 4096 (47.5 ms)
+// the front-end kernels by their id in opv_round_rules.h (which says when each runs and with which launch): what opv_process
+// launches and names, opv_tap_occupancy asks about and opv_create prepares. k_coherent_frontend takes other arguments than the rest.
+using MskFrontend = void (*)(OpvStream*, OpvGlobalCfg, int);
+#define OPV_FE(k) {(const void*)k, #k}
+const struct { const void* fn; const char* name; } kFrontend[FE_N] = {OPV_FE(k_coherent_frontend), OPV_FE(k_msk_frontend_rb), OPV_FE(k_msk_frontend_rb_wg4),
+    OPV_FE(k_msk_frontend_x4_wg4), OPV_FE(k_msk_frontend_x16), OPV_FE(k_msk_frontend_x16_wg4), OPV_FE(k_msk_frontend_x16_wg8)};
+#undef OPV_FE
 
 __global__ void k_apply_inputs(OpvStream* streams, const StreamIn* in, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -99,13 +99,9 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
     c->cap_chunks = (uint32_t)(M / 80000 + 4);
 
     auto cleanup = [&](int code) { opv_destroy(c); return code; };
-#define HIPCHK_C(expr)                                                        \
-    do {                                                                      \
-        hipError_t _e = (expr);                                               \
-        if (_e != hipSuccess) return cleanup(fail(_e == hipErrorOutOfMemory ? OPV_ENOMEM : OPV_EHIP, #expr, _e)); \
-    } while (0)
+    auto hip_failed = [&](hipError_t e, const char* what) { return cleanup(fail(e == hipErrorOutOfMemory ? OPV_ENOMEM : OPV_EHIP, what, e)); };
 
-    HIPCHK_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK_OR(hip_failed, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     {   // The copy stream also carries a KERNEL (k_push_gather). The runtime has a handful of hardware queues per priority and
         // deals streams onto them round-robin: in a process with several contexts the kernel stream and the copy stream of one
         // context can land on the same queue, and the moves of round r + 1 then wait for the kernels of round r (bench.py's
@@ -115,25 +111,25 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
             hipStreamCreateWithPriority(&c->copy_stream, hipStreamNonBlocking, greatest) != hipSuccess) {
             (void)hipGetLastError();                       // (no priorities here: an ordinary stream - correct, the overlap is then up to the queue deal)
             c->copy_stream = nullptr;
-            HIPCHK_C(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
+            HIPCHK_OR(hip_failed, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
         }
     }
     const size_t S = (size_t)n_streams;
-    HIPCHK_C(hipHostMalloc(&c->h_in, sizeof(StreamIn) * S * opv_ctx::kInSlots, hipHostMallocDefault));
-    for (auto& e : c->in_ev) HIPCHK_C(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIPCHK_C(hipHostMalloc(&c->h_stall, sizeof(int) * opv_ctx::kInSlots, hipHostMallocDefault));
+    HIPCHK_OR(hip_failed, hipHostMalloc(&c->h_in, sizeof(StreamIn) * S * opv_ctx::kInSlots, hipHostMallocDefault));
+    for (auto& e : c->in_ev) HIPCHK_OR(hip_failed, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK_OR(hip_failed, hipHostMalloc(&c->h_stall, sizeof(int) * opv_ctx::kInSlots, hipHostMallocDefault));
     for (int i = 0; i < opv_ctx::kInSlots; ++i) c->h_stall[i] = 0;
-    HIPCHK_C(hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming));
-    HIPCHK_C(hipMalloc(&c->d_streams, sizeof(OpvStream) * S));
-    HIPCHK_C(hipMalloc(&c->d_in, sizeof(StreamIn) * S));
-    HIPCHK_C(hipMalloc(&c->d_soft, sizeof(double) * c->cap_soft * S));
-    HIPCHK_C(hipMalloc(&c->d_frec, sizeof(OpvFrameRec) * c->cap_frames * S));
-    HIPCHK_C(hipMalloc(&c->d_events, sizeof(OpvEventRec) * c->cap_events * S));
-    HIPCHK_C(hipMalloc(&c->d_chunks, sizeof(double) * 5 * c->cap_chunks * S));
-    HIPCHK_C(hipMalloc(&c->d_frames, (size_t)OPV_FB * c->cap_frames * S));
-    HIPCHK_C(hipMalloc(&c->d_metrics, sizeof(int32_t) * c->cap_frames * S));
-    HIPCHK_C(hipMalloc(&c->d_fscale, sizeof(double) * c->cap_frames * S));
-    HIPCHK_C(hipMalloc(&c->d_counts, sizeof(int32_t) * S));
+    HIPCHK_OR(hip_failed, hipEventCreateWithFlags(&c->done_ev, hipEventDisableTiming));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_streams, sizeof(OpvStream) * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_in, sizeof(StreamIn) * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_soft, sizeof(double) * c->cap_soft * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_frec, sizeof(OpvFrameRec) * c->cap_frames * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_events, sizeof(OpvEventRec) * c->cap_events * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_chunks, sizeof(double) * 5 * c->cap_chunks * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_frames, (size_t)OPV_FB * c->cap_frames * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_metrics, sizeof(int32_t) * c->cap_frames * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_fscale, sizeof(double) * c->cap_frames * S));
+    HIPCHK_OR(hip_failed, hipMalloc(&c->d_counts, sizeof(int32_t) * S));
     {   // cos / sin(pi i / 80) x u^k / k!, u = i - 19.5: the tone tables of the offset search folded into its Taylor weights
         std::vector<double> w((size_t)OPV_SPS * 2 * OPV_OFFS_TERMS);
         for (int i = 0; i < OPV_SPS; ++i) {
@@ -145,8 +141,8 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
                 t = t * u / (double)(k + 1);
             }
         }
-        HIPCHK_C(hipMalloc(&c->d_offs_wtab, sizeof(double) * w.size()));
-        HIPCHK_C(hipMemcpy(c->d_offs_wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
+        HIPCHK_OR(hip_failed, hipMalloc(&c->d_offs_wtab, sizeof(double) * w.size()));
+        HIPCHK_OR(hip_failed, hipMemcpy(c->d_offs_wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
     }
     // The library's four environment switches, all TEST HOOKS (include/opv_demod.h has the table): read here, once per context,
     // and nowhere else - a context never changes its behaviour after it has been created.
@@ -157,13 +153,13 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
     c->rb_fp64_ring = !std::getenv("OPV_FRONTEND_INT16_RING");
     {   // k_msk_frontend_rb addresses its dynamic LDS from address 0 on: it must have no static LDS (k_frontend.hip)
         hipFuncAttributes fa;
-        HIPCHK_C(hipFuncGetAttributes(&fa, (const void*)k_msk_frontend_rb));
+        HIPCHK_OR(hip_failed, hipFuncGetAttributes(&fa, kFrontend[FE_RB].fn));
         if (fa.sharedSizeBytes != 0) return cleanup(fail(OPV_EHIP, "k_msk_frontend_rb was built with static LDS"));
     }
     // the fp64-ring shape asks for more dynamic LDS than a launch gets by default (one workgroup per CU)
-    if (c->rb_fp64_ring) HIPCHK_C(hipFuncSetAttribute((const void*)k_msk_frontend_rb, hipFuncAttributeMaxDynamicSharedMemorySize, OPV_RB_LDS_F64));
+    if (c->rb_fp64_ring) HIPCHK_OR(hip_failed, hipFuncSetAttribute(kFrontend[FE_RB].fn, hipFuncAttributeMaxDynamicSharedMemorySize, OPV_RB_LDS_F64));
     if (c->host_ties) {
-        HIPCHK_C(hipMalloc(&c->d_tie_list, sizeof(uint32_t) * (S + 1)));
+        HIPCHK_OR(hip_failed, hipMalloc(&c->d_tie_list, sizeof(uint32_t) * (S + 1)));
         c->tie.slots = (uint32_t)(S < (size_t)OPV_TIE_SLOTS_MAX ? S : (size_t)OPV_TIE_SLOTS_MAX);
         // (82 MB of pinned memory for 512 slots: a host that cannot pin that much keeps working - the device then decides the ties
         // itself, and opv_offset_ties_on_host() says so)
@@ -175,8 +171,8 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
             c->tie.stage->n = c->tie.stage->listed = c->tie.stage->beyond = 0;
         }
     }
-    HIPCHK_C(hipMemsetAsync(c->d_frames, 0, (size_t)OPV_FB * c->cap_frames * S, c->stream));
-    HIPCHK_C(hipMemsetAsync(c->d_counts, 0, sizeof(int32_t) * S, c->stream));
+    HIPCHK_OR(hip_failed, hipMemsetAsync(c->d_frames, 0, (size_t)OPV_FB * c->cap_frames * S, c->stream));
+    HIPCHK_OR(hip_failed, hipMemsetAsync(c->d_counts, 0, sizeof(int32_t) * S, c->stream));
     k_fill_i32<<<256, 256, 0, c->stream>>>(c->d_metrics, INT32_MIN, (size_t)c->cap_frames * S);
 
     for (size_t i = 0; i < S; ++i) {
@@ -202,12 +198,11 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
         c->mirror[i] = s;
     }
     c->initial = c->mirror;
-    HIPCHK_C(hipMemcpyAsync(c->d_streams, c->mirror.data(), sizeof(OpvStream) * S, hipMemcpyHostToDevice, c->stream));
-    HIPCHK_C(hipStreamSynchronize(c->stream));
+    HIPCHK_OR(hip_failed, hipMemcpyAsync(c->d_streams, c->mirror.data(), sizeof(OpvStream) * S, hipMemcpyHostToDevice, c->stream));
+    HIPCHK_OR(hip_failed, hipStreamSynchronize(c->stream));
     c->mirror_valid = true;
     *out = c;
     return OPV_OK;
-#undef HIPCHK_C
 }
 
 extern "C" void opv_destroy(opv_ctx* c) {
@@ -246,44 +241,41 @@ static void tie_host_fn(void* p) {
     w->decided.fetch_add(n, std::memory_order_relaxed);
 }
 
-extern "C" int opv_process(opv_ctx* c) {
-    if (!c) return fail(OPV_EINVAL, "null context");
-    HIPCHK(hipSetDevice(c->cfg.device));
-    const int S = c->n_streams;
-    const int slot = (int)(c->round_no % opv_ctx::kInSlots);
-    if (c->round_no >= (unsigned)opv_ctx::kInSlots) HIPCHK(hipEventSynchronize(c->in_ev[slot]));  // upload of round_no-kInSlots done
-    StreamIn* in = c->h_in + (size_t)slot * S;
-    uint64_t max_new = 0, max_tapped = 0;
-    bool any = false;
+// ---- opv_process, stage by stage. What is decided comes from opv_round_rules.h; these enqueue it on c->stream, in this order.
+namespace {
+
+struct RoundInputs { bool any; uint64_t max_new, max_tapped; };
+
+// 1. every stream's update into the round's pinned slot; c->search_now: the streams whose offset search is due
+RoundInputs collect_inputs(opv_ctx* c, StreamIn* in) {
+    RoundInputs r{false, 0, 0};
     c->search_now.clear();
-    for (int i = 0; i < S; ++i) {
+    for (int i = 0; i < c->n_streams; ++i) {
         const HostStream& h = c->hs[i];
         in[i] = {h.d_iq, h.n_avail, h.eof, h.dirty ? 1 : 0, h.popped, h.events_popped};
-        if (h.dirty) any = true;
-        // k_offset_search's own condition (first full chunk in streaming mode, EOF in batch mode), once per stream
-        if (!h.search_seen && (c->cfg.streaming ? h.n_avail >= (uint64_t)OPV_CHUNK : h.eof != 0)) c->search_now.push_back(i);
+        if (h.dirty || h.tap_fresh) r.any = true;          // (tap_fresh: soft symbols staged by opv_tap_push_soft: work for the tracker and the decoder only)
+        if (search_due(c->cfg.streaming, h.n_avail, h.eof, h.search_seen)) c->search_now.push_back(i);
         const uint64_t fresh = h.n_avail - h.last_round_avail;
-        if (fresh > max_new) max_new = fresh;
-        if (h.tap_fresh) any = true;                       // soft symbols staged by opv_tap_push_soft: work for the tracker and the decoder only
-        if (h.tap_fresh > max_tapped) max_tapped = h.tap_fresh;
+        if (fresh > r.max_new) r.max_new = fresh;
+        if (h.tap_fresh > r.max_tapped) r.max_tapped = h.tap_fresh;
     }
-    // nothing new: still run the round while a stream may be waiting behind back-pressure (it resumes by itself once
-    // the tracker has consumed soft symbols / the caller has popped frames; the cursors travel with every round).
-    // Whether one is: the last round's kernels said so in a pinned word (a caller on the zero-copy path - opv_device_frames +
-    // opv_sync, no pops - never refreshes the mirror); while that round is still running the answer is "maybe".
-    if (!any && c->maybe_stalled && c->round_no > 0 && hipEventQuery(c->done_ev) == hipSuccess)
+    return r;
+}
+
+// 2. nothing new: still run the round while a stream may be waiting behind back-pressure (it resumes by itself once
+// the tracker has consumed soft symbols / the caller has popped frames; the cursors travel with every round).
+// Whether one is: the last round's kernels said so in a pinned word (a caller on the zero-copy path - opv_device_frames +
+// opv_sync, no pops - never refreshes the mirror); while that round is still running the answer is "maybe".
+bool round_idle(opv_ctx* c, bool any) {
+    if (any) return false;
+    if (c->maybe_stalled && c->round_no > 0 && hipEventQuery(c->done_ev) == hipSuccess)
         c->maybe_stalled = c->h_stall[(c->round_no - 1) % opv_ctx::kInSlots] != 0;
-    if (!any && !c->maybe_stalled) return OPV_OK;
-    // frames a stream can release this round: new symbols / 2168 plus what was pending (checked before anything is launched)
-    // (staged soft symbols count as what they are: one frame per 2168 of them)
-    uint64_t fr = max_new / (uint64_t)(OPV_FSYMS * 38);
-    if (max_tapped / (uint64_t)OPV_FSYMS > fr) fr = max_tapped / (uint64_t)OPV_FSYMS;
-    fr += 4;
-    if (fr > c->cap_frames) fr = c->cap_frames;
-    if (fr * (uint64_t)S > 0x7FFFFFFFull) return fail(OPV_EINVAL, "opv_process: streams x frames per round exceeds the grid limit");
-    // the round will be launched: only now is the host's view of the streams advanced (a refused round leaves it untouched)
-    for (int i = 0; i < S; ++i) {
-        HostStream& h = c->hs[i];
+    return !c->maybe_stalled;
+}
+
+// 4. the round will be launched: only now is the host's view of the streams advanced (a refused round leaves it untouched)
+void commit_host_view(opv_ctx* c, int slot) {
+    for (HostStream& h : c->hs) {
         h.last_round_avail = h.n_avail;
         h.dirty = false;
         h.tap_fresh = 0;
@@ -292,35 +284,33 @@ extern "C" int opv_process(opv_ctx* c) {
     c->mirror_valid = false;
     c->maybe_stalled = true;
     c->h_stall[slot] = 0;          // (a straggler of round_no - kInSlots could still set it: then one idle round too many, never one too few)
+}
+
+// 5. pinned -> device, in stream order behind the previous round's kernels; no host wait
+int upload_inputs(opv_ctx* c, const StreamIn* in, int slot) {
+    const int S = c->n_streams;
     // samples of an asynchronous batch still crossing PCIe: this round's kernels read them, so they queue behind the moves (on the device)
     if (c->push_pending) HIPCHK(hipStreamWaitEvent(c->stream, c->push_ev, 0));
-    // pinned -> device, in stream order behind the previous round's kernels; no host wait
     HIPCHK(hipMemcpyAsync(c->d_in, in, sizeof(StreamIn) * S, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->in_ev[slot], c->stream));
     ++c->round_no;
-    OpvGlobalCfg g{c->cfg.streaming, c->cfg.have_init_offset, c->cfg.init_offset_hz};
     k_apply_inputs<<<(S + 63) / 64, 64, 0, c->stream>>>(c->d_streams, c->d_in, S);
-    const bool tm = c->timing;
-    if (tm) HIPCHK(hipEventRecord(c->ev[0], c->stream));
-    // searches that can run this round (none under a streaming -o: ref :1031), and whether their ties go to the host's libm
-    const size_t n_search = (c->cfg.streaming && c->cfg.have_init_offset) ? 0 : c->search_now.size();
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[0], c->stream));
+    return OPV_OK;
+}
+
+// 6. the offset search, and its near-ties decided with the host's libm before the front-end takes the estimate, IN STREAM ORDER:
+// per pass (tie_passes) of tie.slots listed streams a kernel stages their inputs in pinned memory, a host function decides them
+// (opv_offset_host.cpp), a kernel carries the results back. The caller never waits.
+int launch_search(opv_ctx* c, const OpvGlobalCfg& g) {
+    const int S = c->n_streams;
+    const size_t n_search = round_searches(c->cfg.streaming, c->cfg.have_init_offset, c->search_now.size());
     const bool host_ties = n_search != 0 && c->host_ties;
     if (host_ties) HIPCHK(hipMemsetAsync(c->d_tie_list, 0, sizeof(uint32_t), c->stream));
     k_offset_search<<<S, 256, 0, c->stream>>>(c->d_streams, g, c->d_offs_wtab, host_ties ? c->d_tie_list : nullptr);
-    if (tm) HIPCHK(hipEventRecord(c->ev[1], c->stream));
-    // near-ties are decided with the host's libm before the front-end takes the estimate, IN STREAM ORDER: per pass of
-    // tie.slots listed streams a kernel stages their inputs in pinned memory, a host function decides them
-    // (opv_offset_host.cpp), a kernel carries the results back. At most n_search streams can be listed, hence the number of
-    // passes - but never more than OPV_TIE_PASSES_MAX (8 x 512 = 4096 listed streams per round): a pass nobody is listed for
-    // costs the stream ~30 us (scripts/microbench/hostfunc.hip), a 32 768-stream round would pay for 64 of them, and a
-    // last-place tie that is NOT an exact mirror happens to about one stream in ten thousand (exact mirrors - real-valued
-    // captures, the one systematic source - come out the same on the device: test_offset_search_ties_decided_like_the_reference
-    // runs both paths). Streams listed beyond that keep the device's decision and are counted (opv_offset_ties_left_to_device).
-    // The caller never waits.
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[1], c->stream));
     if (host_ties) {
-        const uint32_t K = c->tie.slots;
-        uint32_t passes = (uint32_t)((n_search + K - 1) / K);
-        if (passes > OPV_TIE_PASSES_MAX) passes = OPV_TIE_PASSES_MAX;
+        const uint32_t K = c->tie.slots, passes = tie_passes(n_search, K);
         for (uint32_t p = 0; p < passes; ++p) {
             k_tie_collect<<<K, 256, 0, c->stream>>>(c->d_streams, c->d_tie_list, p, K, p + 1 == passes ? 1u : 0u, c->tie.stage);
             if (hipLaunchHostFunc(c->stream, tie_host_fn, &c->tie) != hipSuccess) {
@@ -333,52 +323,64 @@ extern "C" int opv_process(opv_ctx* c) {
             k_tie_apply<<<K, 192, 0, c->stream>>>(c->d_streams, c->tie.stage, K, S);
         }
     }
-    if (tm) HIPCHK(hipEventRecord(c->ev[2], c->stream));
-    // one wave per stream has the shortest per-symbol latency (what counts while SIMDs are idle); four streams per
-    // wave issue fewer instructions per symbol and stream, which pays once there are more streams than the one-wave
-    // kernel's two rounds of 1024 hold
-    const bool x4 = c->frontend == 4 || (c->frontend == 0 && S >= kFrontendX4MinStreams);
-    if (c->cfg.coherent && !c->cfg.streaming) {           // -c, batch only (ref :1144-1161)
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[2], c->stream));
+    return OPV_OK;
+}
+
+// 7. the front-end: the kernel and launch frontend_choice names
+int launch_frontend(opv_ctx* c, const OpvGlobalCfg& g) {
+    const int S = c->n_streams;
+    const FrontendChoice ch = frontend_choice(S, c->frontend, c->cfg.coherent, c->cfg.streaming, c->rb_fp64_ring, c->n_cu);
+    c->last_frontend = kFrontend[ch.kernel].name;
+    if (ch.kernel == FE_COHERENT) {
         const double wn = c->cfg.pll_bw_hz * 2.0 * M_PI, zeta = 0.707, fsym = 2168000.0 / 40.0;   // set_pll_bandwidth (ref :551-558)
-        c->last_frontend = "k_coherent_frontend";
-        k_coherent_frontend<<<S, 64, 0, c->stream>>>(c->d_streams, 2.0 * zeta * wn / fsym, wn * wn / (fsym * fsym));
-    }
-    else if (c->frontend == 16 || (c->frontend == 0 && S > kFrontendX16MinStreams)) {   // sixteen streams per wave (k_frontend_x16.hip): four waves (64 streams) per workgroup
-        if (S > kFrontendX16Wg8MinStreams) { c->last_frontend = "k_msk_frontend_x16_wg8"; k_msk_frontend_x16_wg8<<<(S + 127) / 128, 512, 0, c->stream>>>(c->d_streams, g, S); }
-        else if (S > 16) { c->last_frontend = "k_msk_frontend_x16_wg4"; k_msk_frontend_x16_wg4<<<(S + 63) / 64, 256, 0, c->stream>>>(c->d_streams, g, S); }
-        else { c->last_frontend = "k_msk_frontend_x16"; k_msk_frontend_x16<<<1, 64, 0, c->stream>>>(c->d_streams, g, S); }
-    }
-    else if (x4) {                                        // four waves (16 streams) per workgroup, whatever the stream count (automatic: 2049..8192)
-        c->last_frontend = "k_msk_frontend_x4_wg4";
-        k_msk_frontend_x4_wg4<<<(S + 15) / 16, 256, 0, c->stream>>>(c->d_streams, g, S);
-    }
-    // one wave per stream, row-broadcast reduction (k_frontend.hip: symbol_r). Its 272-278 registers allow one wave per SIMD;
-    // four waves per workgroup (one per SIMD of a CU by construction) as soon as single-wave workgroups could double up
-    else if (S > kFrontendWg4MinStreams) {
-        c->last_frontend = "k_msk_frontend_rb_wg4";
-        k_msk_frontend_rb_wg4<<<(S + 3) / 4, 256, 0, c->stream>>>(c->d_streams, g, S);
-    } else if (c->rb_fp64_ring && S <= c->n_cu) {       // a helper wave per stream widens the IQ to fp64 (k_frontend.hip: f64_ring_helper)
-        c->last_frontend = "k_msk_frontend_rb";
-        k_msk_frontend_rb<<<S, 128, OPV_RB_LDS_F64, c->stream>>>(c->d_streams, g, S);
+        k_coherent_frontend<<<ch.grid, ch.threads, ch.lds, c->stream>>>(c->d_streams, 2.0 * zeta * wn / fsym, wn * wn / (fsym * fsym));
     } else {
-        c->last_frontend = "k_msk_frontend_rb";
-        k_msk_frontend_rb<<<S, 64, OPV_RB_LDS_I16, c->stream>>>(c->d_streams, g, S);
+        ((MskFrontend)kFrontend[ch.kernel].fn)<<<ch.grid, ch.threads, ch.lds, c->stream>>>(c->d_streams, g, S);
     }
-    if (tm) { HIPCHK(hipEventRecord(c->ev[3], c->stream)); HIPCHK(hipEventRecord(c->ev[4], c->stream)); }
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[3], c->stream));
+    return OPV_OK;
+}
+
+// 8. the back half: tracker, the quantiser's scale, decoder (scale_shape / decode_grid), the opt-in link report, the counts
+int launch_back_half(opv_ctx* c, uint64_t fr, int slot) {
+    const int S = c->n_streams;
+    const bool tm = c->timing;
+    if (tm) HIPCHK(hipEventRecord(c->ev[4], c->stream));
     k_sync_track<<<S, 64, 0, c->stream>>>(c->d_streams);
     if (tm) { HIPCHK(hipEventRecord(c->ev[5], c->stream)); HIPCHK(hipEventRecord(c->ev[6], c->stream)); }
-    // the quantiser's scale (2144 dependent additions per frame) with one frame per lane, then one wave per two frames
-    // (one frame per lane - the HBM-rate shape - for bulk rounds; one wave per frame while the round is so small that a wave of 64
-    // frames would be the whole launch: a live round of 64 frames 46 -> 12 us)
-    if (fr * (uint64_t)S <= kScaleWaveMaxFrames) k_frame_scale_wave<<<(unsigned)(fr * (uint64_t)S), 64, 0, c->stream>>>(c->d_streams, (uint32_t)fr);
-    else k_frame_scale<<<(unsigned)((fr * (uint64_t)S + 63) / 64), 64, 0, c->stream>>>(c->d_streams, (uint32_t)fr, (uint32_t)S);
-    k_frame_decode<<<(unsigned)(((fr + 1) / 2) * (uint64_t)S), 64, 0, c->stream>>>(c->d_streams, (uint32_t)((fr + 1) / 2));   // two frames per wave
+    const ScaleShape sc = scale_shape(fr, S);
+    if (sc.wave) k_frame_scale_wave<<<sc.grid, 64, 0, c->stream>>>(c->d_streams, (uint32_t)fr);
+    else k_frame_scale<<<sc.grid, 64, 0, c->stream>>>(c->d_streams, (uint32_t)fr, (uint32_t)S);
+    k_frame_decode<<<decode_grid(fr, S), 64, 0, c->stream>>>(c->d_streams, decode_pairs(fr));
     if (tm) { HIPCHK(hipEventRecord(c->ev[7], c->stream)); c->timing_valid = true; }
     link_launch(c, fr);            // the opt-in fifth stage (opv_link.hip): behind the decoder's bracket, nothing while it is off
     k_collect_counts<<<(S + 63) / 64, 64, 0, c->stream>>>(c->d_streams, c->d_counts, S, c->h_stall + slot);
     HIPCHK(hipEventRecord(c->done_ev, c->stream));
     HIPCHK(hipGetLastError());
     return OPV_OK;
+}
+
+}  // namespace
+
+extern "C" int opv_process(opv_ctx* c) {
+    if (!c) return fail(OPV_EINVAL, "null context");
+    HIPCHK(hipSetDevice(c->cfg.device));
+    const int S = c->n_streams;
+    const int slot = (int)(c->round_no % opv_ctx::kInSlots);
+    if (c->round_no >= (unsigned)opv_ctx::kInSlots) HIPCHK(hipEventSynchronize(c->in_ev[slot]));  // upload of round_no-kInSlots done
+    StreamIn* in = c->h_in + (size_t)slot * S;
+    const RoundInputs ri = collect_inputs(c, in);
+    if (round_idle(c, ri.any)) return OPV_OK;
+    // 3. the frame budget and the refusal, before anything is launched
+    const uint64_t fr = round_frames(ri.max_new, ri.max_tapped, c->cap_frames);
+    if (!round_fits_grid(fr, S)) return fail(OPV_EINVAL, "opv_process: streams x frames per round exceeds the grid limit");
+    commit_host_view(c, slot);
+    const OpvGlobalCfg g{c->cfg.streaming, c->cfg.have_init_offset, c->cfg.init_offset_hz};
+    if (int r = upload_inputs(c, in, slot)) return r;
+    if (int r = launch_search(c, g)) return r;
+    if (int r = launch_frontend(c, g)) return r;
+    return launch_back_half(c, fr, slot);
 }
 
 extern "C" int opv_set_frontend(opv_ctx* c, int streams_per_wave) {
@@ -432,6 +434,17 @@ extern "C" int opv_kernel_times(opv_ctx* c, float ms[4]) {
     return OPV_OK;
 }
 
+// the (at most two) runs `r` of a device ring of `elem`-byte slots against the linear host buffer `lin`: ring -> lin, or lin -> ring
+// with hipMemcpyHostToDevice; asynchronous on `stream` where one is given
+static int ring_copy(void* lin, const void* d_ring, const RingRuns& r, size_t elem, hipMemcpyKind kind, hipStream_t stream = nullptr) {
+    const size_t at[2] = {(size_t)r.p0 * elem, 0}, bytes[2] = {(size_t)r.run0 * elem, (size_t)r.run1 * elem};
+    for (int k = 0; k < 2 && bytes[k]; ++k) {
+        void *h = (char*)lin + k * bytes[0], *d = (char*)d_ring + at[k], *dst = kind == hipMemcpyHostToDevice ? d : h, *src = dst == d ? h : d;
+        HIPCHK(stream ? hipMemcpyAsync(dst, src, bytes[k], kind, stream) : hipMemcpy(dst, src, bytes[k], kind));
+    }
+    return OPV_OK;
+}
+
 // copies records [first, first+n) of a device ring with `cap` slots of `elem` bytes into dst (host)
 static int ring_to_host(opv_ctx* c, void* dst, const void* d_ring, uint32_t first, uint32_t n, uint32_t cap, size_t elem) {
     const RingRuns r = ring_runs(first, n, cap);
@@ -444,9 +457,7 @@ static int ring_to_host(opv_ctx* c, void* dst, const void* d_ring, uint32_t firs
             return OPV_OK;
         }
     }
-    HIPCHK(hipMemcpy(dst, (const char*)d_ring + r.p0 * elem, r.run0 * elem, hipMemcpyDeviceToHost));
-    if (r.run1) HIPCHK(hipMemcpy((char*)dst + r.run0 * elem, d_ring, r.run1 * elem, hipMemcpyDeviceToHost));
-    return OPV_OK;
+    return ring_copy(dst, d_ring, r, elem, hipMemcpyDeviceToHost);
 }
 
 extern "C" long opv_pop_frames(opv_ctx* c, int s, uint8_t* out, size_t cap, opv_frame_meta* meta) {
@@ -573,9 +584,7 @@ extern "C" long opv_tap_soft(opv_ctx* c, int s, uint64_t first, double* out, siz
     if (first >= st.n_soft || cap == 0 || !out) return 0;
     uint64_t n = st.n_soft - first;
     if (n > cap) n = cap;
-    const RingRuns r = ring_runs(first, n, st.cap_soft);
-    HIPCHK(hipMemcpy(out, st.soft + r.p0, sizeof(double) * r.run0, hipMemcpyDeviceToHost));
-    if (r.run1) HIPCHK(hipMemcpy(out + r.run0, st.soft, sizeof(double) * r.run1, hipMemcpyDeviceToHost));
+    if (int r = ring_copy(out, st.soft, ring_runs(first, n, st.cap_soft), sizeof(double), hipMemcpyDeviceToHost)) return r;
     return (long)n;
 }
 
@@ -597,10 +606,8 @@ extern "C" int opv_tap_push_soft(opv_ctx* c, int s, const double* soft, size_t n
     if (n > st.cap_soft || (st.n_soft - soft_keep(st)) + n > st.cap_soft)
         return fail(OPV_ECAPACITY, "opv_tap_push_soft: the soft-symbol ring has no room (unread symbols + this push do not fit; "
                                    "call opv_process / opv_pop_frames between pushes)");
-    const RingRuns r = ring_runs(st.n_soft, n, st.cap_soft);
-    HIPCHK(hipMemcpyAsync(st.soft + r.p0, soft, sizeof(double) * r.run0, hipMemcpyHostToDevice, c->stream));
-    if (r.run1) HIPCHK(hipMemcpyAsync(st.soft, soft + r.run0, sizeof(double) * r.run1, hipMemcpyHostToDevice, c->stream));
-    st.n_soft += n;                                        // (the mirror stays valid: it is what the device holds after these copies)
+    if (int r = ring_copy((void*)soft, st.soft, ring_runs(st.n_soft, n, st.cap_soft), sizeof(double), hipMemcpyHostToDevice, c->stream)) return r;
+    st.n_soft += n;                                       // (the mirror stays valid: it is what the device holds after these copies)
     HIPCHK(hipMemcpyAsync(&c->d_streams[s].n_soft, &st.n_soft, sizeof st.n_soft, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));               // the symbols are the caller's again
     h.soft_tapped = true;
@@ -616,9 +623,7 @@ extern "C" long opv_tap_chunks(opv_ctx* c, int s, uint32_t first, double* out5, 
     if (st.n_chunks - first > st.cap_chunks || first < c->hs[s].chunk_floor) return fail(OPV_EINVAL, "chunk log entries already overwritten (ring)");
     uint32_t n = st.n_chunks - first;
     if (n > cap) n = (uint32_t)cap;
-    const RingRuns r = ring_runs(first, n, st.cap_chunks);
-    HIPCHK(hipMemcpy(out5, st.chunk_log + 5 * r.p0, sizeof(double) * 5 * r.run0, hipMemcpyDeviceToHost));
-    if (r.run1) HIPCHK(hipMemcpy(out5 + 5 * r.run0, st.chunk_log, sizeof(double) * 5 * r.run1, hipMemcpyDeviceToHost));
+    if (int r = ring_copy(out5, st.chunk_log, ring_runs(first, n, st.cap_chunks), 5 * sizeof(double), hipMemcpyDeviceToHost)) return r;
     return (long)n;
 }
 
@@ -646,10 +651,11 @@ extern "C" int opv_tap_wave_info(opv_ctx* c, int s, uint64_t out[4]) {
 extern "C" int opv_tap_occupancy(opv_ctx* c, int out[6]) {
     if (!c || !out) return fail(OPV_EINVAL, "null argument");
     HIPCHK(hipSetDevice(c->cfg.device));
-    const struct { const void* k; int threads; size_t lds; } ks[6] = {
-        {(const void*)k_msk_frontend_rb, 64, OPV_RB_LDS_I16}, {(const void*)k_msk_frontend_rb_wg4, 256, 0}, {(const void*)k_msk_frontend_x16_wg4, 256, 0},
-        {(const void*)k_msk_frontend_x4_wg4, 256, 0}, {(const void*)k_frame_decode, 64, 0}, {(const void*)k_frame_scale, 64, 0}};
-    for (int i = 0; i < 6; ++i) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[i], ks[i].k, ks[i].threads, ks[i].lds));
+    const FrontendKernel fe[4] = {FE_RB, FE_RB_WG4, FE_X16_WG4, FE_X4_WG4};       // (FE_RB: its 64-thread shape)
+    for (int i = 0; i < 4; ++i)
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[i], kFrontend[fe[i]].fn, kFrontendShape[fe[i]].threads, fe[i] == FE_RB ? OPV_RB_LDS_I16 : 0));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[4], (const void*)k_frame_decode, 64, 0));
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&out[5], (const void*)k_frame_scale, 64, 0));
     return OPV_OK;
 }
 

@@ -46,13 +46,7 @@ extern "C" __global__ void k_txb_scan(const OpvTxbEntry*, uint32_t, uint8_t*, ui
 extern "C" __global__ void k_txb_phases(const OpvTxbEntry*, uint32_t, uint32_t, const double2*, double2*);
 extern "C" __global__ void k_txb_modulate(const OpvTxbEntry*, uint32_t, const uint8_t*, const uint8_t*, const double2*, uint32_t*, OpvTxbAmb*, uint32_t, uint64_t, uint64_t, const uint8_t*);
 
-inline int fail(int code, const char* what, hipError_t e = hipSuccess) { return opv_int_fail(code, what, e); }   // sets opv_last_error, returns code
-
-#define HIPCHK(expr)                                              \
-    do {                                                          \
-        hipError_t _e = (expr);                                   \
-        if (_e != hipSuccess) return fail(OPV_EHIP, #expr, _e);   \
-    } while (0)
+inline int fail(int code, const char* what, hipError_t e = hipSuccess) { return opv_int_fail(code, what, e); }   // sets opv_last_error, returns code (HIPCHK: opv_wb_internal.h)
 
 // how a failed allocation is reported: OPV_EHIP with the runtime's text, or - where the caller gives `oom` - OPV_ENOMEM with that
 inline int alloc_failed(hipError_t e, const char* what, const char* oom) {
@@ -200,7 +194,7 @@ struct opv_ctx {
     GrowBuf<uint8_t> tx_flat;
     uint64_t tx_flat_lo = ~0ull, tx_flat_hi = ~0ull, tx_flat_have = 0;
     const char* last_frontend = "";   // kernel the last opv_process launched for the front-end (opv_frontend_kernel)
-    int frontend = 0;  // 0: by stream count, 1: one wave per stream, 4: four streams per wave, -1 / -2: see opv_set_frontend
+    int frontend = 0;  // opv_set_frontend: 0 = by stream count, else 1, 4 or 16 streams per wave (opv_round_rules.h: frontend_kernel)
     bool timing = false;
     bool timing_valid = false;
     hipEvent_t ev[8] = {};

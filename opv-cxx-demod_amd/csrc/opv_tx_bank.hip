@@ -72,16 +72,11 @@ extern "C" int opv_txb_create(opv_txb** out, opv_ctx* ctx, int n_streams) {
     b->stream = ctx->stream;
     b->st.assign((size_t)n_streams, opv_txb_state{0, 0, 0});
     b->h_state.resize(kStateHead + (size_t)n_streams);
-#define TXB_CHK(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) { opv_txb_destroy(b); return fail(OPV_EHIP, #expr, _e); }   \
-    } while (0)
-    TXB_CHK(hipSetDevice(door.device));
-    TXB_CHK(hipMalloc(&b->d_state, kStateHead + (size_t)n_streams));
-    TXB_CHK(hipMalloc(&b->d_amb, sizeof(OpvTxbAmb) * kAmbCap));
-    TXB_CHK(hipMemset(b->d_state, 0, kStateHead + (size_t)n_streams));
-#undef TXB_CHK
+    auto undo = [&](hipError_t e, const char* what) { opv_txb_destroy(b); return fail(OPV_EHIP, what, e); };
+    HIPCHK_OR(undo, hipSetDevice(door.device));
+    HIPCHK_OR(undo, hipMalloc(&b->d_state, kStateHead + (size_t)n_streams));
+    HIPCHK_OR(undo, hipMalloc(&b->d_amb, sizeof(OpvTxbAmb) * kAmbCap));
+    HIPCHK_OR(undo, hipMemset(b->d_state, 0, kStateHead + (size_t)n_streams));
     *out = b;
     return OPV_OK;
 }

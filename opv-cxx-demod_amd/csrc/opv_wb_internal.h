@@ -39,6 +39,18 @@ extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
 
 // ---- what the context offers (defined at the end of opv_push.hip; opv_int_fail in opv_capi.hip)
 int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code
+// a failed HIP call is OPV_EHIP with the call's text and the runtime's; the create paths first destroy the half-made object:
+// on_failure(error, text of the call) does that and says what to return
+#define HIPCHK_OR(on_failure, expr)                                  \
+    do {                                                             \
+        hipError_t _e = (expr);                                      \
+        if (_e != hipSuccess) return on_failure(_e, #expr);          \
+    } while (0)
+#define HIPCHK(expr)                                                      \
+    do {                                                                  \
+        hipError_t _e = (expr);                                           \
+        if (_e != hipSuccess) return opv_int_fail(OPV_EHIP, #expr, _e);   \
+    } while (0)
 // inc_k = (uint32) llrint(centre_hz[k] / (rate_factor x 2 168 000) x 2^32) for both banks, defined once (opv_wideband.hip, beside
 // opv_wb_lo_table, the one LO table); OPV_EINVAL for a centre that is not finite
 int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_hz, uint32_t* inc_out);

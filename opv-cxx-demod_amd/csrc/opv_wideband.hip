@@ -13,12 +13,6 @@
 #include "../../include/opv_demod.h"
 #include "opv_wb_internal.h"
 
-#define HIPCHK(expr)                                                      \
-    do {                                                                  \
-        hipError_t _e = (expr);                                           \
-        if (_e != hipSuccess) return opv_int_fail(OPV_EHIP, #expr, _e);   \
-    } while (0)
-
 namespace {
 
 constexpr double kWideRate = 2168000.0;
@@ -140,23 +134,18 @@ extern "C" int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, 
     opv_wb_lo_table(lo);
     std::vector<int> taps32((size_t)L);
     for (int t = 0; t < L; ++t) taps32[t] = taps[t];
-#define WB_CHK(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t _e = (expr);                                                                  \
-        if (_e != hipSuccess) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, #expr, _e); }   \
-    } while (0)
-    WB_CHK(hipSetDevice(door.device));
+    auto undo = [&](hipError_t e, const char* what) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, what, e); };
+    HIPCHK_OR(undo, hipSetDevice(door.device));
     const size_t hist_bytes = (size_t)(L > 1 ? L - 1 : 1) * 4;
-    WB_CHK(hipMalloc(&w->d_hist[0], hist_bytes));
-    WB_CHK(hipMalloc(&w->d_hist[1], hist_bytes));
-    WB_CHK(hipMalloc(&w->d_lo, sizeof lo));
-    WB_CHK(hipMalloc(&w->d_taps, (size_t)L * 4));
-    WB_CHK(hipMalloc(&w->d_inc, (size_t)K * 4));
-    WB_CHK(hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
-    WB_CHK(hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
-    WB_CHK(hipMemcpy(w->d_taps, taps32.data(), (size_t)L * 4, hipMemcpyHostToDevice));
-    WB_CHK(hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-#undef WB_CHK
+    HIPCHK_OR(undo, hipMalloc(&w->d_hist[0], hist_bytes));
+    HIPCHK_OR(undo, hipMalloc(&w->d_hist[1], hist_bytes));
+    HIPCHK_OR(undo, hipMalloc(&w->d_lo, sizeof lo));
+    HIPCHK_OR(undo, hipMalloc(&w->d_taps, (size_t)L * 4));
+    HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
+    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
+    HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_taps, taps32.data(), (size_t)L * 4, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
     w->streams.assign(streams, streams + K);
     for (int s : w->streams) door.shared->owned[s] = 1;
     *out = w;

@@ -79,26 +79,21 @@ extern "C" int opv_wbtx_create(opv_wbtx** out, opv_ctx* ctx, const opv_wbtx_cfg*
     w->J = (L - 1) / U + 1;
     int16_t lo[4096];
     opv_wb_lo_table(lo);
-#define WBTX_CHK(expr)                                                                       \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) { opv_wbtx_destroy(w); return fail(OPV_EHIP, #expr, _e); }     \
-    } while (0)
-    WBTX_CHK(hipSetDevice(door.device));
+    auto undo = [&](hipError_t e, const char* what) { opv_wbtx_destroy(w); return fail(OPV_EHIP, what, e); };
+    HIPCHK_OR(undo, hipSetDevice(door.device));
     const size_t hist_bytes = (size_t)K * (w->H ? w->H : 1) * 4;
     for (int i = 0; i < 2; ++i) {
-        WBTX_CHK(hipMalloc(&w->d_hist[i], hist_bytes));
-        WBTX_CHK(hipMemset(w->d_hist[i], 0, hist_bytes));                  // x[m] = 0 for m < 0: an empty history is a history of zeros
+        HIPCHK_OR(undo, hipMalloc(&w->d_hist[i], hist_bytes));
+        HIPCHK_OR(undo, hipMemset(w->d_hist[i], 0, hist_bytes));                  // x[m] = 0 for m < 0: an empty history is a history of zeros
     }
-    WBTX_CHK(hipMalloc(&w->d_lo, sizeof lo));
-    WBTX_CHK(hipMalloc(&w->d_taps, (size_t)L * 2));
-    WBTX_CHK(hipMalloc(&w->d_inc, (size_t)K * 4));
-    WBTX_CHK(hipMalloc(&w->d_tab, (size_t)K * sizeof(int*)));
-    WBTX_CHK(hipHostMalloc((void**)&w->h_tab, (size_t)K * sizeof(int*), hipHostMallocDefault));
-    WBTX_CHK(hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
-    WBTX_CHK(hipMemcpy(w->d_taps, taps, (size_t)L * 2, hipMemcpyHostToDevice));
-    WBTX_CHK(hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-#undef WBTX_CHK
+    HIPCHK_OR(undo, hipMalloc(&w->d_lo, sizeof lo));
+    HIPCHK_OR(undo, hipMalloc(&w->d_taps, (size_t)L * 2));
+    HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
+    HIPCHK_OR(undo, hipMalloc(&w->d_tab, (size_t)K * sizeof(int*)));
+    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)K * sizeof(int*), hipHostMallocDefault));
+    HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_taps, taps, (size_t)L * 2, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
     *out = w;
     return OPV_OK;
 }

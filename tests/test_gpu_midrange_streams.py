@@ -1,5 +1,5 @@
 """GPU: streaming contexts of 65 to 512 streams - the range k_msk_frontend_rb serves with two launch shapes under one name
-(csrc/opv_capi.hip, opv_process: 128 threads and an fp64 LDS ring a helper wave fills while the context has no more streams
+(csrc/opv_round_rules.h, frontend_choice: 128 threads and an fp64 LDS ring a helper wave fills while the context has no more streams
 than the device has CUs; 64 threads and the int16 ring beyond) - held to the ORACLE at length: every stream of every
 context, every soft symbol, the chunk carry, the tracker's lines, the estimate and the final state, with the bounds
 test_gpu_parity.check_stream / events_match already carry. No comparison here is against another mapping of the product.

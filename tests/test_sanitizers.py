@@ -312,3 +312,21 @@ def test_stream_rules_under_sanitizers(tmp_path):
     assert outs[0] == outs[1] and len(outs[0]) == 3, outs
     accepted, refused = int(outs[0][0]), int(outs[0][1])
     assert accepted >= 2 and refused > 1000, outs                             # (the good blob and pokes of unread fields pass; the rest is refused)
+
+
+def test_round_rules_under_sanitizers(tmp_path):
+    """csrc/opv_round_rules.h - the index arithmetic every opv_process launch is sized by (frame budget, grid refusal, the front-end's
+    kernel and grid for every stream count and forced mapping, tie passes, the scale pre-pass' and the decoder's grids) - as a
+    stand-alone program (tests/round_rules_probe.cpp, its own main) under ASan + UBSan: S = 1 .. 40 000 for every mode, and the
+    budget around every divisor and limit up to 2^64 - 1. The sanitized build reports nothing, finds every grid covering its
+    streams (exit 0) and prints the line of the unsanitized build of the same file."""
+    pkg = PKG / "csrc"
+    outs = []
+    for extra, exe in ((["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], tmp_path / "san"), ([], tmp_path / "plain")):
+        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-DPROBE_MAIN", "-I", str(pkg)] + extra +
+                       ["-o", str(exe), str(ROOT / "tests" / "round_rules_probe.cpp")], check=True)
+        p = run([str(exe)])
+        assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+        outs.append(p.stdout.decode().split())
+    assert outs[0] == outs[1] and len(outs[0]) == 2, outs
+    assert int(outs[0][0]) > 4 * 4 * 2 * 4 * 40000 * 4, outs                  # (four figures per front-end choice of the sweep alone)

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbr_plan / opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
+                               still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
                                still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
                                still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
                                still 7, additive: + opv_tap_push_soft, a parity tap that stages soft symbols for the tracker and the in-context decoder;
@@ -227,6 +228,40 @@ int opv_wb_push(opv_wb* wb, const int16_t* iq_wide, size_t n_wide);
 int opv_wb_push_async(opv_wb* wb, const int16_t* iq_wide, size_t n_wide);
 int opv_wb_push_device(opv_wb* wb, const int16_t* d_iq_wide, size_t n_wide);
 int opv_wb_flush(opv_wb* wb);
+/* ---- the front door at any radio rate: an exact rational resampler bank ----------------------------------------------------
+ * 2 168 000 = 2^6 x 5^3 x 271, so no common radio rate is an integer multiple of it (2.5 MS/s = 625/542, 4 MS/s = 500/271, 10 MS/s =
+ * 1250/271, 20 MS/s = 2500/271, 30.72 MS/s = 3840/271, 61.44 MS/s = 7680/271). opv_wb_create_rational makes an opv_wb whose wide
+ * rate is Fw = 2 168 000 x down / up S/s; it is an ordinary opv_wb: opv_wb_push / _async / _device, opv_wb_flush and opv_wb_destroy
+ * serve it, stream ownership, detachment and refusals are opv_wb_create's and opv_wb_push's (a refused push changes NOTHING), and
+ * its streams behave as any pushed stream. Same contract: integer-exact, held to a numpy int64 model with == (tests/
+ * test_gpu_wideband_rational.py), any split into pushes gives the same bytes. Write M = down, U = up, L = n_taps, J = ceil(L / U)
+ * the taps per phase, taps[t] = 0 for t >= L; wide samples x[n] = (I, Q) int16, n = 0 at the first sample pushed, a = first_sample + n:
+ *   increment: fw = (double)M x 2 168 000.0 / (double)U; inc_k = (uint32) llrint(centre_hz[k] / fw x 2^32), modulo 2^32 (these
+ *     double operations in this order; for U = 1 they are opv_wb_plan's for decim = M, bit for bit);
+ *   mix (the DDC's): phi = (uint32)(a x inc_k), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095] (opv_wb_lo_table),
+ *     mr = I c + Q s, mi = Q c - I s (int32);
+ *   resample (zero-stuff m by U, filter with taps at U x Fw, keep every M-th): for output r >= 0, n_r = floor(r M / U),
+ *     p_r = (r M) mod U, acc[r] = sum over j = 0 .. J - 1 of taps[p_r + j U] x m[n_r - j], m[n] = 0 for n < 0 (int64);
+ *   output count: output r exists once wide sample n_r has arrived: after N wide samples a channel has ceil(N U / M) outputs
+ *     (opv_wbr_outputs: no overflow for any uint64 N);
+ *   output value, per component: clamp(floor((acc + 2^(S-1)) / 2^S), -32768, 32767) (S = out_shift; S = 0: no rounding term), packed I | Q << 16;
+ *   state between pushes: the last J - 1 wide samples and N.
+ *   Limits (anything else is OPV_EINVAL, decided on the host by opv_wbr_plan): 1 <= up <= 1024, up <= down <= 32 x up,
+ *     gcd(down, up) = 1, 1 <= n_taps and J <= 1024, 1 <= n_channels <= 256, 0 <= out_shift <= 40, reserved = 0, finite centres, and
+ *     for EVERY phase p sum_j |taps[p + j U]| <= 2^21 (with |m| < 2^31: |acc| < 2^52, exact in int64).
+ *   With U = 1 every formula above is opv_wb_create's with decim = M: such an object (down <= 16) delivers the same bytes.
+ * opv_wbr_plan, opv_wbr_outputs (0 for a bad cfg): host only, no device. */
+typedef struct opv_wbr_cfg {
+    int32_t down, up;          /* M, U: wide rate = 2 168 000 x down / up */
+    int32_t n_channels;        /* K */
+    int32_t n_taps;            /* L, prototype filter at up x wide rate */
+    int32_t out_shift;         /* S */
+    int32_t reserved;          /* 0 */
+    uint64_t first_sample;
+} opv_wbr_cfg;                 /* 32 bytes */
+int opv_wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
+size_t opv_wbr_outputs(const opv_wbr_cfg* cfg, uint64_t n_wide_total);
+int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_cfg* cfg, const int* streams, const double* centre_hz, const int16_t* taps);
 /* EOF on a stream: enables the tail processing of :1088-1113 (streaming) or the single
  * whole-capture demodulate of :1166-1173 (batch) at the next opv_process. */
 int opv_flush(opv_ctx* ctx, int stream);

@@ -37,6 +37,29 @@ constexpr uint32_t OPV_WB_THREADS = 256;
 
 extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
 
+// Arguments of k_wbr_ddc (csrc/k_wideband_rational.hip), by value: the rational door, wide rate 2 168 000 x M / U. Output r of the
+// object reads wide samples n_r - j, j = 0 .. J - 1, with n_r = floor(r M / U), against row p_r = (r M) mod U of the phase-major
+// tap table. Output i of this push is r0 + i; the host hands over (n_r0, p_r0) and the device steps from there in 64 bits.
+struct OpvWbrArgs {
+    const int* src;          // as OpvWbArgs
+    const int* hist_in;      // the hist_len samples in front of src[0]
+    int* hist_out;           // the other carry buffer: the last min(n_before + n_new, J - 1) samples, written by block (0, 0)
+    const int16_t* lo;       // T[4096]
+    const int16_t* tab;      // tab[U][rowlen]: tab[p][j] = taps[p + j U], zero-padded; rows are 8-byte aligned
+    const uint32_t* inc;     // inc[K]
+    int* const* dst;         // dst[K]
+    uint64_t n_before;       // N before this push
+    uint32_t a0_lo;          // low 32 bits of first_sample + n_before
+    uint32_t n_new, hist_len, n_out;
+    uint32_t nrel0;          // n_r0 - n_before: index within src of the first output's newest sample (< n_new when n_out > 0)
+    uint32_t p0;             // p_r0
+    uint32_t M, U, J, K, S;
+    uint32_t rowlen;         // J rounded up to a multiple of 4
+    uint32_t tile;           // outputs per workgroup (<= 256): rowlen + floor(tile M / U) <= OPV_WB_SPAN
+    uint32_t kper;           // channels per blockIdx.y
+};
+extern "C" __global__ void k_wbr_ddc(OpvWbrArgs a);
+
 // ---- what the context offers (defined at the end of opv_push.hip; opv_int_fail in opv_capi.hip)
 int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code
 // a failed HIP call is OPV_EHIP with the call's text and the runtime's; the create paths first destroy the half-made object:

@@ -1,17 +1,24 @@
 // opv_wideband.hip — the host half of the wideband front door (include/opv_demod.h, opv_wb_*): plan and validation (host only),
 // the object that carries the last L - 1 wide samples and the count N from push to push, and the push itself: every channel's
 // output count is computed here, room is reserved in all K streams under push_enqueue's rules (opv_int_push_reserve) before
-// anything is launched, then ONE k_wb_ddc launch on the context's copy stream writes all K streams.
+// anything is launched, then ONE k_wb_ddc launch on the context's copy stream writes all K streams. An object is of one of two
+// kinds: the integer door (opv_wb_create: decim wide samples per output, k_wb_ddc) or the rational one (opv_wb_create_rational:
+// down / up wide samples per output, k_wbr_ddc; its rules are opv_wbr_rules.h). They differ in how a push's outputs are counted
+// and in the launch; staging, the destination-table ring, the reservation and the lifetime rules are the same code.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/opv_demod.h"
 #include "opv_wb_internal.h"
+#include "opv_wbr_rules.h"
+
+static_assert(kWbrSpan == OPV_WB_SPAN && kWbrMaxTile == OPV_WB_THREADS, "opv_wbr_rules.h sizes k_wbr_ddc's tile for this span");
 
 namespace {
 
@@ -51,17 +58,23 @@ int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_
     return OPV_OK;
 }
 
+enum class WbKind { Integer, Rational };
+
 struct opv_wb {
     opv_ctx* ctx = nullptr;
-    opv_wb_cfg cfg{};
+    WbKind kind = WbKind::Integer;
+    opv_wb_cfg cfg{};                    // Integer
+    opv_wbr_cfg rcfg{};                  // Rational
+    uint32_t K = 0;
+    uint32_t carry = 0;                  // wide samples carried from push to push: L - 1 (Integer), J - 1 (Rational)
     OpvCtxDoor door{};
     std::vector<int> streams;
     uint64_t n_total = 0;                // N: wide samples pushed so far
-    uint32_t hist_len = 0;               // min(N, L - 1)
+    uint32_t hist_len = 0;               // min(N, carry)
     int cur = 0;                         // which carry buffer holds the history
     int* d_hist[2] = {nullptr, nullptr};
     int16_t* d_lo = nullptr;
-    int* d_taps = nullptr;
+    void* d_taps = nullptr;              // Integer: h[L] widened to int32; Rational: the phase-major int16 table
     uint32_t* d_inc = nullptr;
     int* d_stage = nullptr;              // pageable sources: the block is copied here first (grow-only)
     size_t stage_cap = 0;
@@ -70,6 +83,59 @@ struct opv_wb {
     unsigned pushes = 0;
     uint32_t tile = 0, lpad = 0, rowlen = 0;
 };
+
+namespace {
+
+// What both kinds of object are made of: the checks of the K streams, the object, its device memory and the uploads. `taps` is
+// the kind's own tap table (taps_bytes of it), w_init sets the kind's fields before anything is allocated.
+template <class Init>
+int make_object(opv_wb** out, opv_ctx* ctx, const char* who, int K, uint32_t carry, const int* streams, const uint32_t* inc,
+                const void* taps, size_t taps_bytes, Init w_init) {
+    auto fail = [&](const char* what) {
+        char text[160];
+        snprintf(text, sizeof text, "%s: %s", who, what);
+        return opv_int_fail(OPV_EINVAL, text);
+    };
+    OpvCtxDoor door;
+    if (int r = opv_int_door(ctx, &door)) return r;
+    {
+        std::vector<char> seen((size_t)door.n_streams, 0);
+        for (int k = 0; k < K; ++k) {
+            const int s = streams[k];
+            if (s < 0 || s >= door.n_streams) return fail("stream index out of range");
+            if (seen[s]) return fail("a stream is named twice");
+            if (door.shared->owned[s]) return fail("a stream is already fed by another wideband object");
+            seen[s] = 1;
+        }
+    }
+    opv_wb* w = new (std::nothrow) opv_wb;
+    if (!w) return opv_int_fail(OPV_ENOMEM, who);
+    w->ctx = ctx;
+    w->door = door;
+    w->K = (uint32_t)K;
+    w->carry = carry;
+    w_init(w);
+    int16_t lo[4096];
+    opv_wb_lo_table(lo);
+    auto undo = [&](hipError_t e, const char* what) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, what, e); };
+    HIPCHK_OR(undo, hipSetDevice(door.device));
+    const size_t hist_bytes = (size_t)(carry ? carry : 1) * 4;
+    HIPCHK_OR(undo, hipMalloc(&w->d_hist[0], hist_bytes));
+    HIPCHK_OR(undo, hipMalloc(&w->d_hist[1], hist_bytes));
+    HIPCHK_OR(undo, hipMalloc(&w->d_lo, sizeof lo));
+    HIPCHK_OR(undo, hipMalloc(&w->d_taps, taps_bytes));
+    HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
+    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
+    HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_taps, taps, taps_bytes, hipMemcpyHostToDevice));
+    HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc, (size_t)K * 4, hipMemcpyHostToDevice));
+    w->streams.assign(streams, streams + K);
+    for (int s : w->streams) door.shared->owned[s] = 1;
+    *out = w;
+    return OPV_OK;
+}
+
+}  // namespace
 
 extern "C" void opv_wb_lo_table(int16_t out4096[4096]) {
     if (!out4096) return;
@@ -108,48 +174,47 @@ extern "C" int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, 
     if (!ctx || !streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create: null pointer");
     std::vector<uint32_t> inc(256);
     if (int r = plan(cfg, centre_hz, taps, inc.data())) return r;
-    OpvCtxDoor door;
-    if (int r = opv_int_door(ctx, &door)) return r;
     const int K = cfg->n_channels, L = cfg->n_taps, D = cfg->decim;
-    {
-        std::vector<char> seen((size_t)door.n_streams, 0);
-        for (int k = 0; k < K; ++k) {
-            const int s = streams[k];
-            if (s < 0 || s >= door.n_streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create: stream index out of range");
-            if (seen[s]) return opv_int_fail(OPV_EINVAL, "opv_wb_create: a stream is named twice");
-            if (door.shared->owned[s]) return opv_int_fail(OPV_EINVAL, "opv_wb_create: a stream is already fed by another wideband object");
-            seen[s] = 1;
-        }
-    }
-    opv_wb* w = new (std::nothrow) opv_wb;
-    if (!w) return opv_int_fail(OPV_ENOMEM, "opv_wb_create");
-    w->ctx = ctx;
-    w->cfg = *cfg;
-    w->door = door;
-    w->lpad = (uint32_t)((L - 1 + D - 1) / D * D);
-    w->tile = (OPV_WB_SPAN - w->lpad) / (uint32_t)D;
-    if (w->tile > OPV_WB_THREADS) w->tile = OPV_WB_THREADS;
-    w->rowlen = w->tile + w->lpad / (uint32_t)D;                        // D * rowlen = tile * D + lpad <= OPV_WB_SPAN
-    int16_t lo[4096];
-    opv_wb_lo_table(lo);
     std::vector<int> taps32((size_t)L);
     for (int t = 0; t < L; ++t) taps32[t] = taps[t];
-    auto undo = [&](hipError_t e, const char* what) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, what, e); };
-    HIPCHK_OR(undo, hipSetDevice(door.device));
-    const size_t hist_bytes = (size_t)(L > 1 ? L - 1 : 1) * 4;
-    HIPCHK_OR(undo, hipMalloc(&w->d_hist[0], hist_bytes));
-    HIPCHK_OR(undo, hipMalloc(&w->d_hist[1], hist_bytes));
-    HIPCHK_OR(undo, hipMalloc(&w->d_lo, sizeof lo));
-    HIPCHK_OR(undo, hipMalloc(&w->d_taps, (size_t)L * 4));
-    HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
-    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
-    HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
-    HIPCHK_OR(undo, hipMemcpy(w->d_taps, taps32.data(), (size_t)L * 4, hipMemcpyHostToDevice));
-    HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc.data(), (size_t)K * 4, hipMemcpyHostToDevice));
-    w->streams.assign(streams, streams + K);
-    for (int s : w->streams) door.shared->owned[s] = 1;
-    *out = w;
+    return make_object(out, ctx, "opv_wb_create", K, (uint32_t)(L - 1), streams, inc.data(), taps32.data(), (size_t)L * 4, [&](opv_wb* w) {
+        w->kind = WbKind::Integer;
+        w->cfg = *cfg;
+        w->lpad = (uint32_t)((L - 1 + D - 1) / D * D);
+        w->tile = (OPV_WB_SPAN - w->lpad) / (uint32_t)D;
+        if (w->tile > OPV_WB_THREADS) w->tile = OPV_WB_THREADS;
+        w->rowlen = w->tile + w->lpad / (uint32_t)D;                    // D * rowlen = tile * D + lpad <= OPV_WB_SPAN
+    });
+}
+
+// ---- the rational door: the plan's rules are opv_wbr_rules.cpp's
+extern "C" int opv_wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
+    const char* why = nullptr;
+    if (int r = wbr_plan(cfg, centre_hz, taps, inc_out, &why)) return opv_int_fail(r, why);
     return OPV_OK;
+}
+
+extern "C" size_t opv_wbr_outputs(const opv_wbr_cfg* cfg, uint64_t n_wide_total) {
+    if (wbr_cfg_refusal(cfg)) return 0;
+    return (size_t)wbr_outputs((uint32_t)cfg->down, (uint32_t)cfg->up, n_wide_total);
+}
+
+extern "C" int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_cfg* cfg, const int* streams, const double* centre_hz,
+                                      const int16_t* taps) {
+    if (!out) return opv_int_fail(OPV_EINVAL, "opv_wb_create_rational: null out");
+    *out = nullptr;
+    if (!ctx || !streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create_rational: null pointer");
+    std::vector<uint32_t> inc(256);
+    if (int r = opv_wbr_plan(cfg, centre_hz, taps, inc.data())) return r;
+    const uint32_t J = wbr_taps_per_phase(*cfg), rowlen = wbr_row_len(*cfg);
+    std::vector<int16_t> tab((size_t)cfg->up * rowlen);
+    wbr_phase_table(*cfg, taps, tab.data());
+    return make_object(out, ctx, "opv_wb_create_rational", cfg->n_channels, J - 1, streams, inc.data(), tab.data(), tab.size() * 2, [&](opv_wb* w) {
+        w->kind = WbKind::Rational;
+        w->rcfg = *cfg;
+        w->rowlen = rowlen;
+        w->tile = wbr_tile((uint32_t)cfg->down, (uint32_t)cfg->up, rowlen);
+    });
 }
 
 namespace {
@@ -164,8 +229,21 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     if (!iq) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null IQ pointer");
     if (((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_wb_push: IQ pointer must be 4-byte aligned");
     if (n_new >= (1ull << 31)) return opv_int_fail(OPV_EINVAL, "opv_wb_push: more than 2^31 - 1 samples in one push");
-    const uint32_t K = (uint32_t)w->cfg.n_channels, D = (uint32_t)w->cfg.decim, L = (uint32_t)w->cfg.n_taps;
-    const uint64_t r0 = (w->n_total + D - 1) / D, r1 = (w->n_total + n_new + D - 1) / D;
+    const uint32_t K = w->K;
+    const bool rational = w->kind == WbKind::Rational;
+    // ---- the push's outputs [r0, r1) by the kind's rule: ceil(N / D), or ceil(N U / M) with where output r0 sits (opv_wbr_rules.h)
+    WbrFirst first{};
+    uint64_t r0, r1;
+    if (rational) {
+        const uint32_t M = (uint32_t)w->rcfg.down, U = (uint32_t)w->rcfg.up;
+        first = wbr_first_output(M, U, w->n_total);
+        r0 = first.r0;
+        r1 = wbr_outputs(M, U, w->n_total + n_new);
+    } else {
+        const uint32_t D = (uint32_t)w->cfg.decim;
+        r0 = (w->n_total + D - 1) / D;
+        r1 = (w->n_total + n_new + D - 1) / D;
+    }
     const uint32_t n_out = (uint32_t)(r1 - r0);
     // ---- the source as the device sees it
     const int* src = nullptr;
@@ -203,35 +281,57 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     std::memcpy(tab, dst.data(), (size_t)K * sizeof(int*));
     void* d_tab = nullptr;
     HIPCHK(hipHostGetDevicePointer(&d_tab, tab, 0));
-    OpvWbArgs a{};
-    a.src = src;
-    a.hist_in = w->d_hist[w->cur];
-    a.hist_out = w->d_hist[w->cur ^ 1];
-    a.lo = w->d_lo;
-    a.taps = w->d_taps;
-    a.inc = w->d_inc;
-    a.dst = (int* const*)d_tab;
-    a.n_before = w->n_total;
-    a.r0 = r0;
-    a.a0_lo = (uint32_t)(w->cfg.first_sample + w->n_total);
-    a.n_new = (uint32_t)n_new;
-    a.hist_len = w->hist_len;
-    a.n_out = n_out;
-    a.D = D; a.L = L; a.K = K; a.S = (uint32_t)w->cfg.out_shift;
-    a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen;
-    // few output tiles (a short push, a large D): the channels are shared out over blockIdx.y so that the device still fills
+    // few output tiles (a short push, a large ratio): the channels are shared out over blockIdx.y so that the device still fills
     const uint32_t tiles = n_out ? (n_out + w->tile - 1) / w->tile : 1;
     uint32_t ky = tiles >= 512 ? 1 : (512 + tiles - 1) / tiles;
     if (ky > K) ky = K;
-    a.kper = (K + ky - 1) / ky;
-    ky = (K + a.kper - 1) / a.kper;
-    k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+    const uint32_t kper = (K + ky - 1) / ky;
+    ky = (K + kper - 1) / kper;
+    const uint32_t a0_lo = (uint32_t)((rational ? w->rcfg.first_sample : w->cfg.first_sample) + w->n_total);
+    if (rational) {
+        OpvWbrArgs a{};
+        a.src = src;
+        a.hist_in = w->d_hist[w->cur];
+        a.hist_out = w->d_hist[w->cur ^ 1];
+        a.lo = w->d_lo;
+        a.tab = (const int16_t*)w->d_taps;
+        a.inc = w->d_inc;
+        a.dst = (int* const*)d_tab;
+        a.n_before = w->n_total;
+        a.a0_lo = a0_lo;
+        a.n_new = (uint32_t)n_new;
+        a.hist_len = w->hist_len;
+        a.n_out = n_out;
+        a.nrel0 = (uint32_t)first.n_rel;                                // (< n_new whenever n_out > 0; not read otherwise)
+        a.p0 = first.phase;
+        a.M = (uint32_t)w->rcfg.down; a.U = (uint32_t)w->rcfg.up; a.J = w->carry + 1; a.K = K; a.S = (uint32_t)w->rcfg.out_shift;
+        a.rowlen = w->rowlen; a.tile = w->tile; a.kper = kper;
+        k_wbr_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+    } else {
+        OpvWbArgs a{};
+        a.src = src;
+        a.hist_in = w->d_hist[w->cur];
+        a.hist_out = w->d_hist[w->cur ^ 1];
+        a.lo = w->d_lo;
+        a.taps = (const int*)w->d_taps;
+        a.inc = w->d_inc;
+        a.dst = (int* const*)d_tab;
+        a.n_before = w->n_total;
+        a.r0 = r0;
+        a.a0_lo = a0_lo;
+        a.n_new = (uint32_t)n_new;
+        a.hist_len = w->hist_len;
+        a.n_out = n_out;
+        a.D = (uint32_t)w->cfg.decim; a.L = (uint32_t)w->cfg.n_taps; a.K = K; a.S = (uint32_t)w->cfg.out_shift;
+        a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen; a.kper = kper;
+        k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(w->tab_ev[slot], w->door.copy_stream));
     ++w->pushes;
     w->cur ^= 1;
     w->n_total += n_new;
-    w->hist_len = w->n_total < (uint64_t)(L - 1) ? (uint32_t)w->n_total : L - 1;
+    w->hist_len = w->n_total < (uint64_t)w->carry ? (uint32_t)w->n_total : w->carry;
     return opv_int_push_end(w->ctx, wait);
 }
 

@@ -37,6 +37,7 @@ EXPORTS = [
     "opv_tx_modulate", "opv_tap_tx_checkpoints", "opv_frontend_kernel", "opv_channel_device", "opv_resample_device", "opv_enable_timing", "opv_kernel_times", "opv_tx_modulate_device", "opv_tx_modulate_device_to_host",
     "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
     "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
+    "opv_wbr_plan", "opv_wbr_outputs", "opv_wb_create_rational",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
     "opv_tap_push_soft",
     "opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads",
@@ -59,6 +60,11 @@ class Cfg(C.Structure):
 class WbCfg(C.Structure):
     _fields_ = [("decim", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("first_sample", C.c_uint64)]
+
+
+class WbrCfg(C.Structure):
+    _fields_ = [("down", C.c_int32), ("up", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
+                ("reserved", C.c_int32), ("first_sample", C.c_uint64)]
 
 
 class WbtxCfg(C.Structure):
@@ -228,6 +234,10 @@ def lib():
         L.opv_wb_push_async.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.opv_wb_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.opv_wb_flush.argtypes = [C.c_void_p]
+        L.opv_wbr_plan.argtypes = [C.POINTER(WbrCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wbr_outputs.restype = C.c_size_t
+        L.opv_wbr_outputs.argtypes = [C.POINTER(WbrCfg), C.c_uint64]
+        L.opv_wb_create_rational.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbrCfg), C.c_void_p, C.c_void_p, C.c_void_p]
         L.opv_tap_iq.restype = C.c_long
         L.opv_tap_iq.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_size_t]
         L.opv_enable_link_report.argtypes = [C.c_void_p, C.c_int]
@@ -491,6 +501,27 @@ def wb_outputs(decim, n_wide_total):
     return int(lib().opv_wb_outputs(C.byref(cfg), int(n_wide_total)))
 
 
+def _wbr_args(down, up, centre_hz, taps, out_shift, first_sample):
+    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
+    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
+    return WbrCfg(int(down), int(up), centre.size, taps.size, int(out_shift), 0, int(first_sample)), centre, taps
+
+
+def wbr_plan(down, up, centre_hz, taps, out_shift, first_sample=0):
+    """opv_wbr_plan: validates a plan of the rational door (wide rate 2 168 000 x down / up) and returns its K phase increments
+    (uint32); host only, needs no device"""
+    cfg, centre, taps = _wbr_args(down, up, centre_hz, taps, out_shift, first_sample)
+    inc = np.zeros(max(centre.size, 1), np.uint32)
+    _chk(lib().opv_wbr_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
+    return inc[:centre.size]
+
+
+def wbr_outputs(down, up, n_wide_total):
+    """opv_wbr_outputs: outputs per channel after n_wide_total wide samples, ceil(N up / down)"""
+    cfg = WbrCfg(int(down), int(up), 1, 1, 0, 0, 0)
+    return int(lib().opv_wbr_outputs(C.byref(cfg), int(n_wide_total)))
+
+
 class Wideband:
     """A bank of DDCs on the device that feeds streams[k] of `demod` with the channel at centre_hz[k] of one wide capture
     (opv_wb_*, include/opv_demod.h). Close it before its Demod."""
@@ -505,6 +536,22 @@ class Wideband:
         _chk(lib().opv_wb_create(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
         self._inflight = []
         demod._wideband.add(self)
+
+    @classmethod
+    def rational(cls, demod, down, up, streams, centre_hz, taps, out_shift, first_sample=0):
+        """opv_wb_create_rational: the same object for a capture at 2 168 000 x down / up S/s (10 MS/s is 1250 / 271); `taps` is the
+        prototype filter at up x that rate. push / push_async / push_device / flush / close are the ones above."""
+        self = cls.__new__(cls)
+        self.demod = demod
+        self.cfg, centre, taps = _wbr_args(down, up, centre_hz, taps, out_shift, first_sample)
+        ids = (C.c_int * len(streams))(*[int(s) for s in streams])
+        if len(streams) != centre.size:
+            raise OpvError("Wideband.rational: one centre frequency per stream")
+        self.h = C.c_void_p()
+        _chk(lib().opv_wb_create_rational(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
+        self._inflight = []
+        demod._wideband.add(self)
+        return self
 
     def push(self, iq_wide):
         iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)

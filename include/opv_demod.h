@@ -89,7 +89,8 @@ typedef struct opv_cfg {
 } opv_cfg;
 
 /* Per decoded frame: what main() knows when it prints/writes a frame
- * (src/opv-demod.cpp:1048-1062: metric, res.sync_quality, sym index of release). */
+ * (src/opv-demod.cpp:1048-1062: metric, res.sync_quality, sym index of release). The two symbol indices are absolute and
+ * 64-bit (see "Long-lived streams" at opv_stream_state). */
 typedef struct opv_frame_meta {
     int32_t viterbi_metric;   /* ViterbiDecoder::decode return (:845); 0 == "perfect" (:910) */
     int32_t sync_ok;          /* 1: the sync word in front of this payload passed its check (HUNTING hit :642, or
@@ -107,7 +108,17 @@ typedef struct opv_event {
     double raw;               /* raw correlation (HUNT_TO_VERIFY line) */
 } opv_event;
 
-/* What the status / summary lines of main() read (src/opv-demod.cpp:1080-1082,1117-1120). */
+/* What the status / summary lines of main() read (src/opv-demod.cpp:1080-1082,1117-1120).
+ *
+ * Long-lived streams. Every SYMBOL index (total_symbols; opv_frame_meta.release_symbol / payload_symbol; opv_event.sym_idx;
+ * the `first` of opv_tap_soft) and every SAMPLE index (total_samples, chunk_origin, the `first` of opv_tap_iq) is absolute and
+ * 64-bit. At 2 168 000 S/s the sample count passes 2^31 after 16.5 minutes and 2^32 after 33, the symbol count after 11 and 22
+ * hours; across both, and beyond 2^40, a stream is held to the oracle on every stream-to-wave mapping, with the boundary inside a
+ * demodulate() call, a payload, the tracker's 24-symbol window (LOCKED and HUNTING), a flywheel frame, a silence gap and a
+ * compaction (tests/test_gpu_far_positions.py). The frame, event and chunk COUNTS (frames_released, frames_decoded,
+ * frames_perfect, n_chunks, events_dropped, and the cursors behind opv_pop_frames / opv_pop_events / opv_tap_chunks) are 32-bit:
+ * at one frame and one demodulate() call per 40 ms, 2^31 is reached after 2.7 years of uninterrupted reception (a LOCKED stream
+ * logs one event per frame: the same); no test takes a stream across their wrap. */
 typedef struct opv_stream_state {
     double freq_offset_hz;    /* MSKDemodulatorAFC::get_freq_offset (:331) */
     double timing_freq;       /* get_timing_freq (:332) */

@@ -1,7 +1,8 @@
 // stream_rules_probe.cpp — test support for csrc/opv_stream_rules.{h,cpp} (plain C++, no GPU): a C face for ctypes
 // (tests/test_stream_rules_host.py) and, with -DPROBE_MAIN, a stand-alone program that runs the same blobs and grids through
 // parse_blob, ring_runs, the segment table and the launch shape and prints one line (tests/test_sanitizers.py builds it with and
-// without sanitizers and compares the lines).
+// without sanitizers and compares the lines). probe_blob_shift moves a blob's absolute indices forward: how
+// tests/test_gpu_far_positions.py takes a live stream across symbol and sample 2^32.
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
@@ -45,13 +46,57 @@ long probe_offset(const char* name) {
     H(magic) H(version) H(sizeof_stream) H(sizeof_header) H(sizeof_entry) H(count) H(total_bytes) H(payload_off) H(payload_bytes)
     E(off) E(len) E(seg_off) E(seg_n) E(soft_first) E(events_first) E(chunks_first) E(popped) E(events_popped) E(last_round_avail)
     S(n_avail) S(origin) S(overflow) S(n_soft) S(cap_soft) S(trk_next) S(trk_anchor) S(trk_state) S(n_frames) S(n_events) S(n_chunks) S(iq_base)
+    S(total_samples) S(fo_sum)
 #undef H
 #undef E
 #undef S
+    if (n == "frec.payload_sym") return (long)offsetof(OpvFrameRec, payload_sym);
+    if (n == "frec.release_sym") return (long)offsetof(OpvFrameRec, release_sym);
+    if (n == "event.sym_idx") return (long)offsetof(OpvEventRec, sym_idx);
+    if (n.size() == 9 && n.compare(0, 8, "segelem.") == 0 && n[8] >= '0' && n[8] < '0' + SEG_N) return (long)kSegElem[n[8] - '0'];   // bytes per element of segment k
+    if (n == "sizeof.frec") return (long)sizeof(OpvFrameRec);
+    if (n == "sizeof.event") return (long)sizeof(OpvEventRec);
     if (n == "sizeof.header") return (long)sizeof(BlobHeader);
     if (n == "sizeof.entry") return (long)sizeof(BlobEntry);
     if (n == "sizeof.stream") return (long)sizeof(OpvStream);
     return -1;
+}
+// A stream moved to a far position: every absolute SYMBOL index of every entry of the blob (n_soft, the tracker's anchor and next,
+// soft_first, payload_sym / release_sym of the carried frame records, sym_idx of the carried events) forward by d_sym, every absolute
+// SAMPLE index (total_samples, iq_base) by d_samp, in place. origin, n_avail and last_round_avail are relative to the IQ tail, fo_sum
+// is the LO's phase and the 32-bit frame / event / chunk counters wrap years away: all left alone. Returns 0 if the blob passed
+// parse_blob before and after; non-zero, with the bytes as they were, if it did not, if a shift is no multiple of 4 (silence_pd
+// reads ksym & 3, soft_first stays even, the IQ tail stays 16-byte aligned) or if an entry has n_soft < 24 or trk_next < 23 (its
+// hunt has not reached symbol 23 yet and would start at another symbol after the shift: not the same run).
+int probe_blob_shift(void* blob, size_t bytes, uint64_t d_sym, uint64_t d_samp) {
+    BlobHeader h;
+    std::vector<BlobEntry> ents;
+    if (parse_blob(blob, bytes, &h, &ents)) return 1;
+    if ((d_sym & 3u) || (d_samp & 3u)) return 2;
+    for (const BlobEntry& e : ents)
+        if (e.st.n_soft < 24 || e.st.trk_next < 23) return 3;
+    std::vector<char> b((const char*)blob, (const char*)blob + h.total_bytes);
+    auto add = [&](uint64_t at, uint64_t d) {               // (the caller's bytes may sit at any alignment)
+        uint64_t v;
+        std::memcpy(&v, b.data() + at, 8);
+        v += d;
+        std::memcpy(b.data() + at, &v, 8);
+    };
+    for (size_t i = 0; i < ents.size(); ++i) {
+        BlobEntry& e = ents[i];
+        e.st.n_soft += d_sym; e.st.trk_anchor += d_sym; e.st.trk_next += d_sym; e.soft_first += d_sym;
+        e.st.total_samples += d_samp; e.st.iq_base += d_samp;
+        std::memcpy(b.data() + sizeof(BlobHeader) + i * sizeof(BlobEntry), &e, sizeof e);
+        const uint64_t at = h.payload_off + e.off;
+        for (uint64_t k = 0; k < e.seg_n[SEG_FREC]; ++k) {
+            add(at + e.seg_off[SEG_FREC] + k * sizeof(OpvFrameRec) + offsetof(OpvFrameRec, payload_sym), d_sym);
+            add(at + e.seg_off[SEG_FREC] + k * sizeof(OpvFrameRec) + offsetof(OpvFrameRec, release_sym), d_sym);
+        }
+        for (uint64_t k = 0; k < e.seg_n[SEG_EVENTS]; ++k) add(at + e.seg_off[SEG_EVENTS] + k * sizeof(OpvEventRec) + offsetof(OpvEventRec, sym_idx), d_sym);
+    }
+    if (parse_blob(b.data(), b.size(), &h, &ents)) return 4;
+    std::memcpy(blob, b.data(), b.size());
+    return 0;
 }
 uint64_t probe_blob_payload_off(int count) { return blob_payload_off(count); }
 uint64_t probe_blob_magic(void) { return kBlobMagic; }
@@ -108,9 +153,64 @@ static std::vector<char> base_blob() {
     return b;
 }
 
+// a valid blob of two streams past symbol 24, each with a soft tail of 40 symbols, two unpopped frame records and three events
+static std::vector<char> live_blob() {
+    const uint64_t n[SEG_N] = {0, 40, 2, 2, 2, 2, 3, 0};
+    uint64_t off[SEG_N], len = 0;
+    for (int k = 0; k < SEG_N; ++k) { off[k] = len; len += up16(n[k] * kSegElem[k]); }
+    BlobHeader h;
+    std::memset(&h, 0, sizeof h);
+    h.magic = kBlobMagic; h.version = kBlobVersion; h.sizeof_stream = sizeof(OpvStream); h.sizeof_header = sizeof(BlobHeader); h.sizeof_entry = sizeof(BlobEntry);
+    h.streaming = 1; h.count = 2; h.payload_off = blob_payload_off(2); h.payload_bytes = 2 * len; h.total_bytes = h.payload_off + h.payload_bytes;
+    std::vector<char> b((size_t)h.total_bytes, 0);
+    std::memcpy(b.data(), &h, sizeof h);
+    for (int i = 0; i < 2; ++i) {
+        BlobEntry e;
+        std::memset(&e, 0, sizeof e);
+        e.off = len * i; e.len = len;
+        for (int k = 0; k < SEG_N; ++k) { e.seg_off[k] = off[k]; e.seg_n[k] = n[k]; }
+        e.st.n_soft = 5000 + 2 * i; e.st.trk_next = e.st.n_soft; e.st.trk_anchor = 4990; e.st.trk_state = i ? OPV_LOCKED : OPV_HUNTING; e.st.cap_soft = 4096;
+        e.soft_first = e.st.n_soft - 40;
+        e.popped = 3u * i; e.st.n_frames = e.popped + 2; e.events_first = e.events_popped = 5u * i; e.st.n_events = e.events_first + 3;
+        e.st.total_samples = 200000; e.st.iq_base = 1000u * i;
+        std::memcpy(b.data() + sizeof h + sizeof e * i, &e, sizeof e);
+        for (uint64_t k = 0; k < 2; ++k) {
+            const OpvFrameRec r = {2800 + 2168 * k, 4944 + 2168 * k, 0.9, 1, 0};
+            std::memcpy(b.data() + h.payload_off + e.off + off[SEG_FREC] + k * sizeof r, &r, sizeof r);
+        }
+        for (uint64_t k = 0; k < 3; ++k) {
+            const OpvEventRec r = {(int32_t)(1 + k), 0, 23 + 2168 * k, 0.8, 1.0};
+            std::memcpy(b.data() + h.payload_off + e.off + off[SEG_EVENTS] + k * sizeof r, &r, sizeof r);
+        }
+    }
+    return b;
+}
+
 int main() {
     unsigned long long acc = 0;
     auto mix = [&](unsigned long long v) { acc = acc * 1000003ull + v; };
+    // the far-position shift (probe_blob_shift): taken with its multiples of 4, each in an allocation of exactly the blob's length;
+    // refused - the bytes untouched - for the other shifts, for a truncated blob and for the base blob's streams below symbol 24
+    {
+        const std::vector<char> live = live_blob();
+        for (uint64_t d : {(uint64_t)0, (uint64_t)4, (uint64_t)1 << 31, ((uint64_t)1 << 32) - 4, ((uint64_t)1 << 40) + 8}) {
+            std::vector<char> b = live;
+            if (probe_blob_shift(b.data(), b.size(), d, d + 4) != 0) return 5;
+            BlobHeader h;
+            std::vector<BlobEntry> ents;
+            if (parse_blob(b.data(), b.size(), &h, &ents) || ents[1].st.n_soft != 5002 + d || ents[1].st.iq_base != 1000 + d + 4) return 6;
+            uint64_t v;
+            std::memcpy(&v, b.data() + h.payload_off + ents[1].off + ents[1].seg_off[SEG_EVENTS] + 2 * sizeof(OpvEventRec) + offsetof(OpvEventRec, sym_idx), 8);
+            if (v != 23 + 2 * 2168 + d) return 7;
+            mix(ents[0].soft_first); mix(ents[1].st.trk_anchor); mix(ents[0].st.total_samples);
+        }
+        for (uint64_t d : {(uint64_t)1, (uint64_t)2, (uint64_t)6}) {
+            std::vector<char> b = live;
+            if (probe_blob_shift(b.data(), b.size(), d, 0) == 0 || probe_blob_shift(b.data(), b.size(), 0, d) == 0 || b != live) return 8;
+        }
+        std::vector<char> cut(live.begin(), live.end() - 8), low = base_blob(), low0 = low;
+        if (probe_blob_shift(cut.data(), cut.size(), 4, 4) == 0 || probe_blob_shift(low.data(), low.size(), 4, 4) == 0 || low != low0) return 9;
+    }
     // blobs: the base, every prefix length that matters, every byte of the header and of the first entry's index fields poked
     const std::vector<char> good = base_blob();
     uint32_t count = 0;

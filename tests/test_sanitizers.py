@@ -299,8 +299,10 @@ def test_stream_rules_under_sanitizers(tmp_path):
     """csrc/opv_stream_rules.{h,cpp} - the host code that reads a caller's bytes (parse_blob: an imported stream blob) and all the
     index arithmetic of rings, segment tables and launch shapes - as a stand-alone program (tests/stream_rules_probe.cpp, its own
     main) under ASan + UBSan: a valid blob, every prefix of it in an allocation of exactly that length, every header and index
-    byte poked, rings around the wrap, the segment moves of an export and of imports into smaller rings. The sanitized build
-    reports nothing and prints the line of the unsanitized build of the same files."""
+    byte poked, rings around the wrap, the segment moves of an export and of imports into smaller rings, and the far-position
+    shift of a blob with frame records and events (probe_blob_shift: by 0, 4, 2^31, 2^32 - 4 and 2^40 + 8, and each of its
+    refusals with the bytes compared; a wrong result is an exit status of its own). The sanitized build reports nothing and
+    prints the line of the unsanitized build of the same files."""
     pkg = PKG / "csrc"
     outs = []
     for extra, exe in ((["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], tmp_path / "san"), ([], tmp_path / "plain")):

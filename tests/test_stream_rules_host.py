@@ -1,6 +1,7 @@
 """CPU-only: csrc/opv_stream_rules.{h,cpp} - the rules that keep a stream's device buffers consistent (what compaction keeps and
 its re-base, the runs of a ring, the launch shape of the table-driven kernels, the migration blob's checks) - compiled with g++
-into a shared object (tests/stream_rules_probe.cpp gives it a C face) and called through ctypes. Every check is exact."""
+into a shared object (tests/stream_rules_probe.cpp gives it a C face) and called through ctypes; and that file's own
+probe_blob_shift, the far-position shift of a blob that tests/test_gpu_far_positions.py relies on. Every check is exact."""
 import ctypes
 import struct
 import subprocess
@@ -210,3 +211,104 @@ def test_parse_blob_accepts_a_consistent_blob_and_refuses_each_mutation_with_its
     assert why(rules, good.copy().put("e.last_round_avail", 1, "Q", 0).b)[0] == CONTRADICT
     # without the directory (opv_blob_streams) only the header is judged
     assert why(rules, good.copy().put("e.popped", 2, "I", 1).b, 0) == ("", 2)
+
+
+# ---- the far-position shift (tests/stream_rules_probe.cpp: probe_blob_shift) ---------------------------------------------------
+SEGS = ["iq", "soft", "frec", "frames", "metrics", "fscale", "events", "chunks"]
+
+
+def live_blob(L):
+    """the two-stream blob above, grown to streams past symbol 24: a soft tail of 40 symbols, two unpopped frame records and three
+    events per stream, one stream HUNTING and one LOCKED"""
+    g = Blob(L)
+    elem = {s: L.probe_offset(b"segelem.%d" % k) for k, s in enumerate(SEGS)}
+    assert elem["frec"] == L.probe_offset(b"sizeof.frec") and elem["events"] == L.probe_offset(b"sizeof.event") and min(elem.values()) >= 4
+    n = dict(iq=0, soft=40, frec=2, frames=2, metrics=2, fscale=2, events=3, chunks=0)
+    off, length = {}, 0
+    for s in SEGS:
+        off[s] = length
+        length += (n[s] * elem[s] + 15) & ~15
+    g.b = g.b[:g.payload_off] + bytearray(2 * length)
+    g.put("h.total_bytes", len(g.b), "Q").put("h.payload_bytes", 2 * length, "Q")
+    g.rec = {}
+    for i in range(2):
+        g.put("e.off", length * i, "Q", i).put("e.len", length, "Q", i)
+        for k, s in enumerate(SEGS):
+            g.put("e.seg_off", off[s], "Q", i, 8 * k).put("e.seg_n", n[s], "Q", i, 8 * k)
+        n_soft = 5000 + 2 * i
+        for name, v in (("st.n_soft", n_soft), ("st.trk_next", n_soft), ("st.trk_anchor", 4990), ("st.cap_soft", 4096),
+                        ("e.soft_first", n_soft - 40), ("st.total_samples", 200000), ("st.iq_base", 1000 * i)):
+            g.put(name, v, "Q", i)
+        g.put("st.trk_state", 2 * i, "i", i)
+        for name, v in (("e.popped", 3 * i), ("st.n_frames", 3 * i + 2), ("e.events_first", 5 * i), ("e.events_popped", 5 * i),
+                        ("st.n_events", 5 * i + 3), ("e.chunks_first", 2 * i), ("st.n_chunks", 2 * i)):
+            g.put(name, v, "I", i)
+        at = g.payload_off + length * i
+        g.rec[i] = [at + off["frec"] + k * elem["frec"] + L.probe_offset(f.encode()) for k in range(2) for f in ("frec.payload_sym", "frec.release_sym")]
+        g.rec[i] += [at + off["events"] + k * elem["events"] + L.probe_offset(b"event.sym_idx") for k in range(3)]
+        for j, a in enumerate(g.rec[i]):
+            struct.pack_into("<Q", g.b, a, 2800 + 1000 * j + i)
+    return g
+
+
+SYM_FIELDS = ["st.n_soft", "st.trk_anchor", "st.trk_next", "e.soft_first"]
+SAMP_FIELDS = ["st.total_samples", "st.iq_base"]
+KEPT_FIELDS = [("st.origin", "Q"), ("st.n_avail", "Q"), ("e.last_round_avail", "Q"), ("st.fo_sum", "d"), ("st.n_frames", "I"), ("st.n_events", "I"),
+               ("st.n_chunks", "I"), ("e.popped", "I"), ("e.events_first", "I"), ("e.events_popped", "I"), ("e.chunks_first", "I")]
+
+
+def shift(L, data, d_sym, d_samp):
+    buf = (ctypes.c_char * len(data)).from_buffer_copy(bytes(data))
+    rc = L.probe_blob_shift(buf, len(data), d_sym, d_samp)
+    return rc, bytearray(buf.raw)
+
+
+@pytest.mark.parametrize("d", [4, 2**31, 2**32 - 4, 2**40 + 8])
+def test_blob_shift_moves_every_absolute_index_and_nothing_else(rules, d):
+    rules.probe_blob_shift.argtypes = [ctypes.c_void_p, ctypes.c_size_t, U64, U64]
+    g = live_blob(rules)
+    assert why(rules, g.b) == ("", 2)
+    d_samp = d + 12
+    rc, out = shift(rules, g.b, d, d_samp)
+    assert rc == 0 and why(rules, out) == ("", 2)
+    q = lambda b, at: struct.unpack_from("<Q", b, at)[0]
+    moved = set()
+    for i in range(2):
+        for fields, by in ((SYM_FIELDS, d), (SAMP_FIELDS, d_samp)):
+            for f in fields:
+                assert q(out, g.at(f, i)) == q(g.b, g.at(f, i)) + by, (f, i)
+                moved.add(g.at(f, i))
+        for a in g.rec[i]:                                                       # payload_sym, release_sym of each record; sym_idx of each event
+            assert q(out, a) == q(g.b, a) + d, (i, a)
+            moved.add(a)
+        for f, fmt in KEPT_FIELDS:
+            assert struct.unpack_from("<" + fmt, out, g.at(f, i)) == struct.unpack_from("<" + fmt, g.b, g.at(f, i)), (f, i)
+    # every other byte of the blob is what it was
+    same = bytearray(out)
+    for a in moved:
+        same[a:a + 8] = g.b[a:a + 8]
+    assert same == g.b and len(moved) == 2 * (6 + 7)
+    # a second shift adds up; a buffer longer than the blob keeps its tail
+    rc, twice = shift(rules, out, 2**32, 4)
+    assert rc == 0 and q(twice, g.at("st.n_soft", 1)) == 5002 + d + 2**32 and q(twice, g.at("st.iq_base", 1)) == 1000 + d_samp + 4
+    rc, longer = shift(rules, bytes(g.b) + b"\xA5" * 40, d, d_samp)
+    assert rc == 0 and longer[:len(out)] == out and longer[len(out):] == b"\xA5" * 40
+
+
+def test_blob_shift_refusals_leave_the_bytes_untouched(rules):
+    rules.probe_blob_shift.argtypes = [ctypes.c_void_p, ctypes.c_size_t, U64, U64]
+    g = live_blob(rules)
+    def low(n_soft, trk_next):                                                   # a blob that holds together, stream 1 short of symbol 24
+        return g.copy().put("st.n_soft", n_soft, "Q", 1).put("st.trk_next", trk_next, "Q", 1).put("e.soft_first", 0, "Q", 1).put("e.seg_n", n_soft, "Q", 1, 8).b
+    for data in (low(23, 23), low(30, 22), low(0, 0)):
+        assert why(rules, data) == ("", 2)
+    refused = [(g.b, 1, 0, 2), (g.b, 2, 0, 2), (g.b, 2**32 + 2, 0, 2), (g.b, 0, 3, 2), (g.b, 4, 6, 2), (g.b, 2**32, 2**32 + 1, 2),   # not multiples of 4
+               (low(23, 23), 4, 4, 3), (low(30, 22), 2**32, 4, 3), (low(0, 0), 4, 4, 3),   # n_soft < 24, trk_next < 23
+               (Blob(rules).b, 4, 4, 3),                                         # the synthetic blob above: n_soft = 0 in both streams
+               (g.b[:-8], 4, 4, 1), (poked(g.b, 0, 8), 4, 4, 1),                 # does not pass parse_blob before the shift
+               (g.copy().put("e.popped", 1, "I", 1).b, 4, 4, 1),
+               (low(24, 23), 4, 4, 4)]                                           # ... or after it: 24 symbols behind symbol 23 + d do not reach back to d
+    for data, d_sym, d_samp, code in refused:
+        rc, out = shift(rules, data, d_sym, d_samp)
+        assert rc == code and out == bytearray(data), (d_sym, d_samp, rc)
+    assert shift(rules, low(24, 24), 4, 4)[0] == 0

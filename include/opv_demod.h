@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbr_plan / opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
+                               still 7, additive: + opv_wbr_plan/ opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
                                still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
                                still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
                                still 7, additive: + opv_link, opv_enable_link_report / opv_pop_frames_link / opv_device_link / opv_link_payloads, the per-frame link report;
@@ -626,6 +627,51 @@ void opv_wbtx_destroy(opv_wbtx* wbtx);
 int opv_wbtx_push(opv_wbtx* wbtx, const int16_t* const* d_in, size_t n_in, int16_t* d_wide_out);
 uint64_t opv_wbtx_samples(const opv_wbtx* wbtx);
 int opv_wbtx_reset(opv_wbtx* wbtx, uint64_t first_sample);
+/* ---- wideband transmit at any radio rate: an exact rational up-converter bank ----------------------------------------------
+ * The mirror image of opv_wb_create_rational. opv_wbtx_create_rational makes an opv_wbtx whose wide rate is
+ * Fw = 2 168 000 x down / up S/s (10 MS/s = 1250/271, 61.44 MS/s = 7680/271: the SAME pair the radio's opv_wbr_cfg carries); it is an
+ * ordinary opv_wbtx: opv_wbtx_push, opv_wbtx_samples, opv_wbtx_reset and opv_wbtx_destroy serve it, detachment and refusals are
+ * opv_wbtx_push's (a refused push changes NOTHING). Same contract: integer-exact, independent of summation order, held to a numpy
+ * int64 model with == (tests/test_gpu_wideband_tx_rational.py), any split of the inputs into pushes gives the bytes of one push.
+ * Write M = down, U = up, L = n_taps, J = ceil(L / M) the taps per phase, taps[t] = 0 for t >= L; every channel delivers the same
+ * number of inputs x_k[m] = (I, Q) int16 per push, m = 0 at the first sample pushed, x_k[m] = 0 for m < 0:
+ *   increment: opv_wbr_plan's for the same (down, up, centre), bit for bit (one definition serves both): a channel sent up through
+ *     this bank comes down through a rational door with the same (down, up, centre_hz);
+ *   resample (zero-stuff x by M, filter with taps at M x 2 168 000 S/s = U x Fw, keep every U-th): for wide sample n >= 0,
+ *     q_n = floor(n U / M), p_n = (n U) mod M, y_k[n] = sum over j = 0 .. J - 1 of taps[p_n + j M] x x_k[q_n - j], per component (int32);
+ *   mix up and sum: a = first_sample + n, phi = (uint32)(a x inc_k), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095]
+ *     (opv_wb_lo_table), wr += yr c - yi s, wi += yi c + yr s (int64, summed over k);
+ *   output value: opv_wbtx_push's: clamp(floor((w + 2^(S-1)) / 2^S), -32768, 32767) (S = out_shift; S = 0: no rounding term), packed I | Q << 16;
+ *   output count: wide sample n exists once input q_n has arrived: after N inputs per channel the object has written
+ *     W(N) = ceil(N M / U) wide samples (opv_wbtxr_outputs). A push of n_in inputs behind N writes W(N + n_in) - W(N) samples to
+ *     d_wide_out, the first with index W(N), input q = N and phase p = W(N) U - N M. One frame (86 720 = 320 x 271 inputs) at up = 271
+ *     is a whole number of wide samples;
+ *   state between pushes: the last J - 1 inputs of every channel (zeros for a channel absent from a push, as in opv_wbtx_push) and N.
+ *   Limits (anything else is OPV_EINVAL, decided on the host by opv_wbtxr_plan): 1 <= up <= down <= 8192, down <= 32 x up,
+ *     gcd(down, up) = 1, 1 <= n_taps and J <= 64 (so n_taps <= 524 288), 1 <= n_channels <= 256, 0 <= out_shift <= 40, reserved = 0,
+ *     finite centres, non-null pointers, and for EVERY phase p sum_j |taps[p + j M]| <= 65535 (so |y| < 2^31: exact in int32; and
+ *     |sum_k w| < 2^55: exact in int64).
+ *   Push refusals, decided before anything is enqueued: OPV_EINVAL for a null table or output, a misaligned pointer, an output range of
+ *     (W(N + n_in) - W(N)) x 4 bytes that overlaps an input, n_in >= 2^31 or 2^31 or more wide samples in one push; OPV_ECAPACITY for
+ *     a push that would take N past 2^50 (16 years of signal; it keeps N M + U inside uint64); OPV_ESTATE for a detached object.
+ *     n_in = 0 is allowed and changes nothing.
+ *   With U = 1 every formula above is opv_wbtx_create's with interp = M: for M <= 16 and L <= min(1024, 64 M) such an object
+ *     delivers the same bytes.
+ *   opv_wbtx_reset(first_sample) empties the history and sets N = 0. The object does NOT migrate: rebuild it at the destination
+ *     where N is a multiple of up (a frame boundary, for instance) with first_sample + N x down / up as its first_sample - elsewhere
+ *     the phase p does not restart at 0 - and mind that its n = 0 then starts with an empty filter history.
+ * opv_wbtxr_plan, opv_wbtxr_outputs (0 for a bad cfg or N > 2^50): host only, no device. */
+typedef struct opv_wbtxr_cfg {
+    int32_t down, up;          /* M, U: wide rate = 2 168 000 x down / up - the SAME pair a radio's opv_wbr_cfg carries */
+    int32_t n_channels;        /* K */
+    int32_t n_taps;            /* L, prototype filter at down x 2 168 000 S/s (= up x wide rate: the rate the rational door's prototype runs at) */
+    int32_t out_shift;         /* S */
+    int32_t reserved;          /* 0 */
+    uint64_t first_sample;     /* absolute index of the first wide sample written */
+} opv_wbtxr_cfg;               /* 32 bytes, the layout of opv_wbr_cfg */
+int opv_wbtxr_plan(const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
+uint64_t opv_wbtxr_outputs(const opv_wbtxr_cfg* cfg, uint64_t n_in_total);
+int opv_wbtx_create_rational(opv_wbtx** out, opv_ctx* ctx, const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t* taps);
 /* Device-side channel tool for synthetic multi-stream workloads:
  * d_out[n] = clip(rint(gain * d_in[n] * exp(j 2 pi f0 n / Fs) + sigma * N(0,1)+jN(0,1))),
  * noise from a counter-based generator keyed by (seed, n). d_in/d_out: device int16 IQ. */

@@ -1,0 +1,109 @@
+// k_wideband_tx_rational.hip — k_wbtxr_duc: the up-converters of the rational wideband transmit bank (include/opv_demod.h,
+// opv_wbtx_create_rational), the mirror image of k_wbr_ddc: the wide rate is 2 168 000 x M / U S/s. One launch per push serves all K
+// channels: zero-stuff each channel by M, filter with int16 taps, keep every U-th sample - wide sample n reads the J inputs q_n,
+// q_n - 1, ... (q_n = floor(n U / M)) against row p_n = (n U) mod M of the phase-major tap table - mix it up to +f_k with the DDC's
+// closed-form integer LO, sum the channels, round, clamp and store one wide capture. Integer-exact and independent of summation
+// order (|y| < 2^31 per channel: int32 over the taps; |sum| < 2^55: int64 over the channels), so parity with the numpy model is `==`.
+//
+// Shape, as k_wbtx_duc: a workgroup owns 256 consecutive wide outputs of the push, one per thread, and loops over all K channels
+// itself: a thread keeps its output's (wr, wi) in int64 registers, so there is no sum across workgroups and no atomic. A thread's
+// phase, and with it its row of taps, is the same for all K channels: the rows are read from the global table ONCE per workgroup
+// into LDS, j-major with two int16 per dword (tile[j / 2][tid]: lanes at unit stride on every read; a thread-major row of 64 taps
+// would put 64 lanes on two banks). Per channel the workgroup's span of inputs - floor(255 U / M) + 1 new ones at most and the
+// taps' reach in front, from the carry, from this push, or zeros for an absent channel - goes into LDS once (neighbouring lanes
+// read the same or the adjacent input: a broadcast); a thread fetches the next channel's share of the span into registers while it
+// runs the taps of this one, and two span buffers taken in turn leave one barrier per channel.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "opv_wbtx_internal.h"
+
+extern "C" __global__ __launch_bounds__(256) void k_wbtxr_duc(OpvWbtxrArgs a) {
+    __shared__ int tile[OPV_WBTXR_MAXJ / 2][OPV_WBTXR_THREADS];   // taps (2 j, 2 j + 1) of thread tid's row: lo | hi << 16
+    __shared__ int xs[2][OPV_WBTXR_SPAN];                        // packed int16 I | Q << 16
+    __shared__ int16_t lo[4096];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t M = a.M, U = a.U, H = a.H, J2 = a.J2;
+
+    // the carry of the NEXT push: the last H samples of (carry, this push). It goes to the other buffer, so nobody's reads race it.
+    // (a push shorter than H: ci < H takes what is left of the old carry)
+    for (uint32_t k = blockIdx.x; k < a.K; k += gridDim.x) {
+        const int* src = a.in[k];
+        const int* old = a.hist_in + (size_t)k * H;
+        int* nxt = a.hist_out + (size_t)k * H;
+        for (uint32_t i = tid; i < H; i += OPV_WBTXR_THREADS) {
+            const uint64_t ci = (uint64_t)a.n_in + i;                     // index into (old, src) laid end to end
+            nxt[i] = ci < H ? old[ci] : src ? src[ci - H] : 0;
+        }
+    }
+    const uint32_t out0 = blockIdx.x * OPV_WBTXR_THREADS;                 // first wide output of this workgroup, within the push
+    if (out0 >= a.n_out) return;
+    const uint32_t cnt = a.n_out - out0 < OPV_WBTXR_THREADS ? a.n_out - out0 : OPV_WBTXR_THREADS;
+
+    // output out0 + l of the push: (p0 + (out0 + l) U) / M inputs behind the push's first, remainder = its phase. 64 bits once per
+    // workgroup for out0; per lane pbase + l U < 2^13 + 2^8 2^13 stays in 32.
+    const uint64_t t0 = (uint64_t)a.p0 + (uint64_t)out0 * U;
+    const uint64_t q0 = t0 / M;
+    const uint32_t pbase = (uint32_t)(t0 - q0 * M);
+    const uint32_t tl = pbase + (tid < cnt ? tid : cnt - 1) * U;          // (threads past the end redo the last output and store nothing)
+    const uint32_t dq = tl / M, p = tl - dq * M;
+    // local sample i of the span is input q0 - front + i of this push: negative ones lie in the carry, or in front of it (zeros:
+    // they meet the zero padding of a tap row). The newest input of the workgroup's last output, q0 + dq_last, is < n_in by W's rule.
+    const uint32_t front = 2 * J2 - 1;
+    const uint32_t span = front + (pbase + (cnt - 1) * U) / M + 1;        // <= 63 + 256
+    const int64_t m0 = (int64_t)q0 - (int64_t)front;
+    const uint32_t xq = front + dq;                                       // where x[q] stands; tap j reads xq - j >= 0
+
+    auto fetch = [&](uint32_t k, uint32_t i) -> int {
+        if (i >= span) return 0;
+        const int64_t m = m0 + (int64_t)i;
+        if (m < -(int64_t)H) return 0;
+        if (m < 0) return a.hist_in[(size_t)k * H + (size_t)((int64_t)H + m)];
+        const int* src = a.in[k];
+        return src ? src[m] : 0;
+    };
+
+    for (uint32_t i = tid; i < 4096; i += OPV_WBTXR_THREADS) lo[i] = a.lo[i];
+    {
+        const int2* row = (const int2*)(a.tab + (size_t)p * a.rowlen);   // rowlen is a multiple of 4: rows start on 8 bytes
+        for (uint32_t i = 0; i < a.rowlen / 4; ++i) {
+            const int2 h = row[i];
+            tile[2 * i][tid] = h.x;
+            tile[2 * i + 1][tid] = h.y;
+        }
+    }
+    const uint32_t a_lo = a.a0_lo + out0 + (tid < cnt ? tid : cnt - 1);   // phi = (uint32)((first_sample + n) * inc): the low 32 bits only
+    int64_t wr = 0, wi = 0;
+    int v0 = fetch(0, tid), v1 = fetch(0, tid + OPV_WBTXR_THREADS);
+    for (uint32_t k = 0; k < a.K; ++k) {
+        int* x = xs[k & 1];
+        x[tid] = v0;
+        if (tid < OPV_WBTXR_SPAN - OPV_WBTXR_THREADS) x[tid + OPV_WBTXR_THREADS] = v1;
+        __syncthreads();                                                  // (also: lo, before the first channel; tile is each thread's own)
+        if (k + 1 < a.K) {
+            v0 = fetch(k + 1, tid);
+            v1 = fetch(k + 1, tid + OPV_WBTXR_THREADS);
+        }
+        int yr = 0, yi = 0;
+        for (uint32_t j = 0; j < J2; ++j) {
+            const int h2 = tile[j][tid];
+            const int u0 = x[xq - 2 * j], u1 = x[xq - 2 * j - 1];
+            const int h0 = (int16_t)(h2 & 0xFFFF), h1 = h2 >> 16;
+            yr += h0 * (int)(int16_t)(u0 & 0xFFFF) + h1 * (int)(int16_t)(u1 & 0xFFFF);
+            yi += h0 * (u0 >> 16) + h1 * (u1 >> 16);
+        }
+        const uint32_t ix = (a_lo * a.inc[k]) >> 20;
+        const int64_t c = lo[ix], s = lo[(ix - 1024u) & 4095u];
+        wr += yr * c - yi * s;                                            // up: the conjugate of the DDC's mix
+        wi += yi * c + yr * s;
+        // (no second barrier: the next channel fills the other span buffer, which was last read before the barrier above)
+    }
+    if (tid < cnt) {
+        const int64_t half = a.S ? (int64_t)1 << (a.S - 1) : 0;
+        wr = (wr + half) >> a.S;                                          // floor((sum + 2^(S-1)) / 2^S): an arithmetic shift
+        wi = (wi + half) >> a.S;
+        wr = wr < -32768 ? -32768 : wr > 32767 ? 32767 : wr;
+        wi = wi < -32768 ? -32768 : wi > 32767 ? 32767 : wi;
+        a.out[out0 + tid] = (int)(((uint32_t)wi << 16) | ((uint32_t)wr & 0xFFFFu));
+    }
+}

@@ -25,15 +25,23 @@ int wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* tap
         for (int64_t t = p; t < cfg->n_taps; t += cfg->up) gain += taps[t] < 0 ? -(int64_t)taps[t] : (int64_t)taps[t];
         if (gain > (1ll << 21)) return refuse("opv_wbr: sum of |taps| of one phase exceeds 2^21");
     }
-    const double fw = (double)cfg->down * 2168000.0 / (double)cfg->up;
-    for (int k = 0; k < cfg->n_channels; ++k) {
+    switch (wbr_increments(cfg->down, cfg->up, cfg->n_channels, centre_hz, inc_out)) {
+        case WbrCentre::NotFinite: return refuse("opv_wbr: non-finite centre frequency");
+        case WbrCentre::OutOfRange: return refuse("opv_wbr: centre frequency out of range");
+        default: return OPV_OK;
+    }
+}
+
+WbrCentre wbr_increments(int32_t down, int32_t up, int32_t n_channels, const double* centre_hz, uint32_t* inc_out) {
+    const double fw = (double)down * 2168000.0 / (double)up;
+    for (int k = 0; k < n_channels; ++k) {
         const double f = centre_hz[k];
-        if (!std::isfinite(f)) return refuse("opv_wbr: non-finite centre frequency");
+        if (!std::isfinite(f)) return WbrCentre::NotFinite;
         const double turns = f / fw * 4294967296.0;
-        if (!(std::fabs(turns) < 9.0e18)) return refuse("opv_wbr: centre frequency out of range");
+        if (!(std::fabs(turns) < 9.0e18)) return WbrCentre::OutOfRange;
         inc_out[k] = (uint32_t)(uint64_t)std::llrint(turns);             // modulo 2^32: a negative centre wraps
     }
-    return OPV_OK;
+    return WbrCentre::Ok;
 }
 
 uint64_t wbr_outputs(uint32_t down, uint32_t up, uint64_t n_wide_total) {

@@ -20,6 +20,11 @@ inline uint32_t wbr_row_len(const opv_wbr_cfg& c) { return (wbr_taps_per_phase(c
 // opv_wbr_plan without the error text's destination: OPV_OK, or OPV_EINVAL with *why set
 int wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out, const char** why);
 
+// The increment rule of a wide rate of 2 168 000 x down / up S/s, for both directions (the rational up-converter bank plans with it
+// too, opv_wbtxr_rules.cpp): inc_out[k] for k < n_channels, or which centre it met that has no increment
+enum class WbrCentre { Ok, NotFinite, OutOfRange };
+WbrCentre wbr_increments(int32_t down, int32_t up, int32_t n_channels, const double* centre_hz, uint32_t* inc_out);
+
 // ceil(N U / M) for any uint64 N (1 <= U <= M)
 uint64_t wbr_outputs(uint32_t down, uint32_t up, uint64_t n_wide_total);
 

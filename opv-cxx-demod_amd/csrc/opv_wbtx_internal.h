@@ -28,4 +28,29 @@ constexpr uint32_t OPV_WBTX_TAPS = 1024 + 16;                               // J
 
 extern "C" __global__ void k_wbtx_duc(OpvWbtxArgs a);
 
+// Arguments of k_wbtxr_duc (k_wideband_tx_rational.hip: the object made by opv_wbtx_create_rational), by value. The wide rate is
+// 2 168 000 x M / U: output i of this push is wide sample W(N) + i of the object; with t = p0 + i U it reads input floor(t / M) of
+// this push and the ones in front of it against row t mod M of the phase-major tap table (opv_wbtxr_rules.h).
+struct OpvWbtxrArgs {
+    const int* const* in;    // in[K]: as OpvWbtxArgs
+    const int* hist_in;      // [K][H]: as OpvWbtxArgs, H = J - 1
+    int* hist_out;
+    const int16_t* lo;       // T[4096]
+    const int16_t* tab;      // [M][rowlen]: tab[p * rowlen + j] = taps[p + j M], zeros from L on
+    const uint32_t* inc;     // inc[K]
+    int* out;                // n_out packed wide samples
+    uint32_t a0_lo;          // low 32 bits of first_sample + W(N)
+    uint32_t n_in, n_out;    // n_out = W(N + n_in) - W(N)
+    uint32_t M, U, K, S;
+    uint32_t H;              // J - 1: input samples carried per channel
+    uint32_t J2;             // ceil(J / 2): tap pairs per phase (2 J2 <= rowlen)
+    uint32_t rowlen;         // J rounded up to a multiple of 4
+    uint32_t p0;             // phase of the push's first output: W(N) U - N M
+};
+constexpr uint32_t OPV_WBTXR_THREADS = 256;                                 // = wide outputs per workgroup, one per thread (= kWbtxrTile)
+constexpr uint32_t OPV_WBTXR_MAXJ = 64;                                     // (= kWbtxrMaxJ)
+constexpr uint32_t OPV_WBTXR_SPAN = OPV_WBTXR_THREADS + OPV_WBTXR_MAXJ;     // input samples a workgroup holds per channel: <= floor(255 U / M) + 1 new ones + 2 J2 - 1 <= 63 in front
+
+extern "C" __global__ void k_wbtxr_duc(OpvWbtxrArgs a);
+
 #endif

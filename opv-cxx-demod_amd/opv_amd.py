@@ -44,6 +44,7 @@ EXPORTS = [
     "opv_txb_create", "opv_txb_destroy", "opv_txb_reset", "opv_txb_get_state", "opv_txb_set_state", "opv_txb_round", "opv_txb_plan_round",
     "opv_tap_txb_patch",
     "opv_wbtx_plan", "opv_wbtx_create", "opv_wbtx_destroy", "opv_wbtx_push", "opv_wbtx_samples", "opv_wbtx_reset",
+    "opv_wbtxr_plan", "opv_wbtxr_outputs", "opv_wbtx_create_rational",
 ]
 
 
@@ -70,6 +71,11 @@ class WbrCfg(C.Structure):
 class WbtxCfg(C.Structure):
     _fields_ = [("interp", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("first_sample", C.c_uint64)]
+
+
+class WbtxrCfg(C.Structure):
+    _fields_ = [("down", C.c_int32), ("up", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
+                ("reserved", C.c_int32), ("first_sample", C.c_uint64)]
 
 
 class TxbState(C.Structure):
@@ -263,6 +269,10 @@ def lib():
         L.opv_wbtx_samples.restype = C.c_uint64
         L.opv_wbtx_samples.argtypes = [C.c_void_p]
         L.opv_wbtx_reset.argtypes = [C.c_void_p, C.c_uint64]
+        L.opv_wbtxr_plan.argtypes = [C.POINTER(WbtxrCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wbtxr_outputs.restype = C.c_uint64
+        L.opv_wbtxr_outputs.argtypes = [C.POINTER(WbtxrCfg), C.c_uint64]
+        L.opv_wbtx_create_rational.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbtxrCfg), C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -598,6 +608,27 @@ def wbtx_plan(interp, centre_hz, taps, out_shift, first_sample=0):
     return inc[:centre.size]
 
 
+def _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample):
+    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
+    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
+    return WbtxrCfg(int(down), int(up), centre.size, taps.size, int(out_shift), 0, int(first_sample)), centre, taps
+
+
+def wbtxr_plan(down, up, centre_hz, taps, out_shift, first_sample=0):
+    """opv_wbtxr_plan: validates a plan of the rational up-converter bank (wide rate 2 168 000 x down / up) and returns its K phase
+    increments (uint32): wbr_plan's for the same (down, up, centres); host only, needs no device"""
+    cfg, centre, taps = _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample)
+    inc = np.zeros(max(centre.size, 1), np.uint32)
+    _chk(lib().opv_wbtxr_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
+    return inc[:centre.size]
+
+
+def wbtxr_outputs(down, up, n_in_total):
+    """opv_wbtxr_outputs: wide samples written after n_in_total inputs per channel, ceil(N down / up)"""
+    cfg = WbtxrCfg(int(down), int(up), 1, 1, 0, 0, 0)
+    return int(lib().opv_wbtxr_outputs(C.byref(cfg), int(n_in_total)))
+
+
 class WidebandTx:
     """A bank of up-converters on the device of `demod` that puts K per-channel captures (a TxBank's outputs) at centre_hz[k] of one
     wide capture (opv_wbtx_*, include/opv_demod.h). Close it before its Demod."""
@@ -608,9 +639,21 @@ class WidebandTx:
         self.h = C.c_void_p()
         _chk(lib().opv_wbtx_create(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
 
+    @classmethod
+    def rational(cls, demod, down, up, centre_hz, taps, out_shift, first_sample=0):
+        """opv_wbtx_create_rational: the same object for a wide capture at 2 168 000 x down / up S/s (10 MS/s is 1250 / 271); `taps`
+        is the prototype filter at down x 2 168 000 S/s. push / samples / reset / close are the ones below; a push behind N inputs
+        writes wbtxr_outputs(down, up, N + n_in) - wbtxr_outputs(down, up, N) wide samples."""
+        self = cls.__new__(cls)
+        self.demod = demod
+        self.cfg, centre, taps = _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample)
+        self.h = C.c_void_p()
+        _chk(lib().opv_wbtx_create_rational(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
+        return self
+
     def push(self, d_in_ptrs, n_in, d_out_ptr):
         """opv_wbtx_push: d_in_ptrs[k] is channel k's device pointer to n_in samples, or None for a channel absent from this push;
-        n_in x interp wide samples go to the device pointer d_out_ptr"""
+        n_in x interp wide samples go to the device pointer d_out_ptr (a rational object: the count `rational` names)"""
         if len(d_in_ptrs) != self.cfg.n_channels:
             raise OpvError("WidebandTx: one input pointer (or None) per channel")
         tab = (C.c_void_p * len(d_in_ptrs))(*[None if p is None else int(p) for p in d_in_ptrs])

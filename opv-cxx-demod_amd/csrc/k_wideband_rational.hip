@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wideband_common.h"
 #include "opv_wb_internal.h"
 
 namespace {
@@ -36,16 +37,7 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t M = a.M, U = a.U, J = a.J, rowlen = a.rowlen;
 
-    // the carry of the NEXT push: the last J - 1 samples of (carry, this push). It goes to the other buffer, so nobody's reads race it.
-    if (blockIdx.x == 0 && blockIdx.y == 0) {
-        const uint64_t have = a.n_before + a.n_new;
-        const uint32_t keep = have < (uint64_t)(J - 1) ? (uint32_t)have : J - 1;
-        const uint32_t from = a.hist_len + a.n_new - keep;             // index into (hist_in, src) laid end to end
-        for (uint32_t i = tid; i < keep; i += OPV_WB_THREADS) {
-            const uint32_t ci = from + i;
-            a.hist_out[i] = ci < a.hist_len ? a.hist_in[ci] : a.src[ci - a.hist_len];
-        }
-    }
+    wb_write_next_carry<OPV_WB_THREADS>(a.hist_out, a.hist_in, a.hist_len, a.src, a.n_new, a.n_before, J - 1, tid);
     const uint64_t out0 = (uint64_t)blockIdx.x * a.tile;               // first output of this workgroup, within the push
     if (out0 >= a.n_out) return;
     const uint32_t cnt = a.n_out - out0 < a.tile ? (uint32_t)(a.n_out - out0) : a.tile;
@@ -59,62 +51,27 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
     const uint32_t span = front + (pbase + (cnt - 1) * M) / U + 1;     // <= rowlen + floor(tile M / U) <= OPV_WB_SPAN by the host's tile
     if (span > OPV_WB_SPAN) return;                                    // (a plan the host would not make: touch nothing)
 
-    for (uint32_t i = tid; i < 4096; i += OPV_WB_THREADS) lo[i] = a.lo[i];
+    wb_load_lo<OPV_WB_THREADS>(lo, a.lo, tid);
 
     // local sample j of the span is src[base_i + j]; the newest sample of output out0 + l is local sample front + dn_l
     const int64_t base_i = (int64_t)((uint64_t)a.nrel0 + q0) - (int64_t)front;
-    // (1) what lies in front of this push (the carry, zeros before sample 0) and behind it (zeros: no output of this push reads them)
-    for (uint32_t j = tid; j < span; j += OPV_WB_THREADS) {
-        const int64_t i = base_i + (int64_t)j;
-        if (i < 0) {
-            const int64_t h = (int64_t)a.hist_len + i;
-            raw[j] = h >= 0 ? a.hist_in[h] : 0;
-        } else if (i >= (int64_t)a.n_new) {
-            raw[j] = 0;
-        }
-    }
-    // (2) the part inside this push, in 16-byte pieces of the source wherever a whole piece lies inside both the push and the span
-    {
-        const int64_t i_lo = base_i > 0 ? base_i : 0;
-        const int64_t i_end = base_i + (int64_t)span < (int64_t)a.n_new ? base_i + (int64_t)span : (int64_t)a.n_new;
-        if (i_end > i_lo) {
-            const int64_t mis = (int64_t)(((uintptr_t)a.src >> 2) & 3u);   // src[4 q - mis] is 16-byte aligned
-            const int64_t q_lo = (i_lo + mis) >> 2, q_hi = (i_end - 1 + mis) >> 2;
-            for (int64_t q = q_lo + tid; q <= q_hi; q += OPV_WB_THREADS) {
-                const int64_t i = 4 * q - mis;
-                if (i >= i_lo && i + 4 <= i_end) {
-                    const int4 v = *(const int4*)(a.src + i);
-                    const uint32_t j = (uint32_t)(i - base_i);
-                    raw[j] = v.x;
-                    raw[j + 1] = v.y;
-                    raw[j + 2] = v.z;
-                    raw[j + 3] = v.w;
-                } else {
-                    for (int64_t e = i; e < i + 4; ++e)
-                        if (e >= i_lo && e < i_end) raw[(uint32_t)(e - base_i)] = a.src[e];
-                }
-            }
-        }
-    }
+    wb_fetch_span<OPV_WB_THREADS>(raw, a.hist_in, a.hist_len, a.src, a.n_new, base_i, span, tid, [](uint32_t j) { return j; });
     __syncthreads();
 
     // phase of local sample j: phi = (uint32)((first_sample + n) * inc) - the low 32 bits only, so 32-bit arithmetic that wraps
     const uint32_t a_base = a.a0_lo + (uint32_t)(uint64_t)base_i;
     const uint32_t k_end = (blockIdx.y + 1) * a.kper < a.K ? (blockIdx.y + 1) * a.kper : a.K;
-    const int64_t half = a.S ? (int64_t)1 << (a.S - 1) : 0;
     const uint32_t tl = pbase + (tid < cnt ? tid : 0u) * M;
     const uint32_t dn = tl / U;
     const uint32_t top = front + dn;                                    // tap j reads local sample top - j >= dn >= 0
-    const int2* row = (const int2*)(a.tab + (size_t)(tl - dn * U) * rowlen);   // 4 taps per 8 bytes
+    const int16_t* tab = (const int16_t*)a.taps;                        // the rational door's image: the phase-major int16 table
+    const int2* row = (const int2*)(tab + (size_t)(tl - dn * U) * rowlen);   // 4 taps per 8 bytes
     for (uint32_t k = blockIdx.y * a.kper; k < k_end; ++k) {
         const uint32_t inc = a.inc[k];
         for (uint32_t j = tid; j < span; j += OPV_WB_THREADS) {
-            const uint32_t phi = (a_base + j) * inc;
-            const uint32_t ix = phi >> 20;
-            const int c = lo[ix], s = lo[(ix - 1024u) & 4095u];
-            const int x = raw[j];
-            const int I = (int16_t)(x & 0xFFFF), Q = x >> 16;
-            mixed[mixed_slot(j)] = make_int2(I * c + Q * s, Q * c - I * s);
+            int c, s;
+            wb_lo_at(lo, (a_base + j) * inc, c, s);
+            mixed[mixed_slot(j)] = wb_mix_down(raw[j], c, s);
         }
         __syncthreads();
         if (tid < cnt) {
@@ -129,11 +86,7 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
                     ai += (int64_t)h[e] * m.y;
                 }
             }
-            ar = (ar + half) >> a.S;                                    // floor((acc + 2^(S-1)) / 2^S): an arithmetic shift
-            ai = (ai + half) >> a.S;
-            ar = ar < -32768 ? -32768 : ar > 32767 ? 32767 : ar;
-            ai = ai < -32768 ? -32768 : ai > 32767 ? 32767 : ai;
-            a.dst[k][out0 + tid] = (int)(((uint32_t)ai << 16) | ((uint32_t)ar & 0xFFFFu));
+            a.dst[k][out0 + tid] = wb_round_pack(ar, ai, a.S);
         }
         __syncthreads();
     }

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wideband_common.h"
 #include "opv_wbtx_internal.h"
 
 extern "C" __global__ __launch_bounds__(256) void k_wbtx_duc(OpvWbtxArgs a) {
@@ -23,20 +24,11 @@ extern "C" __global__ __launch_bounds__(256) void k_wbtx_duc(OpvWbtxArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t U = a.U, H = a.H, J = a.J;
 
-    // the carry of the NEXT push: the last H samples of (carry, this push). It goes to the other buffer, so nobody's reads race it.
-    for (uint32_t k = blockIdx.x; k < a.K; k += gridDim.x) {
-        const int* src = a.in[k];
-        const int* old = a.hist_in + (size_t)k * H;
-        int* nxt = a.hist_out + (size_t)k * H;
-        for (uint32_t i = tid; i < H; i += OPV_WBTX_THREADS) {
-            const uint64_t ci = (uint64_t)a.n_in + i;                     // index into (old, src) laid end to end
-            nxt[i] = ci < H ? old[ci] : src ? src[ci - H] : 0;
-        }
-    }
+    wbtx_write_next_carry<OPV_WBTX_THREADS>(a.hist_out, a.hist_in, H, a.in, a.n_in, a.K, tid);
     const uint32_t n0 = blockIdx.x * OPV_WBTX_THREADS;                    // first wide output of this workgroup, within the push
     if (n0 >= a.n_out) return;
 
-    for (uint32_t i = tid; i < 4096; i += OPV_WBTX_THREADS) lo[i] = a.lo[i];
+    wb_load_lo<OPV_WBTX_THREADS>(lo, a.lo, tid);
     for (uint32_t i = tid; i < J * U; i += OPV_WBTX_THREADS) tp[i] = i < a.L ? a.taps[i] : (int16_t)0;
 
     const uint32_t n_last = n0 + OPV_WBTX_THREADS - 1 < a.n_out ? n0 + OPV_WBTX_THREADS - 1 : a.n_out - 1;
@@ -64,18 +56,10 @@ extern "C" __global__ __launch_bounds__(256) void k_wbtx_duc(OpvWbtxArgs a) {
             yr += h * (int)(int16_t)(v & 0xFFFF);
             yi += h * (v >> 16);
         }
-        const uint32_t ix = (a_lo * a.inc[k]) >> 20;
-        const int64_t c = lo[ix], s = lo[(ix - 1024u) & 4095u];
-        wr += yr * c - yi * s;                                            // up: the conjugate of the DDC's mix
-        wi += yi * c + yr * s;
+        int c, s;
+        wb_lo_at(lo, a_lo * a.inc[k], c, s);
+        wb_mix_up(wr, wi, yr, yi, c, s);
         // (no second barrier: the next channel fills the other span buffer, which was last read before the barrier above)
     }
-    if (n0 + tid < a.n_out) {
-        const int64_t half = a.S ? (int64_t)1 << (a.S - 1) : 0;
-        wr = (wr + half) >> a.S;                                          // floor((sum + 2^(S-1)) / 2^S): an arithmetic shift
-        wi = (wi + half) >> a.S;
-        wr = wr < -32768 ? -32768 : wr > 32767 ? 32767 : wr;
-        wi = wi < -32768 ? -32768 : wi > 32767 ? 32767 : wi;
-        a.out[n0 + tid] = (int)(((uint32_t)wi << 16) | ((uint32_t)wr & 0xFFFFu));
-    }
+    if (n0 + tid < a.n_out) a.out[n0 + tid] = wb_round_pack(wr, wi, a.S);
 }

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "k_wideband_common.h"
 #include "opv_wbtx_internal.h"
 
 extern "C" __global__ __launch_bounds__(256) void k_wbtxr_duc(OpvWbtxrArgs a) {
@@ -25,17 +26,7 @@ extern "C" __global__ __launch_bounds__(256) void k_wbtxr_duc(OpvWbtxrArgs a) {
     const uint32_t tid = threadIdx.x;
     const uint32_t M = a.M, U = a.U, H = a.H, J2 = a.J2;
 
-    // the carry of the NEXT push: the last H samples of (carry, this push). It goes to the other buffer, so nobody's reads race it.
-    // (a push shorter than H: ci < H takes what is left of the old carry)
-    for (uint32_t k = blockIdx.x; k < a.K; k += gridDim.x) {
-        const int* src = a.in[k];
-        const int* old = a.hist_in + (size_t)k * H;
-        int* nxt = a.hist_out + (size_t)k * H;
-        for (uint32_t i = tid; i < H; i += OPV_WBTXR_THREADS) {
-            const uint64_t ci = (uint64_t)a.n_in + i;                     // index into (old, src) laid end to end
-            nxt[i] = ci < H ? old[ci] : src ? src[ci - H] : 0;
-        }
-    }
+    wbtx_write_next_carry<OPV_WBTXR_THREADS>(a.hist_out, a.hist_in, H, a.in, a.n_in, a.K, tid);
     const uint32_t out0 = blockIdx.x * OPV_WBTXR_THREADS;                 // first wide output of this workgroup, within the push
     if (out0 >= a.n_out) return;
     const uint32_t cnt = a.n_out - out0 < OPV_WBTXR_THREADS ? a.n_out - out0 : OPV_WBTXR_THREADS;
@@ -63,9 +54,9 @@ extern "C" __global__ __launch_bounds__(256) void k_wbtxr_duc(OpvWbtxrArgs a) {
         return src ? src[m] : 0;
     };
 
-    for (uint32_t i = tid; i < 4096; i += OPV_WBTXR_THREADS) lo[i] = a.lo[i];
+    wb_load_lo<OPV_WBTXR_THREADS>(lo, a.lo, tid);
     {
-        const int2* row = (const int2*)(a.tab + (size_t)p * a.rowlen);   // rowlen is a multiple of 4: rows start on 8 bytes
+        const int2* row = (const int2*)(a.taps + (size_t)p * a.rowlen);   // rowlen is a multiple of 4: rows start on 8 bytes
         for (uint32_t i = 0; i < a.rowlen / 4; ++i) {
             const int2 h = row[i];
             tile[2 * i][tid] = h.x;
@@ -92,18 +83,10 @@ extern "C" __global__ __launch_bounds__(256) void k_wbtxr_duc(OpvWbtxrArgs a) {
             yr += h0 * (int)(int16_t)(u0 & 0xFFFF) + h1 * (int)(int16_t)(u1 & 0xFFFF);
             yi += h0 * (u0 >> 16) + h1 * (u1 >> 16);
         }
-        const uint32_t ix = (a_lo * a.inc[k]) >> 20;
-        const int64_t c = lo[ix], s = lo[(ix - 1024u) & 4095u];
-        wr += yr * c - yi * s;                                            // up: the conjugate of the DDC's mix
-        wi += yi * c + yr * s;
+        int c, s;
+        wb_lo_at(lo, a_lo * a.inc[k], c, s);
+        wb_mix_up(wr, wi, yr, yi, c, s);
         // (no second barrier: the next channel fills the other span buffer, which was last read before the barrier above)
     }
-    if (tid < cnt) {
-        const int64_t half = a.S ? (int64_t)1 << (a.S - 1) : 0;
-        wr = (wr + half) >> a.S;                                          // floor((sum + 2^(S-1)) / 2^S): an arithmetic shift
-        wi = (wi + half) >> a.S;
-        wr = wr < -32768 ? -32768 : wr > 32767 ? 32767 : wr;
-        wi = wi < -32768 ? -32768 : wi > 32767 ? 32767 : wi;
-        a.out[out0 + tid] = (int)(((uint32_t)wi << 16) | ((uint32_t)wr & 0xFFFFu));
-    }
+    if (tid < cnt) a.out[out0 + tid] = wb_round_pack(wr, wi, a.S);
 }

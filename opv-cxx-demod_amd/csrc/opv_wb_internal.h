@@ -12,51 +12,45 @@
 
 struct opv_ctx;
 
-// Arguments of k_wb_ddc (csrc/k_wideband.hip), by value. Sample n of the object (0 = the first sample ever pushed) has the absolute
-// index first_sample + n; this push holds samples [n_before, n_before + n_new).
-struct OpvWbArgs {
+// What both front-door kernels are handed, by value, filled once by wb_push (opv_wideband.hip). Sample n of the object (0 = the first
+// sample ever pushed) has the absolute index first_sample + n; this push holds samples [n_before, n_before + n_new).
+struct OpvWbHead {
     const int* src;          // this push: n_new packed (I | Q << 16) samples, device-visible (pinned host, staging copy or device)
     const int* hist_in;      // the hist_len samples in front of src[0] (the carry of the pushes so far)
-    int* hist_out;           // the other carry buffer: the last min(n_before + n_new, L - 1) samples, written by block (0, 0)
+    int* hist_out;           // the other carry buffer: the last min(n_before + n_new, carry) samples, written by block (0, 0)
     const int16_t* lo;       // T[4096]
-    const int* taps;         // h[L], widened to int32
+    const void* taps;        // the taps as the kind's kernel reads them: h[L] widened to int32 (k_wb_ddc), or the phase-major int16 table
+                             // tab[U][rowlen], tab[p][j] = taps[p + j U], zero-padded, rows 8-byte aligned (k_wbr_ddc)
     const uint32_t* inc;     // inc[K]
     int* const* dst;         // dst[K]: where each channel's first output of this push goes (device-visible table)
     uint64_t n_before;       // N before this push
-    uint64_t r0;             // first output index of this push = ceil(n_before / D)
     uint32_t a0_lo;          // low 32 bits of first_sample + n_before: all the closed-form phase needs
     uint32_t n_new, hist_len, n_out;
-    uint32_t D, L, K, S;
-    uint32_t tile;           // outputs per workgroup (<= 256)
-    uint32_t lpad;           // L - 1 rounded up to a multiple of D
-    uint32_t rowlen;         // tile + lpad / D: entries per decimation phase of the workgroup's span; D * rowlen <= OPV_WB_SPAN
+    uint32_t K, S;
     uint32_t kper;           // channels per blockIdx.y
 };
 constexpr uint32_t OPV_WB_SPAN = 4096;     // wide samples (history included) a workgroup holds in LDS
 constexpr uint32_t OPV_WB_THREADS = 256;
 
+// Arguments of k_wb_ddc (csrc/k_wideband.hip): the integer door, carry = L - 1.
+struct OpvWbArgs : OpvWbHead {
+    uint64_t r0;             // first output index of this push = ceil(n_before / D)
+    uint32_t D, L;
+    uint32_t tile;           // outputs per workgroup (<= 256)
+    uint32_t lpad;           // L - 1 rounded up to a multiple of D
+    uint32_t rowlen;         // tile + lpad / D: entries per decimation phase of the workgroup's span; D * rowlen <= OPV_WB_SPAN
+};
 extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
 
-// Arguments of k_wbr_ddc (csrc/k_wideband_rational.hip), by value: the rational door, wide rate 2 168 000 x M / U. Output r of the
-// object reads wide samples n_r - j, j = 0 .. J - 1, with n_r = floor(r M / U), against row p_r = (r M) mod U of the phase-major
+// Arguments of k_wbr_ddc (csrc/k_wideband_rational.hip): the rational door, wide rate 2 168 000 x M / U, carry = J - 1. Output r of
+// the object reads wide samples n_r - j, j = 0 .. J - 1, with n_r = floor(r M / U), against row p_r = (r M) mod U of the phase-major
 // tap table. Output i of this push is r0 + i; the host hands over (n_r0, p_r0) and the device steps from there in 64 bits.
-struct OpvWbrArgs {
-    const int* src;          // as OpvWbArgs
-    const int* hist_in;      // the hist_len samples in front of src[0]
-    int* hist_out;           // the other carry buffer: the last min(n_before + n_new, J - 1) samples, written by block (0, 0)
-    const int16_t* lo;       // T[4096]
-    const int16_t* tab;      // tab[U][rowlen]: tab[p][j] = taps[p + j U], zero-padded; rows are 8-byte aligned
-    const uint32_t* inc;     // inc[K]
-    int* const* dst;         // dst[K]
-    uint64_t n_before;       // N before this push
-    uint32_t a0_lo;          // low 32 bits of first_sample + n_before
-    uint32_t n_new, hist_len, n_out;
+struct OpvWbrArgs : OpvWbHead {
     uint32_t nrel0;          // n_r0 - n_before: index within src of the first output's newest sample (< n_new when n_out > 0)
     uint32_t p0;             // p_r0
-    uint32_t M, U, J, K, S;
+    uint32_t M, U, J;
     uint32_t rowlen;         // J rounded up to a multiple of 4
     uint32_t tile;           // outputs per workgroup (<= 256): rowlen + floor(tile M / U) <= OPV_WB_SPAN
-    uint32_t kper;           // channels per blockIdx.y
 };
 extern "C" __global__ void k_wbr_ddc(OpvWbrArgs a);
 
@@ -74,9 +68,6 @@ int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // se
         hipError_t _e = (expr);                                           \
         if (_e != hipSuccess) return opv_int_fail(OPV_EHIP, #expr, _e);   \
     } while (0)
-// inc_k = (uint32) llrint(centre_hz[k] / (rate_factor x 2 168 000) x 2^32) for both banks, defined once (opv_wideband.hip, beside
-// opv_wb_lo_table, the one LO table); OPV_EINVAL for a centre that is not finite
-int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_hz, uint32_t* inc_out);
 // What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
 // (or used) after its context finds ctx_alive false and touches nothing of the context.
 struct OpvWbShared {

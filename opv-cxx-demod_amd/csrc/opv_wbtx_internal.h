@@ -1,25 +1,32 @@
 // opv_wbtx_internal.h — what the host half of the wideband transmit bank (opv_wideband_tx.hip) hands to its kernel (k_wideband_tx.hip).
-// The door to the context, the increment rule and the LO table are the receive bank's (opv_wb_internal.h): one definition each.
+// The door to the context is the receive bank's (opv_wb_internal.h); the rules of both are opv_wb_rules.h.
 #ifndef OPV_WBTX_INTERNAL_H
 #define OPV_WBTX_INTERNAL_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Arguments of k_wbtx_duc, by value. Input sample m of a channel (0 = its first sample ever pushed) feeds wide samples
-// [m U, (m + 1) U) of the object; this push holds input samples [N, N + n_in) and writes wide samples [N U, (N + n_in) U).
-struct OpvWbtxArgs {
+// What both up-converter kernels are handed, by value, filled once by opv_wbtx_push. This push holds input samples [N, N + n_in)
+// of every channel and writes n_out wide samples.
+struct OpvWbtxHead {
     const int* const* in;    // in[K]: n_in packed (I | Q << 16) samples per channel in device memory, or null for an absent channel (zeros)
     const int* hist_in;      // [K][H]: the H input samples in front of this push, zeros where the channel had none yet
     int* hist_out;           // the other carry buffer: the last H samples of (hist_in, this push), channel k by workgroup k % gridDim.x
     const int16_t* lo;       // T[4096]
-    const int16_t* taps;     // h[L]
+    const int16_t* taps;     // the taps as the kind's kernel reads them: h[L] (k_wbtx_duc), or the phase-major table [M][rowlen],
+                             // tab[p * rowlen + j] = taps[p + j M], zeros from L on (k_wbtxr_duc)
     const uint32_t* inc;     // inc[K]
-    int* out;                // n_out = n_in U packed wide samples
-    uint32_t a0_lo;          // low 32 bits of first_sample + N U: all the closed-form phase needs
+    int* out;                // n_out packed wide samples
+    uint32_t a0_lo;          // low 32 bits of first_sample + the push's first wide sample: all the closed-form phase needs
     uint32_t n_in, n_out;
-    uint32_t U, L, K, S;
-    uint32_t H;              // ceil((L - 1) / U): input samples carried per channel
+    uint32_t K, S;
+    uint32_t H;              // input samples carried per channel
+};
+
+// Arguments of k_wbtx_duc (k_wideband_tx.hip). Input sample m of a channel (0 = its first sample ever pushed) feeds wide samples
+// [m U, (m + 1) U) of the object; this push writes wide samples [N U, (N + n_in) U). H = ceil((L - 1) / U).
+struct OpvWbtxArgs : OpvWbtxHead {
+    uint32_t U, L;
     uint32_t J;              // floor((L - 1) / U) + 1: taps of the longest phase (p = 0)
 };
 constexpr uint32_t OPV_WBTX_THREADS = 256;                                  // = wide outputs per workgroup, one per thread
@@ -28,21 +35,12 @@ constexpr uint32_t OPV_WBTX_TAPS = 1024 + 16;                               // J
 
 extern "C" __global__ void k_wbtx_duc(OpvWbtxArgs a);
 
-// Arguments of k_wbtxr_duc (k_wideband_tx_rational.hip: the object made by opv_wbtx_create_rational), by value. The wide rate is
+// Arguments of k_wbtxr_duc (k_wideband_tx_rational.hip: the object made by opv_wbtx_create_rational). The wide rate is
 // 2 168 000 x M / U: output i of this push is wide sample W(N) + i of the object; with t = p0 + i U it reads input floor(t / M) of
-// this push and the ones in front of it against row t mod M of the phase-major tap table (opv_wbtxr_rules.h).
-struct OpvWbtxrArgs {
-    const int* const* in;    // in[K]: as OpvWbtxArgs
-    const int* hist_in;      // [K][H]: as OpvWbtxArgs, H = J - 1
-    int* hist_out;
-    const int16_t* lo;       // T[4096]
-    const int16_t* tab;      // [M][rowlen]: tab[p * rowlen + j] = taps[p + j M], zeros from L on
-    const uint32_t* inc;     // inc[K]
-    int* out;                // n_out packed wide samples
-    uint32_t a0_lo;          // low 32 bits of first_sample + W(N)
-    uint32_t n_in, n_out;    // n_out = W(N + n_in) - W(N)
-    uint32_t M, U, K, S;
-    uint32_t H;              // J - 1: input samples carried per channel
+// this push and the ones in front of it against row t mod M of the phase-major tap table (opv_wb_rules.h). H = J - 1,
+// n_out = W(N + n_in) - W(N).
+struct OpvWbtxrArgs : OpvWbtxHead {
+    uint32_t M, U;
     uint32_t J2;             // ceil(J / 2): tap pairs per phase (2 J2 <= rowlen)
     uint32_t rowlen;         // J rounded up to a multiple of 4
     uint32_t p0;             // phase of the push's first output: W(N) U - N M

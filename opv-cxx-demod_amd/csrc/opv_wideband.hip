@@ -1,13 +1,12 @@
-// opv_wideband.hip — the host half of the wideband front door (include/opv_demod.h, opv_wb_*): plan and validation (host only),
-// the object that carries the last L - 1 wide samples and the count N from push to push, and the push itself: every channel's
-// output count is computed here, room is reserved in all K streams under push_enqueue's rules (opv_int_push_reserve) before
-// anything is launched, then ONE k_wb_ddc launch on the context's copy stream writes all K streams. An object is of one of two
-// kinds: the integer door (opv_wb_create: decim wide samples per output, k_wb_ddc) or the rational one (opv_wb_create_rational:
-// down / up wide samples per output, k_wbr_ddc; its rules are opv_wbr_rules.h). They differ in how a push's outputs are counted
-// and in the launch; staging, the destination-table ring, the reservation and the lifetime rules are the same code.
+// opv_wideband.hip — the host half of the wideband front door (include/opv_demod.h, opv_wb_*): the object that carries the last
+// L - 1 wide samples and the count N from push to push, and the push itself: every channel's output count is computed here, room
+// is reserved in all K streams under push_enqueue's rules (opv_int_push_reserve) before anything is launched, then ONE k_wb_ddc
+// launch on the context's copy stream writes all K streams. An object is of one of two kinds: the integer door (opv_wb_create:
+// decim wide samples per output, k_wb_ddc) or the rational one (opv_wb_create_rational: down / up wide samples per output,
+// k_wbr_ddc). They differ in how a push's outputs are counted and in the launch; staging, the destination-table ring, the
+// reservation and the lifetime rules are the same code. Plans and every other rule that needs no device are opv_wb_rules.h's.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -16,47 +15,15 @@
 
 #include "../../include/opv_demod.h"
 #include "opv_wb_internal.h"
-#include "opv_wbr_rules.h"
+#include "opv_wb_rules.h"
 
-static_assert(kWbrSpan == OPV_WB_SPAN && kWbrMaxTile == OPV_WB_THREADS, "opv_wbr_rules.h sizes k_wbr_ddc's tile for this span");
+static_assert(kWbrSpan == OPV_WB_SPAN && kWbrMaxTile == OPV_WB_THREADS, "opv_wb_rules.h sizes k_wbr_ddc's tile for this span");
 
 namespace {
 
-constexpr double kWideRate = 2168000.0;
 constexpr int kTabSlots = 8;             // pushes whose destination tables may be in flight before the host waits for the oldest
 
-int check_cfg(const opv_wb_cfg* cfg) {
-    if (!cfg) return opv_int_fail(OPV_EINVAL, "opv_wb: null configuration");
-    if (cfg->decim < 1 || cfg->decim > 16) return opv_int_fail(OPV_EINVAL, "opv_wb: decim outside 1..16");
-    if (cfg->n_channels < 1 || cfg->n_channels > 256) return opv_int_fail(OPV_EINVAL, "opv_wb: n_channels outside 1..256");
-    if (cfg->n_taps < 1 || cfg->n_taps > 1024) return opv_int_fail(OPV_EINVAL, "opv_wb: n_taps outside 1..1024");
-    if (cfg->out_shift < 0 || cfg->out_shift > 40) return opv_int_fail(OPV_EINVAL, "opv_wb: out_shift outside 0..40");
-    return OPV_OK;
-}
-
-int plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
-    if (int r = check_cfg(cfg)) return r;
-    if (!centre_hz || !taps || !inc_out) return opv_int_fail(OPV_EINVAL, "opv_wb: null pointer");
-    int64_t gain = 0;
-    for (int t = 0; t < cfg->n_taps; ++t) gain += taps[t] < 0 ? -(int64_t)taps[t] : (int64_t)taps[t];
-    if (gain > (1ll << 21)) return opv_int_fail(OPV_EINVAL, "opv_wb: sum of |taps| exceeds 2^21");
-    return opv_int_wb_increments(cfg->decim, cfg->n_channels, centre_hz, inc_out);
-}
-
 }  // namespace
-
-// the increment rule of both banks (the DDCs here, the up-converters of opv_wideband_tx.hip): the wide rate is rate_factor x 2 168 000 S/s
-int opv_int_wb_increments(int rate_factor, int n_channels, const double* centre_hz, uint32_t* inc_out) {
-    const double fs = (double)rate_factor * kWideRate;
-    for (int k = 0; k < n_channels; ++k) {
-        const double f = centre_hz[k];
-        if (!std::isfinite(f)) return opv_int_fail(OPV_EINVAL, "opv_wb / opv_wbtx: non-finite centre frequency");
-        const double turns = f / fs * 4294967296.0;
-        if (!(std::fabs(turns) < 9.0e18)) return opv_int_fail(OPV_EINVAL, "opv_wb / opv_wbtx: centre frequency out of range");
-        inc_out[k] = (uint32_t)(uint64_t)std::llrint(turns);          // modulo 2^32: a negative centre wraps
-    }
-    return OPV_OK;
-}
 
 enum class WbKind { Integer, Rational };
 
@@ -137,13 +104,10 @@ int make_object(opv_wb** out, opv_ctx* ctx, const char* who, int K, uint32_t car
 
 }  // namespace
 
-extern "C" void opv_wb_lo_table(int16_t out4096[4096]) {
-    if (!out4096) return;
-    for (int i = 0; i < 4096; ++i) out4096[i] = (int16_t)std::lrint(32767.0 * std::cos(2.0 * 3.14159265358979323846 * (double)i / 4096.0));
-}
-
 extern "C" int opv_wb_plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
-    return plan(cfg, centre_hz, taps, inc_out);
+    const char* why = nullptr;
+    if (int r = wb_plan(cfg, centre_hz, taps, inc_out, &why)) return opv_int_fail(r, why);
+    return OPV_OK;
 }
 
 extern "C" size_t opv_wb_outputs(const opv_wb_cfg* cfg, uint64_t n_wide_total) {
@@ -173,7 +137,7 @@ extern "C" int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, 
     *out = nullptr;
     if (!ctx || !streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create: null pointer");
     std::vector<uint32_t> inc(256);
-    if (int r = plan(cfg, centre_hz, taps, inc.data())) return r;
+    if (int r = opv_wb_plan(cfg, centre_hz, taps, inc.data())) return r;
     const int K = cfg->n_channels, L = cfg->n_taps, D = cfg->decim;
     std::vector<int> taps32((size_t)L);
     for (int t = 0; t < L; ++t) taps32[t] = taps[t];
@@ -187,7 +151,7 @@ extern "C" int opv_wb_create(opv_wb** out, opv_ctx* ctx, const opv_wb_cfg* cfg, 
     });
 }
 
-// ---- the rational door: the plan's rules are opv_wbr_rules.cpp's
+// ---- the rational door
 extern "C" int opv_wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
     const char* why = nullptr;
     if (int r = wbr_plan(cfg, centre_hz, taps, inc_out, &why)) return opv_int_fail(r, why);
@@ -206,9 +170,9 @@ extern "C" int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_
     if (!ctx || !streams) return opv_int_fail(OPV_EINVAL, "opv_wb_create_rational: null pointer");
     std::vector<uint32_t> inc(256);
     if (int r = opv_wbr_plan(cfg, centre_hz, taps, inc.data())) return r;
-    const uint32_t J = wbr_taps_per_phase(*cfg), rowlen = wbr_row_len(*cfg);
+    const uint32_t J = wb_taps_per_phase(cfg->n_taps, cfg->up), rowlen = wb_row_len(J);
     std::vector<int16_t> tab((size_t)cfg->up * rowlen);
-    wbr_phase_table(*cfg, taps, tab.data());
+    wb_phase_table(taps, cfg->n_taps, (uint32_t)cfg->up, J, rowlen, tab.data());
     return make_object(out, ctx, "opv_wb_create_rational", cfg->n_channels, J - 1, streams, inc.data(), tab.data(), tab.size() * 2, [&](opv_wb* w) {
         w->kind = WbKind::Rational;
         w->rcfg = *cfg;
@@ -231,7 +195,7 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     if (n_new >= (1ull << 31)) return opv_int_fail(OPV_EINVAL, "opv_wb_push: more than 2^31 - 1 samples in one push");
     const uint32_t K = w->K;
     const bool rational = w->kind == WbKind::Rational;
-    // ---- the push's outputs [r0, r1) by the kind's rule: ceil(N / D), or ceil(N U / M) with where output r0 sits (opv_wbr_rules.h)
+    // ---- the push's outputs [r0, r1) by the kind's rule: ceil(N / D), or ceil(N U / M) with where output r0 sits (opv_wb_rules.h)
     WbrFirst first{};
     uint64_t r0, r1;
     if (rational) {
@@ -287,43 +251,32 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     if (ky > K) ky = K;
     const uint32_t kper = (K + ky - 1) / ky;
     ky = (K + kper - 1) / kper;
-    const uint32_t a0_lo = (uint32_t)((rational ? w->rcfg.first_sample : w->cfg.first_sample) + w->n_total);
+    OpvWbHead h{};
+    h.src = src;
+    h.hist_in = w->d_hist[w->cur];
+    h.hist_out = w->d_hist[w->cur ^ 1];
+    h.lo = w->d_lo;
+    h.taps = w->d_taps;
+    h.inc = w->d_inc;
+    h.dst = (int* const*)d_tab;
+    h.n_before = w->n_total;
+    h.a0_lo = (uint32_t)((rational ? w->rcfg.first_sample : w->cfg.first_sample) + w->n_total);
+    h.n_new = (uint32_t)n_new;
+    h.hist_len = w->hist_len;
+    h.n_out = n_out;
+    h.K = K; h.S = (uint32_t)(rational ? w->rcfg.out_shift : w->cfg.out_shift); h.kper = kper;
     if (rational) {
-        OpvWbrArgs a{};
-        a.src = src;
-        a.hist_in = w->d_hist[w->cur];
-        a.hist_out = w->d_hist[w->cur ^ 1];
-        a.lo = w->d_lo;
-        a.tab = (const int16_t*)w->d_taps;
-        a.inc = w->d_inc;
-        a.dst = (int* const*)d_tab;
-        a.n_before = w->n_total;
-        a.a0_lo = a0_lo;
-        a.n_new = (uint32_t)n_new;
-        a.hist_len = w->hist_len;
-        a.n_out = n_out;
+        OpvWbrArgs a{h};
         a.nrel0 = (uint32_t)first.n_rel;                                // (< n_new whenever n_out > 0; not read otherwise)
         a.p0 = first.phase;
-        a.M = (uint32_t)w->rcfg.down; a.U = (uint32_t)w->rcfg.up; a.J = w->carry + 1; a.K = K; a.S = (uint32_t)w->rcfg.out_shift;
-        a.rowlen = w->rowlen; a.tile = w->tile; a.kper = kper;
+        a.M = (uint32_t)w->rcfg.down; a.U = (uint32_t)w->rcfg.up; a.J = w->carry + 1;
+        a.rowlen = w->rowlen; a.tile = w->tile;
         k_wbr_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
     } else {
-        OpvWbArgs a{};
-        a.src = src;
-        a.hist_in = w->d_hist[w->cur];
-        a.hist_out = w->d_hist[w->cur ^ 1];
-        a.lo = w->d_lo;
-        a.taps = (const int*)w->d_taps;
-        a.inc = w->d_inc;
-        a.dst = (int* const*)d_tab;
-        a.n_before = w->n_total;
+        OpvWbArgs a{h};
         a.r0 = r0;
-        a.a0_lo = a0_lo;
-        a.n_new = (uint32_t)n_new;
-        a.hist_len = w->hist_len;
-        a.n_out = n_out;
-        a.D = (uint32_t)w->cfg.decim; a.L = (uint32_t)w->cfg.n_taps; a.K = K; a.S = (uint32_t)w->cfg.out_shift;
-        a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen; a.kper = kper;
+        a.D = (uint32_t)w->cfg.decim; a.L = (uint32_t)w->cfg.n_taps;
+        a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen;
         k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
     }
     HIPCHK(hipGetLastError());

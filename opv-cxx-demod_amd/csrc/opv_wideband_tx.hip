@@ -1,63 +1,44 @@
-// opv_wideband_tx.hip — the host half of the wideband transmit bank (include/opv_demod.h, opv_wbtx_*): plan and validation (host
-// only; the increment rule and the LO table are the receive bank's, opv_wb_internal.h), the object that carries the last
-// ceil((L - 1) / U) input samples of every channel and the count N from push to push, and the push itself: refused on the host
-// before anything is enqueued, then one upload of the K input pointers, ONE k_wbtx_duc launch on the context's stream and one wait.
-// An object is of one of two kinds: the integer bank (opv_wbtx_create: interp wide samples per input, k_wbtx_duc) or the rational
-// one (opv_wbtx_create_rational: down / up wide samples per input, k_wbtxr_duc; its rules are opv_wbtxr_rules.h). They differ in
-// how a push's outputs are counted and in the kernel; the object, its carry and its door to the context are shared.
+// opv_wideband_tx.hip — the host half of the wideband transmit bank (include/opv_demod.h, opv_wbtx_*): the object that carries the
+// last H input samples of every channel and the count N from push to push, and the push itself: refused on the host before
+// anything is enqueued, then one upload of the K input pointers, ONE launch on the context's stream and one wait. An object is of
+// one of two kinds: the integer bank (opv_wbtx_create: interp wide samples per input, k_wbtx_duc) or the rational one
+// (opv_wbtx_create_rational: down / up wide samples per input, k_wbtxr_duc). They differ in how a push's outputs are counted and in
+// the kernel; the object, its carry and its door to the context are shared. Plans, refusals and every other rule that needs no
+// device are opv_wb_rules.h's.
 #include <cstdint>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "opv_ctx.h"
+#include "opv_wb_rules.h"
 #include "opv_wbtx_internal.h"
-#include "opv_wbtxr_rules.h"
 
-static_assert(kWbtxrTile == OPV_WBTXR_THREADS && kWbtxrMaxJ == OPV_WBTXR_MAXJ, "opv_wbtxr_rules.h sizes k_wbtxr_duc's tile and tap rows");
-
-namespace {
-
-int wbtx_plan(const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
-    if (!cfg) return fail(OPV_EINVAL, "opv_wbtx: null configuration");
-    if (cfg->interp < 1 || cfg->interp > 16) return fail(OPV_EINVAL, "opv_wbtx: interp outside 1..16");
-    if (cfg->n_channels < 1 || cfg->n_channels > 256) return fail(OPV_EINVAL, "opv_wbtx: n_channels outside 1..256");
-    if (cfg->n_taps < 1 || cfg->n_taps > 1024) return fail(OPV_EINVAL, "opv_wbtx: n_taps outside 1..1024");
-    if (cfg->out_shift < 0 || cfg->out_shift > 40) return fail(OPV_EINVAL, "opv_wbtx: out_shift outside 0..40");
-    if (!centre_hz || !taps || !inc_out) return fail(OPV_EINVAL, "opv_wbtx: null pointer");
-    for (int p = 0; p < cfg->interp && p < cfg->n_taps; ++p) {          // |y| <= 65535 x 32768 < 2^31: what licenses the kernel's int32
-        int64_t gain = 0;
-        for (int t = p; t < cfg->n_taps; t += cfg->interp) gain += taps[t] < 0 ? -(int64_t)taps[t] : (int64_t)taps[t];
-        if (gain > 65535) return fail(OPV_EINVAL, "opv_wbtx: sum of |taps| of one phase exceeds 65535");
-    }
-    return opv_int_wb_increments(cfg->interp, cfg->n_channels, centre_hz, inc_out);
-}
-
-}  // namespace
+static_assert(kWbtxrTile == OPV_WBTXR_THREADS && kWbtxrMaxJ == OPV_WBTXR_MAXJ, "opv_wb_rules.h sizes k_wbtxr_duc's tile and tap rows");
 
 struct opv_wbtx {
     opv_ctx* ctx = nullptr;
-    opv_wbtx_cfg cfg{};
+    WbtxShape shape{};                   // the kind, its ratio (Integer: interp / 1) and K
+    uint32_t L = 0, S = 0;               // n_taps, out_shift
+    uint64_t first_sample = 0;
     OpvCtxDoor door{};                   // what outlives the context: door.shared->ctx_alive
     hipStream_t stream = nullptr;        // the context's: the one its transmit bank uses
     uint64_t n_total = 0;                // N: input samples per channel pushed so far
-    uint32_t H = 0, J = 0;               // ceil((L - 1) / U) samples carried per channel; floor((L - 1) / U) + 1 taps of the longest phase
+    uint32_t H = 0, J = 0;               // input samples carried per channel; taps of the longest phase. Integer: ceil((L - 1) / U), floor((L - 1) / U) + 1; Rational: J - 1, ceil(L / M)
+    uint32_t rowlen = 0;                 // Rational: the row length of the phase-major table
     int cur = 0;                         // which carry buffer holds the history
     int* d_hist[2] = {nullptr, nullptr};
     int16_t* d_lo = nullptr;
-    int16_t* d_taps = nullptr;
+    int16_t* d_taps = nullptr;           // Integer: h[L]; Rational: the phase-major table [down][rowlen]
     uint32_t* d_inc = nullptr;
     const int** d_tab = nullptr;         // the push's K input pointers as the kernel reads them ...
     const int** h_tab = nullptr;         // ... and the pinned copy they are uploaded from
-    // an object made by opv_wbtx_create_rational (rules: opv_wbtxr_rules.h): cfg above holds K, L, S and first_sample, interp = 0;
-    // H = J - 1, and d_taps holds the phase-major table [down][rowlen]
-    bool rational = false;
-    opv_wbtxr_cfg rcfg{};
-    uint32_t rowlen = 0;
 };
 
 extern "C" int opv_wbtx_plan(const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
-    return wbtx_plan(cfg, centre_hz, taps, inc_out);
+    const char* why = nullptr;
+    if (int r = wbtx_plan(cfg, centre_hz, taps, inc_out, &why)) return fail(r, why);
+    return OPV_OK;
 }
 
 extern "C" void opv_wbtx_destroy(opv_wbtx* w) {
@@ -71,26 +52,17 @@ extern "C" void opv_wbtx_destroy(opv_wbtx* w) {
     delete w;
 }
 
-// the object of either kind: `image` is the taps as the kind's kernel reads them (h[L], or the phase-major table), H the input
-// samples carried per channel
-static int wbtx_make(opv_wbtx** out, opv_ctx* ctx, const char* what, const opv_wbtx_cfg& cfg, const opv_wbtxr_cfg* rcfg, uint32_t H, uint32_t J,
-                     const uint32_t* inc, const int16_t* image, size_t image_len) {
+// the object of either kind: `plan` is an object with the kind's own fields set by its creator (shape, L, S, first_sample, H, J,
+// rowlen) and nothing else, `image` the taps as the kind's kernel reads them (h[L], or the phase-major table)
+static int wbtx_make(opv_wbtx** out, opv_ctx* ctx, const char* what, const opv_wbtx& plan, const uint32_t* inc, const int16_t* image, size_t image_len) {
     OpvCtxDoor door;
     if (int r = opv_int_door(ctx, &door)) return r;
-    opv_wbtx* w = new (std::nothrow) opv_wbtx;
+    opv_wbtx* w = new (std::nothrow) opv_wbtx(plan);
     if (!w) return fail(OPV_ENOMEM, what);
-    const uint32_t K = (uint32_t)cfg.n_channels;
+    const uint32_t K = w->shape.K;
     w->ctx = ctx;
-    w->cfg = cfg;
     w->door = door;
     w->stream = ctx->stream;
-    w->H = H;
-    w->J = J;
-    if (rcfg) {
-        w->rational = true;
-        w->rcfg = *rcfg;
-        w->rowlen = wbtxr_row_len(*rcfg);
-    }
     int16_t lo[4096];
     opv_wb_lo_table(lo);
     auto undo = [&](hipError_t e, const char* where) { opv_wbtx_destroy(w); return fail(OPV_EHIP, where, e); };
@@ -117,12 +89,19 @@ extern "C" int opv_wbtx_create(opv_wbtx** out, opv_ctx* ctx, const opv_wbtx_cfg*
     *out = nullptr;
     if (!ctx) return fail(OPV_EINVAL, "opv_wbtx_create: null context");
     std::vector<uint32_t> inc(256);
-    if (int r = wbtx_plan(cfg, centre_hz, taps, inc.data())) return r;
+    if (int r = opv_wbtx_plan(cfg, centre_hz, taps, inc.data())) return r;
     const uint32_t L = (uint32_t)cfg->n_taps, U = (uint32_t)cfg->interp;
-    return wbtx_make(out, ctx, "opv_wbtx_create", *cfg, nullptr, (L - 1 + U - 1) / U, (L - 1) / U + 1, inc.data(), taps, L);
+    opv_wbtx plan;
+    plan.shape = {WbtxKind::Integer, U, 1, (uint32_t)cfg->n_channels};
+    plan.L = L;
+    plan.S = (uint32_t)cfg->out_shift;
+    plan.first_sample = cfg->first_sample;
+    plan.H = (L - 1 + U - 1) / U;
+    plan.J = (L - 1) / U + 1;
+    return wbtx_make(out, ctx, "opv_wbtx_create", plan, inc.data(), taps, L);
 }
 
-// ---- the rational bank: the plan's rules are opv_wbtxr_rules.cpp's
+// ---- the rational bank
 extern "C" int opv_wbtxr_plan(const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
     const char* why = nullptr;
     if (int r = wbtxr_plan(cfg, centre_hz, taps, inc_out, &why)) return fail(r, why);
@@ -140,11 +119,18 @@ extern "C" int opv_wbtx_create_rational(opv_wbtx** out, opv_ctx* ctx, const opv_
     if (!ctx) return fail(OPV_EINVAL, "opv_wbtx_create_rational: null context");
     std::vector<uint32_t> inc(256);
     if (int r = opv_wbtxr_plan(cfg, centre_hz, taps, inc.data())) return r;
-    const uint32_t J = wbtxr_taps_per_phase(*cfg);
-    std::vector<int16_t> tab((size_t)cfg->down * wbtxr_row_len(*cfg));
-    wbtxr_phase_table(*cfg, taps, tab.data());
-    const opv_wbtx_cfg as_wbtx{0, cfg->n_channels, cfg->n_taps, cfg->out_shift, cfg->first_sample};   // (interp = 0: no integer push reads it)
-    return wbtx_make(out, ctx, "opv_wbtx_create_rational", as_wbtx, cfg, J - 1, J, inc.data(), tab.data(), tab.size());
+    const uint32_t J = wb_taps_per_phase(cfg->n_taps, cfg->down), rowlen = wb_row_len(J);
+    std::vector<int16_t> tab((size_t)cfg->down * rowlen);                  // at most 8192 x 64 x 2 B = 1 MB
+    wb_phase_table(taps, cfg->n_taps, (uint32_t)cfg->down, J, rowlen, tab.data());
+    opv_wbtx plan;
+    plan.shape = {WbtxKind::Rational, (uint32_t)cfg->down, (uint32_t)cfg->up, (uint32_t)cfg->n_channels};
+    plan.L = (uint32_t)cfg->n_taps;
+    plan.S = (uint32_t)cfg->out_shift;
+    plan.first_sample = cfg->first_sample;
+    plan.H = J - 1;
+    plan.J = J;
+    plan.rowlen = rowlen;
+    return wbtx_make(out, ctx, "opv_wbtx_create_rational", plan, inc.data(), tab.data(), tab.size());
 }
 
 extern "C" uint64_t opv_wbtx_samples(const opv_wbtx* w) { return w ? w->n_total : 0; }
@@ -153,83 +139,51 @@ extern "C" int opv_wbtx_reset(opv_wbtx* w, uint64_t first_sample) {
     if (!w) return fail(OPV_EINVAL, "opv_wbtx_reset: null object");
     if (!w->door.shared->ctx_alive) return fail(OPV_ESTATE, "opv_wbtx_reset: the object's context has been destroyed");
     HIPCHK(hipSetDevice(w->door.device));
-    HIPCHK(hipMemsetAsync(w->d_hist[w->cur], 0, (size_t)w->cfg.n_channels * (w->H ? w->H : 1) * 4, w->stream));
+    HIPCHK(hipMemsetAsync(w->d_hist[w->cur], 0, (size_t)w->shape.K * (w->H ? w->H : 1) * 4, w->stream));
     HIPCHK(hipStreamSynchronize(w->stream));
     w->n_total = 0;
-    w->cfg.first_sample = first_sample;
-    return OPV_OK;
-}
-
-// opv_wbtx_push of a rational object: the same steps, the count and the first output by opv_wbtxr_rules.h, k_wbtxr_duc
-static int wbtxr_push(opv_wbtx* w, const int16_t* const* d_in, size_t n_in, int16_t* d_wide_out) {
-    // ---- what can refuse the push, all of it on the host: nothing is enqueued and nothing changes before this is through
-    uint64_t n_out = 0;
-    const char* why = nullptr;
-    if (int r = wbtxr_push_plan(w->rcfg, w->n_total, d_in, n_in, d_wide_out, &n_out, &why)) return fail(r, why);
-    if (n_in == 0) return OPV_OK;
-    // ---- one upload, one launch, one wait: all on the context's stream
-    const uint32_t K = (uint32_t)w->rcfg.n_channels, M = (uint32_t)w->rcfg.down, U = (uint32_t)w->rcfg.up;
-    const WbtxrFirst first = wbtxr_first_output(M, U, w->n_total);
-    HIPCHK(hipSetDevice(w->door.device));
-    for (uint32_t k = 0; k < K; ++k) w->h_tab[k] = (const int*)d_in[k];
-    HIPCHK(hipMemcpyAsync(w->d_tab, w->h_tab, (size_t)K * sizeof(int*), hipMemcpyHostToDevice, w->stream));
-    OpvWbtxrArgs a{};
-    a.in = w->d_tab;
-    a.hist_in = w->d_hist[w->cur];
-    a.hist_out = w->d_hist[w->cur ^ 1];
-    a.lo = w->d_lo;
-    a.tab = w->d_taps;
-    a.inc = w->d_inc;
-    a.out = (int*)d_wide_out;
-    a.a0_lo = (uint32_t)(w->cfg.first_sample + first.n0);
-    a.n_in = (uint32_t)n_in;
-    a.n_out = (uint32_t)n_out;
-    a.M = M; a.U = U; a.K = K; a.S = (uint32_t)w->cfg.out_shift;
-    a.H = w->H; a.J2 = (w->J + 1) / 2; a.rowlen = w->rowlen;
-    a.p0 = first.phase;
-    k_wbtxr_duc<<<(a.n_out + OPV_WBTXR_THREADS - 1) / OPV_WBTXR_THREADS, OPV_WBTXR_THREADS, 0, w->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(w->stream));                               // (the inputs and the output are the caller's again)
-    w->cur ^= 1;
-    w->n_total += n_in;
+    w->first_sample = first_sample;
     return OPV_OK;
 }
 
 extern "C" int opv_wbtx_push(opv_wbtx* w, const int16_t* const* d_in, size_t n_in, int16_t* d_wide_out) {
     if (!w) return fail(OPV_EINVAL, "opv_wbtx_push: null object");
     if (!w->door.shared->ctx_alive) return fail(OPV_ESTATE, "opv_wbtx_push: the object's context has been destroyed");
-    if (w->rational) return wbtxr_push(w, d_in, n_in, d_wide_out);
     // ---- what can refuse the push, all of it on the host: nothing is enqueued and nothing changes before this is through
-    if (!d_in || !d_wide_out) return fail(OPV_EINVAL, "opv_wbtx_push: null pointer");
-    const uint64_t K = (uint64_t)w->cfg.n_channels, U = (uint64_t)w->cfg.interp;
-    if ((uint64_t)n_in >= (1ull << 31) || (uint64_t)n_in * U >= (1ull << 31)) return fail(OPV_EINVAL, "opv_wbtx_push: 2^31 or more wide samples in one push");
+    uint64_t n_out = 0;
+    const char* why = nullptr;
+    if (int r = wbtx_push_plan(w->shape, w->n_total, d_in, n_in, d_wide_out, &n_out, &why)) return fail(r, why);
     if (n_in == 0) return OPV_OK;
-    const uintptr_t out_lo = (uintptr_t)d_wide_out, out_hi = out_lo + (uintptr_t)(n_in * U * 4);
-    if (out_lo & 3u) return fail(OPV_EINVAL, "opv_wbtx_push: output pointer must be 4-byte aligned");
-    for (uint64_t k = 0; k < K; ++k) {
-        const uintptr_t lo = (uintptr_t)d_in[k], hi = lo + (uintptr_t)(n_in * 4);
-        if (!lo) continue;
-        if (lo & 3u) return fail(OPV_EINVAL, "opv_wbtx_push: input pointer must be 4-byte aligned");
-        if (lo < out_hi && out_lo < hi) return fail(OPV_EINVAL, "opv_wbtx_push: the output overlaps an input");
-    }
     // ---- one upload, one launch, one wait: all on the context's stream
+    const uint32_t K = w->shape.K, M = w->shape.down, U = w->shape.up;
     HIPCHK(hipSetDevice(w->door.device));
-    for (uint64_t k = 0; k < K; ++k) w->h_tab[k] = (const int*)d_in[k];
+    for (uint32_t k = 0; k < K; ++k) w->h_tab[k] = (const int*)d_in[k];
     HIPCHK(hipMemcpyAsync(w->d_tab, w->h_tab, (size_t)K * sizeof(int*), hipMemcpyHostToDevice, w->stream));
-    OpvWbtxArgs a{};
-    a.in = w->d_tab;
-    a.hist_in = w->d_hist[w->cur];
-    a.hist_out = w->d_hist[w->cur ^ 1];
-    a.lo = w->d_lo;
-    a.taps = w->d_taps;
-    a.inc = w->d_inc;
-    a.out = (int*)d_wide_out;
-    a.a0_lo = (uint32_t)(w->cfg.first_sample + w->n_total * U);
-    a.n_in = (uint32_t)n_in;
-    a.n_out = (uint32_t)(n_in * U);
-    a.U = (uint32_t)U; a.L = (uint32_t)w->cfg.n_taps; a.K = (uint32_t)K; a.S = (uint32_t)w->cfg.out_shift;
-    a.H = w->H; a.J = w->J;
-    k_wbtx_duc<<<(a.n_out + OPV_WBTX_THREADS - 1) / OPV_WBTX_THREADS, OPV_WBTX_THREADS, 0, w->stream>>>(a);
+    OpvWbtxHead h{};
+    h.in = w->d_tab;
+    h.hist_in = w->d_hist[w->cur];
+    h.hist_out = w->d_hist[w->cur ^ 1];
+    h.lo = w->d_lo;
+    h.taps = w->d_taps;
+    h.inc = w->d_inc;
+    h.out = (int*)d_wide_out;
+    h.n_in = (uint32_t)n_in;
+    h.n_out = (uint32_t)n_out;
+    h.K = K; h.S = w->S; h.H = w->H;
+    if (w->shape.kind == WbtxKind::Rational) {
+        const WbtxrFirst first = wbtxr_first_output(M, U, w->n_total);
+        h.a0_lo = (uint32_t)(w->first_sample + first.n0);
+        OpvWbtxrArgs a{h};
+        a.M = M; a.U = U; a.J2 = (w->J + 1) / 2; a.rowlen = w->rowlen;
+        a.p0 = first.phase;
+        k_wbtxr_duc<<<(h.n_out + OPV_WBTXR_THREADS - 1) / OPV_WBTXR_THREADS, OPV_WBTXR_THREADS, 0, w->stream>>>(a);
+    } else {
+        const uint32_t interp = M;                                        // (the integer bank's ratio is interp / 1)
+        h.a0_lo = (uint32_t)(w->first_sample + w->n_total * interp);      // the first wide sample is N interp
+        OpvWbtxArgs a{h};
+        a.U = interp; a.L = w->L; a.J = w->J;
+        k_wbtx_duc<<<(h.n_out + OPV_WBTX_THREADS - 1) / OPV_WBTX_THREADS, OPV_WBTX_THREADS, 0, w->stream>>>(a);
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(w->stream));                               // (the inputs and the output are the caller's again)
     w->cur ^= 1;

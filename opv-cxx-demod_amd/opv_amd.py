@@ -484,18 +484,26 @@ def blob_streams(blob):
 
 
 # ---------------------------------------------------------------- wideband front door (opv_wb_*)
-def _wb_args(decim, centre_hz, taps, out_shift, first_sample):
+def _wb_cfg(Cfg, centre_hz, taps, out_shift, first_sample, **ratio):
+    """(cfg, centre, taps) for any of the four wideband configuration structs, every field by name: `ratio` is the kind's own
+    (decim=, interp=, or down= and up=); a field not named (the rational structs' `reserved`) stays 0"""
     centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
     taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
-    return WbCfg(int(decim), centre.size, taps.size, int(out_shift), int(first_sample)), centre, taps
+    cfg = Cfg(n_channels=centre.size, n_taps=taps.size, out_shift=int(out_shift), first_sample=int(first_sample),
+              **{k: int(v) for k, v in ratio.items()})
+    return cfg, centre, taps
+
+
+def _wb_plan(plan, cfg, centre, taps):
+    """one of the four opv_*_plan calls: validates a plan and returns its K phase increments (uint32)"""
+    inc = np.zeros(max(centre.size, 1), np.uint32)
+    _chk(plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
+    return inc[:centre.size]
 
 
 def wb_plan(decim, centre_hz, taps, out_shift, first_sample=0):
     """opv_wb_plan: validates a plan and returns its K phase increments (uint32); host only, needs no device"""
-    cfg, centre, taps = _wb_args(decim, centre_hz, taps, out_shift, first_sample)
-    inc = np.zeros(max(centre.size, 1), np.uint32)
-    _chk(lib().opv_wb_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
-    return inc[:centre.size]
+    return _wb_plan(lib().opv_wb_plan, *_wb_cfg(WbCfg, centre_hz, taps, out_shift, first_sample, decim=decim))
 
 
 def wb_lo_table():
@@ -511,19 +519,10 @@ def wb_outputs(decim, n_wide_total):
     return int(lib().opv_wb_outputs(C.byref(cfg), int(n_wide_total)))
 
 
-def _wbr_args(down, up, centre_hz, taps, out_shift, first_sample):
-    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
-    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
-    return WbrCfg(int(down), int(up), centre.size, taps.size, int(out_shift), 0, int(first_sample)), centre, taps
-
-
 def wbr_plan(down, up, centre_hz, taps, out_shift, first_sample=0):
     """opv_wbr_plan: validates a plan of the rational door (wide rate 2 168 000 x down / up) and returns its K phase increments
     (uint32); host only, needs no device"""
-    cfg, centre, taps = _wbr_args(down, up, centre_hz, taps, out_shift, first_sample)
-    inc = np.zeros(max(centre.size, 1), np.uint32)
-    _chk(lib().opv_wbr_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
-    return inc[:centre.size]
+    return _wb_plan(lib().opv_wbr_plan, *_wb_cfg(WbrCfg, centre_hz, taps, out_shift, first_sample, down=down, up=up))
 
 
 def wbr_outputs(down, up, n_wide_total):
@@ -537,31 +536,26 @@ class Wideband:
     (opv_wb_*, include/opv_demod.h). Close it before its Demod."""
 
     def __init__(self, demod, decim, streams, centre_hz, taps, out_shift, first_sample=0):
-        self.demod = demod
-        self.cfg, centre, taps = _wb_args(decim, centre_hz, taps, out_shift, first_sample)
-        ids = (C.c_int * len(streams))(*[int(s) for s in streams])
-        if len(streams) != centre.size:
-            raise OpvError("Wideband: one centre frequency per stream")
-        self.h = C.c_void_p()
-        _chk(lib().opv_wb_create(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
-        self._inflight = []
-        demod._wideband.add(self)
+        self._create("Wideband", lib().opv_wb_create, demod, streams, _wb_cfg(WbCfg, centre_hz, taps, out_shift, first_sample, decim=decim))
 
     @classmethod
     def rational(cls, demod, down, up, streams, centre_hz, taps, out_shift, first_sample=0):
         """opv_wb_create_rational: the same object for a capture at 2 168 000 x down / up S/s (10 MS/s is 1250 / 271); `taps` is the
-        prototype filter at up x that rate. push / push_async / push_device / flush / close are the ones above."""
+        prototype filter at up x that rate. push / push_async / push_device / flush / close are the ones below."""
         self = cls.__new__(cls)
+        self._create("Wideband.rational", lib().opv_wb_create_rational, demod, streams, _wb_cfg(WbrCfg, centre_hz, taps, out_shift, first_sample, down=down, up=up))
+        return self
+
+    def _create(self, who, create, demod, streams, args):
         self.demod = demod
-        self.cfg, centre, taps = _wbr_args(down, up, centre_hz, taps, out_shift, first_sample)
+        self.cfg, centre, taps = args
         ids = (C.c_int * len(streams))(*[int(s) for s in streams])
         if len(streams) != centre.size:
-            raise OpvError("Wideband.rational: one centre frequency per stream")
+            raise OpvError(f"{who}: one centre frequency per stream")
         self.h = C.c_void_p()
-        _chk(lib().opv_wb_create_rational(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
+        _chk(create(C.byref(self.h), demod.h, C.byref(self.cfg), ids, centre.ctypes.data, taps.ctypes.data))
         self._inflight = []
         demod._wideband.add(self)
-        return self
 
     def push(self, iq_wide):
         iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
@@ -594,33 +588,15 @@ class Wideband:
 
 
 # ---------------------------------------------------------------- wideband transmit (opv_wbtx_*)
-def _wbtx_args(interp, centre_hz, taps, out_shift, first_sample):
-    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
-    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
-    return WbtxCfg(int(interp), centre.size, taps.size, int(out_shift), int(first_sample)), centre, taps
-
-
 def wbtx_plan(interp, centre_hz, taps, out_shift, first_sample=0):
     """opv_wbtx_plan: validates a plan and returns its K phase increments (uint32); host only, needs no device"""
-    cfg, centre, taps = _wbtx_args(interp, centre_hz, taps, out_shift, first_sample)
-    inc = np.zeros(max(centre.size, 1), np.uint32)
-    _chk(lib().opv_wbtx_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
-    return inc[:centre.size]
-
-
-def _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample):
-    centre = np.ascontiguousarray(centre_hz, np.float64).reshape(-1)
-    taps = np.ascontiguousarray(taps, np.int16).reshape(-1)
-    return WbtxrCfg(int(down), int(up), centre.size, taps.size, int(out_shift), 0, int(first_sample)), centre, taps
+    return _wb_plan(lib().opv_wbtx_plan, *_wb_cfg(WbtxCfg, centre_hz, taps, out_shift, first_sample, interp=interp))
 
 
 def wbtxr_plan(down, up, centre_hz, taps, out_shift, first_sample=0):
     """opv_wbtxr_plan: validates a plan of the rational up-converter bank (wide rate 2 168 000 x down / up) and returns its K phase
     increments (uint32): wbr_plan's for the same (down, up, centres); host only, needs no device"""
-    cfg, centre, taps = _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample)
-    inc = np.zeros(max(centre.size, 1), np.uint32)
-    _chk(lib().opv_wbtxr_plan(C.byref(cfg), centre.ctypes.data, taps.ctypes.data, inc.ctypes.data))
-    return inc[:centre.size]
+    return _wb_plan(lib().opv_wbtxr_plan, *_wb_cfg(WbtxrCfg, centre_hz, taps, out_shift, first_sample, down=down, up=up))
 
 
 def wbtxr_outputs(down, up, n_in_total):
@@ -634,10 +610,7 @@ class WidebandTx:
     wide capture (opv_wbtx_*, include/opv_demod.h). Close it before its Demod."""
 
     def __init__(self, demod, interp, centre_hz, taps, out_shift, first_sample=0):
-        self.demod = demod
-        self.cfg, centre, taps = _wbtx_args(interp, centre_hz, taps, out_shift, first_sample)
-        self.h = C.c_void_p()
-        _chk(lib().opv_wbtx_create(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
+        self._create(lib().opv_wbtx_create, demod, _wb_cfg(WbtxCfg, centre_hz, taps, out_shift, first_sample, interp=interp))
 
     @classmethod
     def rational(cls, demod, down, up, centre_hz, taps, out_shift, first_sample=0):
@@ -645,11 +618,14 @@ class WidebandTx:
         is the prototype filter at down x 2 168 000 S/s. push / samples / reset / close are the ones below; a push behind N inputs
         writes wbtxr_outputs(down, up, N + n_in) - wbtxr_outputs(down, up, N) wide samples."""
         self = cls.__new__(cls)
-        self.demod = demod
-        self.cfg, centre, taps = _wbtxr_args(down, up, centre_hz, taps, out_shift, first_sample)
-        self.h = C.c_void_p()
-        _chk(lib().opv_wbtx_create_rational(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
+        self._create(lib().opv_wbtx_create_rational, demod, _wb_cfg(WbtxrCfg, centre_hz, taps, out_shift, first_sample, down=down, up=up))
         return self
+
+    def _create(self, create, demod, args):
+        self.demod = demod
+        self.cfg, centre, taps = args
+        self.h = C.c_void_p()
+        _chk(create(C.byref(self.h), demod.h, C.byref(self.cfg), centre.ctypes.data, taps.ctypes.data))
 
     def push(self, d_in_ptrs, n_in, d_out_ptr):
         """opv_wbtx_push: d_in_ptrs[k] is channel k's device pointer to n_in samples, or None for a channel absent from this push;

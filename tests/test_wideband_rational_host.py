@@ -1,5 +1,5 @@
 """CPU-only: the host half of the rational wideband front door (include/opv_demod.h, opv_wbr_plan / opv_wbr_outputs /
-opv_wb_create_rational; the rules are csrc/opv_wbr_rules.cpp) against a numpy int64 restatement of the header's arithmetic. The
+opv_wb_create_rational; the rules are csrc/opv_wb_rules.cpp) against a numpy int64 restatement of the header's arithmetic. The
 model lives here (wbr_model_*), and tests/test_gpu_wideband_rational.py holds the device to the same functions with ==."""
 import ctypes as C
 import subprocess

@@ -1,5 +1,5 @@
 """CPU-only: the host half of the rational up-converter bank (include/opv_demod.h, opv_wbtxr_plan / opv_wbtxr_outputs /
-opv_wbtx_create_rational; the rules are csrc/opv_wbtxr_rules.cpp) against a numpy int64 restatement of the header's arithmetic.
+opv_wbtx_create_rational; the rules are csrc/opv_wb_rules.cpp) against a numpy int64 restatement of the header's arithmetic.
 The model lives here (wbtxr_model), and tests/test_gpu_wideband_tx_rational.py holds the device to it with ==. The increment rule
 is the rational door's (opv_wbr_plan): one definition serves both directions."""
 import ctypes as C

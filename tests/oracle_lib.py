@@ -440,17 +440,18 @@ class Reference:
         payload = np.zeros(CODED_BITS, np.float64)
         q = C.c_double(0)
         total = 0
+        step, pp, pq = L.ref_tracker_process, payload.ctypes.data, C.addressof(q)       # (one call per symbol: nothing rebuilt inside)
 
         def feed(s):
             nonlocal total
-            for i, v in enumerate(s):
-                if L.ref_tracker_process(tr, float(v), total + i, payload.ctypes.data, C.byref(q)):
+            for i, v in enumerate(s.tolist(), total):                                  # i: the symbol's index in the whole run
+                if step(tr, v, i, pp, pq):
                     m, fr = self.frame_decode(payload)
                     if m >= 0:
                         frames.append(fr)
                         metrics.append(m)
                         quality.append(q.value)
-                        fsym.append(total + i)
+                        fsym.append(i)
             total += len(s)
 
         def demod(view):

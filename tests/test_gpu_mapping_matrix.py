@@ -5,7 +5,7 @@ digital-silence / signed-zero rule (k_frontend_common.h: silence_pd), their own 
 scheduling under exec masks; the input classes this suite was built on reached only some of them. No comparison here is against another mapping of the
 product.
 
-The set (hostile_captures, 32 captures, 900 samples to 30 chunks, fixed seeds, built on the CPU from the oracle's transmit chain):
+The set (tests/hostile_inputs.py: hostile_captures, 32 captures, 900 samples to 30 chunks, fixed seeds, built on the CPU from the oracle's transmit chain):
 the eight pathological inputs (soak_inputs.pathological_captures), sample-clock errors of +/-3000 and +/-25 000 ppm, four
 channel-accident captures, the nudged and the un-nudged silence-gap capture, a carrier beyond the AFC clamp and one at its edge,
 3-4 LSB signals, a capture shorter than the 24-symbol sync word, ordinary 16 dB captures of mixed lengths (one an exact multiple of
@@ -23,24 +23,20 @@ chunk log at 1e-7 for the pathological and gapped captures (test_pathological_in
 test_many_silence_gaps_signed_zero_rule); up to the oracle's first one-tap window, and edge_ties >= 1, for the un-nudged capture
 (test_one_tap_windows_are_counted). In batch mode (another timing trajectory) a capture with runs of exact zeros is compared up
 to the oracle's first one-tap window, as test_many_silence_gaps_signed_zero_rule does."""
-from concurrent.futures import ProcessPoolExecutor
-from functools import partial
-
 import numpy as np
 import pytest
 
 from amd_lib import load
-from oracle_lib import accidents, impair, resample_clock
-from soak_inputs import host_workers, oracle_receive_job, pathological_captures
+from hostile_inputs import LONG, ambiguous, assert_set_is_hostile, hostile_captures, oracle_over
+from soak_inputs import host_workers
 from test_frontend_fp64_ring import make_demod
-from test_gpu_midrange_streams import CHUNK, PIECES, collect, explain
-from test_gpu_parity import _gapped_capture, check_stream, events_match, soft_err
+from test_gpu_midrange_streams import PIECES, collect, explain
+from test_gpu_parity import check_stream, events_match, soft_err
 
 pytestmark = pytest.mark.gpu
 
 SOFT_HOSTILE = 1e-8     # pathological / gapped captures (the bound their own tests carry)
 CARRY_ATOL = 1e-7       # float columns of the chunk log (fo, tf, mu), as everywhere in the suite
-LONG = "clamp+2600"     # the 30-frame capture: the one that keeps the push test running for >= 12 rounds
 
 
 @pytest.fixture(scope="module")
@@ -50,72 +46,7 @@ def amd():
     return m
 
 
-# ------------------------------------------------------------------ part 1: the set
-def hostile_captures(oracle):
-    """[(name, class, int16 IQ)]; class: "full" (check_stream), "patho" / "gap" (1e-8 + chunk log), "tie" (un-nudged gaps)"""
-    iq10 = oracle.modulate(oracle.bert_frames(10))
-    caps = [(f"patho{k}", "patho", x) for k, x in enumerate(pathological_captures(iq10))]
-    for ppm in (-25000.0, -3000.0, 3000.0, 25000.0):                         # test_timing_loop_slipping's recipe
-        caps.append((f"slip{ppm:+.0f}", "full", impair(resample_clock(iq10, ppm), amp=5000.0, f0_hz=-300.0, ebn0_db=20.0, seed=9)))
-    rng = np.random.default_rng(20261004)                                     # test_channel_accidents' recipe (its captures 0, 5, 6, 7)
-    for k in range(8):
-        base = oracle.modulate(oracle.bert_frames(int(rng.integers(6, 12)), "A%d" % k, first=40 * k))
-        amp = float(rng.uniform(400, 8000))
-        x = impair(base, amp=amp, f0_hz=float(rng.uniform(-1800, 1800)), ebn0_db=float(rng.uniform(10, 22)), seed=900 + k)
-        x = accidents(x, rng, amp)[0]
-        if k in (0, 5, 6, 7):
-            caps.append((f"accident{k}", "full", x))
-    caps.append(("gaps_nudged", "gap", _gapped_capture(oracle, iq10)[0]))
-    caps.append(("gaps_as_drawn", "tie", _gapped_capture(oracle, iq10, nudge=False)[0]))
-    caps.append((LONG, "full", impair(oracle.modulate(oracle.bert_frames(30, "CLAMP", first=7)), amp=3000.0, f0_hz=2600.0, ebn0_db=14.0, seed=41)))
-    caps.append(("edge-1990", "full", impair(oracle.modulate(oracle.bert_frames(6, "EDGE", first=3)), amp=1500.0, f0_hz=-1990.0, ebn0_db=6.0, seed=42)))
-    lsb = oracle.modulate(oracle.bert_frames(3, "LSB", first=11))
-    caps.append(("lsb_2_chunks", "patho", (lsb[: 2 * 2 * CHUNK] // 4000).astype(np.int16)))      # 3-4 LSB, exactly two chunks
-    caps.append(("short", "full", impair(iq10[: 2 * 900], amp=4000.0, f0_hz=250.0, ebn0_db=16.0, seed=43)))     # 22 symbols
-    # ordinary 16 dB captures: (frames, f0, amplitude, cut in samples or None)
-    for k, (F, f0, amp, cut) in enumerate([(1, 700.0, 2000.0, 50000), (5, -1100.0, 900.0, 4 * CHUNK), (3, 1500.0, 6000.0, None),
-                                           (5, -250.0, 12000.0, None), (8, 1900.0, 2500.0, None), (12, 40.0, 4000.0, None),
-                                           (4, -1400.0, 700.0, None), (7, 900.0, 3000.0, 6 * CHUNK + 33333), (2, -1800.0, 8000.0, None),
-                                           (9, -600.0, 5000.0, 3 * CHUNK - 1)]):
-        x = impair(oracle.modulate(oracle.bert_frames(F, "H%d" % k, first=500 + 17 * k)), amp=amp, f0_hz=f0, ebn0_db=16.0, seed=600 + k)
-        caps.append((f"ord{k}_{F}f", "full", x if cut is None else x[: 2 * cut]))
-    return caps
-
-
-def ambiguous(soft):
-    """one-tap windows as the oracle shows them: soft = -/+2^-31 against energies of ~1e10"""
-    return np.nonzero((soft != 0) & (np.abs(soft) < 1.0))[0]
-
-
-def oracle_over(caps, streaming):
-    with ProcessPoolExecutor(host_workers()) as pool:
-        return list(pool.map(partial(oracle_receive_job, want_soft=True, streaming=streaming), caps))
-
-
-def assert_set_is_hostile(names, classes, caps, exp_s, exp_b):
-    """what the set is FOR, said by the oracle alone before the product has seen an input"""
-    n = [c.size // 2 for c in caps]
-    assert 28 <= len(caps) <= 32 and min(n) < 24 * 40 and any(v < CHUNK for v in n) and any(v >= 12 * CHUNK for v in n)
-    assert any(v % CHUNK == 0 for v in n), "an exact multiple of the chunk length belongs to the set"
-    assert len(set(n)) >= 20, "mixed lengths"
-    kinds = set(int(v) for e in exp_s for v in e["events"]["kind"])
-    assert {1, 2, 3, 4, 5} <= kinds, kinds
-    clamp = [(names[j], int(np.sum(np.abs(e["chunks"][:, 0]) == 2000.0))) for j, e in enumerate(exp_s)]
-    assert any(c for _, c in clamp), "no demodulate() call ended with the AFC on its clamp"
-    left = set(int(v) for e in exp_s for v in e["chunks"][:-1, 3])
-    assert len(left) >= 8, left
-    tie, gap = names.index("gaps_as_drawn"), names.index("gaps_nudged")
-    assert ambiguous(exp_s[tie]["soft"]).size >= 1 and ambiguous(exp_s[gap]["soft"]).size == 0
-    per = [len(e["frames"]) for e in exp_s]
-    assert min(per) == 0 and max(per) >= 10, per
-    for e in exp_s + exp_b:
-        assert e["n_soft"] == len(e["soft"])
-    tf = max(float(np.max(np.abs(e["chunks"][:, 1]))) for e in exp_s + exp_b if len(e["chunks"]))
-    print(f"hostile set: {len(caps)} captures, {min(n)} .. {max(n)} samples; -s frames {sum(per)}; event kinds {sorted(kinds)}; calls ending on the "
-          f"AFC clamp {[c for c in clamp if c[1]]}; leftovers {sorted(left)}; one-tap windows in the un-nudged capture "
-          f"{ambiguous(exp_s[tie]['soft']).size}; largest |timing_freq| at a call boundary {tf:.1e}")
-
-
+# ------------------------------------------------------------------ part 1: the set (tests/hostile_inputs.py)
 @pytest.fixture(scope="module")
 def hostile():
     import time

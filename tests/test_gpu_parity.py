@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 from amd_lib import load
+from hostile_inputs import (AFC_ALPHA_FLAG, EXTREME_FLAGS, extreme_flags_capture, fuzz_captures, gapped_capture as _gapped_capture,
+                            near_tie_captures, staged_ties_capture)
 from oracle_lib import CODED_BITS, FRAME_BYTES, Oracle, channel_model, format_events, impair, resample_clock
 from soak_inputs import pathological_captures
 
@@ -139,12 +141,11 @@ def test_initial_offset_flag(amd, oracle, iq10):
     d.close()
 
 
-@pytest.mark.parametrize("off,alpha", [(6000.0, 0.001), (-2600.0, 0.001), (150000.0, 0.001), (300.0, 0.08), (0.0, 1.0),
-                                       (-700.0, 0.0), (100.0, -0.01)])
+@pytest.mark.parametrize("off,alpha", EXTREME_FLAGS)
 def test_extreme_flag_values(amd, oracle, iq10, off, alpha):
     """-o beyond the AFC clamp (the reference takes any value for the symbols before the first AFC update,
     :1004-1005 / :302-303) and -a so large that the loop slams into its clamp every symbol."""
-    x = impair(iq10, amp=3000.0, f0_hz=400.0, ebn0_db=18.0, seed=77)
+    x = extreme_flags_capture(iq10)
     for frontend in (1, 4, 16):
         d = amd.Demod(1, max_samples=x.size // 2 + 64, streaming=True, init_offset=off, afc_alpha=alpha)
         d.set_frontend(frontend)
@@ -169,9 +170,9 @@ def test_timing_loop_slipping(amd, oracle, iq10, ppm):
 
 
 def test_afc_alpha_flag(amd, oracle, iq10):
-    d = amd.Demod(1, max_samples=iq10.size // 2 + 64, streaming=True, afc_alpha=0.01)
+    d = amd.Demod(1, max_samples=iq10.size // 2 + 64, streaming=True, afc_alpha=AFC_ALPHA_FLAG)
     got = d.receive([iq10])[0]
-    check_stream(amd, got, oracle.receive(iq10, streaming=True, afc_alpha=0.01), "-a 0.01")
+    check_stream(amd, got, oracle.receive(iq10, streaming=True, afc_alpha=AFC_ALPHA_FLAG), "-a 0.01")
     d.close()
 
 
@@ -206,17 +207,7 @@ def test_offset_search_near_tie_guard(amd, oracle, iq10):
     winner (first maximum, strict '>') is decided by the rounding of its own 40 000-sample phase accumulation. The
     one-pass evaluation (agreement ~1e-13) cannot call that; its near-tie guard must notice (offset_ties >= 2)
     and re-evaluate the contenders in the reference's order of operations - and then return the oracle's estimate."""
-    rng = np.random.default_rng(2024)
-    caps = []
-    t = np.arange(86720)
-    # real tones well outside the +/-13.55 kHz pair: two window main lobes 2 x 20..33 kHz apart add up to a landscape
-    # that is convex at o = 0, so its maximum is the tied pair of edge candidates -1500 / +1500
-    for f_hz, amp in ((33550.0, 9000.0), (36000.0, 20000.0), (42000.0, 3000.0), (47000.0, 12000.0)):
-        x = np.zeros(2 * 86720, np.int16); x[0::2] = np.rint(amp * np.cos(2 * np.pi * f_hz * t / 2168000.0 + 0.3)); caps.append(x)
-    x = np.zeros(2 * 86720, np.int16); x[0::2] = np.rint(8000 * np.cos(2 * np.pi * 33550.0 * t / 2168000.0) + 300 * rng.standard_normal(86720)); caps.append(x)
-    x = np.zeros(2 * 86720, np.int16); x[0::2] = np.clip(np.rint(rng.standard_normal(86720) * 50), -32768, 32767); caps.append(x)   # real noise
-    x = iq10[: 2 * 86720].copy(); x[1::2] = 0; caps.append(x)                       # I branch of the MSK capture: peak at 0, no tie
-    x = np.zeros(2 * 86720, np.int16); x[0::2] = 12345; caps.append(x)              # DC: peak at 0, no tie
+    caps = near_tie_captures(iq10)             # (tests/hostile_inputs.py: four real tones, one with noise, real noise, two controls)
     d = amd.Demod(len(caps), max_samples=86720 + 64, streaming=True)
     got = d.receive(caps)
     n_guarded = 0
@@ -516,8 +507,7 @@ def test_more_ties_in_one_round_than_the_host_passes_stage(amd, oracle):
     are counted, and (an exact mirror tie survives any odd / even sin / cos) every estimate equals the oracle's either way."""
     import torch
     S, n = 4200, 4000
-    x = np.zeros(2 * n, np.int16)
-    x[0::2] = np.rint(9000 * np.cos(2 * np.pi * 36000.0 * np.arange(n) / 2168000.0 + 0.3))
+    x = staged_ties_capture(n)
     off, e = oracle.estimate_offset(x, energies=True)
     assert off in (-1530.0, 1530.0)                                  # (a convex, exactly symmetric landscape: the edges tie)
     d_x = torch.from_numpy(x).to("cuda")
@@ -1645,40 +1635,6 @@ def test_pathological_inputs_match_the_oracle(amd, oracle, iq10):
         d.close()
 
 
-def _gapped_capture(oracle, iq10, nudge=True):
-    """10 frames, 1.2 kHz off tune, ~300 gaps of exact zeros. With nudge=True, gap edges that would leave a
-    symbol window with ONE non-zero tap are moved until the oracle sees none (see the tests below)."""
-    base = impair(iq10, amp=6000.0, f0_hz=1200.0).reshape(-1, 2)
-    rng = np.random.default_rng(5)
-    pos, gaps = 3000, []
-    while pos + 400 < base.shape[0]:
-        glen = int(rng.integers(105, 260))          # >= one whole 60-sample correlation window of zeros
-        gaps.append([pos, glen])
-        pos += glen + int(rng.integers(1500, 4000))
-
-    def build():
-        z = base.copy()
-        for p, n in gaps:
-            z[p:p + n] = 0
-        return z.reshape(-1)
-
-    if not nudge:
-        return build(), [g[0] for g in gaps]
-    for _ in range(200):
-        x = build()
-        soft = oracle.receive(x, streaming=True)["soft"]
-        amb = np.nonzero((soft != 0) & (np.abs(soft) < 1.0))[0]            # energies are ~1e10
-        if amb.size == 0:
-            return x, [g[0] for g in gaps]
-        at = 40 * int(amb[0])                                                # roughly the sample position
-        j = int(np.argmin([min(abs(p - at), abs(p + n - at)) for p, n in gaps]))
-        if abs(gaps[j][0] - at) < abs(gaps[j][0] + gaps[j][1] - at):
-            gaps[j][0] -= 3; gaps[j][1] += 3                                 # leading edge 3 samples earlier
-        else:
-            gaps[j][1] += 3                                                  # trailing edge 3 samples later
-    raise AssertionError("could not remove the tie symbols")
-
-
 @pytest.mark.gpu
 def test_many_silence_gaps_signed_zero_rule(amd, oracle, iq10):
     """Hundreds of digital-silence gaps inside a capture that sits 1.2 kHz off tune: every gap edge
@@ -1837,16 +1793,7 @@ def test_reference_makefile_targets_with_our_binaries():
 def test_clock_rate_error_and_random_channels_fuzz(amd, oracle, iq10, iq100, seed):
     """Differential fuzz: 24 streams in one context, each with its own sample-clock error (the timing
     loop then drifts through integer sample boundaries, the chunk grid moves: leftovers from 18 to 50), carrier offset, level, Eb/N0 and a random truncation point; both -s and batch mode."""
-    rng = np.random.default_rng(seed)
-    caps = []
-    for k in range(24):
-        base = iq100[: 2 * 86720 * 14] if k % 3 == 0 else iq10
-        ppm = float(rng.choice([-400.0, -120.0, -35.0, 0.0, 7.0, 60.0, 250.0, 900.0]))
-        x = resample_clock(base, ppm) if ppm else base
-        x = impair(x, amp=float(rng.uniform(300, 9000)), f0_hz=float(rng.uniform(-2100, 2100)),
-                   ebn0_db=float(rng.uniform(9, 24)), seed=seed % 1000 + k)
-        cut = int(rng.integers(x.size // 4, x.size // 2)) if k % 4 == 1 else x.size // 2
-        caps.append(x[: 2 * cut])
+    caps = fuzz_captures(seed, iq10, iq100)
     nmax = max(c.size // 2 for c in caps)
     for streaming in (True, False):
         d = amd.Demod(len(caps), max_samples=nmax + 64, streaming=streaming)

@@ -77,8 +77,8 @@ def to_wide(z):
     return wide
 
 
-def make_plan_capture(amd, oracle, n_frames):
-    """-> dict(wide, taps, tx[k], model[k] (int16 IQ per slot), exp[k] (the oracle on model[k]))"""
+def make_plan_wide(amd, n_frames):
+    """-> (wide int16 IQ, tx[k]): the plan's channels side by side at 10 MS/s, before the door (host code only)"""
     M, U, centres = PLAN["down"], PLAN["up"], PLAN["centres"]
     fw = M * WIDE_RATE / U
     tx, z = {}, None
@@ -86,7 +86,13 @@ def make_plan_capture(amd, oracle, n_frames):
         tx[k], zk = make_channel(amd, k, n_frames)
         zk = zk * np.exp(2j * np.pi * centres[k] / fw * np.arange(zk.size, dtype=np.float64))
         z = zk if z is None else z + zk
-    wide = to_wide(z)
+    return to_wide(z), tx
+
+
+def make_plan_capture(amd, oracle, n_frames):
+    """-> dict(wide, taps, tx[k], model[k] (int16 IQ per slot), exp[k] (the oracle on model[k]))"""
+    M, U, centres = PLAN["down"], PLAN["up"], PLAN["centres"]
+    wide, tx = make_plan_wide(amd, n_frames)
     taps = plan_taps()
     model = wbr_model(amd.wb_lo_table(), wide, M, U, wbr_model_inc(M, U, centres), taps, PLAN["out_shift"])
     exp = [oracle.receive(model[k], streaming=True) for k in range(len(centres))]

@@ -196,7 +196,7 @@ int opv_push_wait(opv_ctx* ctx);
  * Replaces nothing in the reference, which starts at one channel's baseband. A radio delivers one wideband capture with many OPV
  * channels side by side; an opv_wb object is a bank of K digital down-converters on the device, so that the capture crosses PCIe
  * once and each channel arrives in its stream's device buffer as if it had been pushed with opv_push_iq. The arithmetic is
- * integer-exact and independent of summation order (tests/test_gpu_wideband.py holds the device to a numpy int64 model with ==):
+ * integer-exact and independent of summation order (tests/test_gpu_wideband.py holds the device to the numpy int64 model of tests/wideband_models.py with ==):
  *   wide samples x[n] = (I, Q) int16 at decim x 2 168 000 S/s, n = 0 at the first sample pushed into the object, a = first_sample + n;
  *   per channel k: inc_k = (uint32) llrint(centre_hz[k] / (decim x 2 168 000) x 2^32) (modulo 2^32: negative centres wrap),
  *     phi = (uint32)(a x inc_k) (a closed form: no accumulator is carried), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095] with
@@ -585,7 +585,7 @@ int opv_tap_txb_patch(uint64_t symbol, int sample, int code, int16_t out_iq[2]);
  * The mirror image of opv_wb_*, and the stage behind the transmit bank: opv_txb_round leaves per-channel int16 captures at
  * 2 168 000 S/s in device memory; an opv_wbtx object is a bank of K digital up-converters on the device that puts them on one
  * carrier raster at interp x 2 168 000 S/s. The arithmetic is integer-exact and independent of summation order
- * (tests/test_gpu_wideband_tx.py holds the device to a numpy int64 model with ==):
+ * (tests/test_gpu_wideband_tx.py holds the device to the numpy int64 model of tests/wideband_models.py with ==):
  *   every channel delivers the same number of input samples x_k[m] = (I, Q) int16 per push, m = 0 at the first sample pushed into the
  *   object, x_k[m] = 0 for m < 0; after N input samples per channel the object has written exactly N x interp wide samples.
  *   Wide sample n = q interp + p (0 <= p < interp) has the absolute index a = first_sample + n. Per channel k and component:

@@ -41,7 +41,7 @@ def oracle_one(args):
 
 def main():
     from amd_lib import load
-    import test_gpu_parity as T
+    import stream_checks as T
     amd = load()
     runs = bad = frames = edge = 0
     kinds = {}

@@ -5,7 +5,7 @@ repetitions after one warm-up, host clock (time.perf_counter) around a synchrono
   up   K = 64 / 256 channels x 86 720 input samples (one frame each), U = 4, L = 321  ->  346 880 wide samples
   down the same 346 880 wide samples, D = 4, K = 64 / 256, L = 321                    ->  86 720 samples per stream
 
-Inputs are random int16 (seeded), the taps the 321-tap Hamming sinc of tests/test_gpu_wideband.py. The HBM bytes each direction
+Inputs are random int16 (seeded), the taps the 321-tap Hamming sinc of tests/wideband_device.py (PLAN_D4). The HBM bytes each direction
 has to move are printed beside the times: 4 K n_in read + 4 n_in U written going up, 4 n_in U read + 4 K n_in written coming down.
 The kernels' own durations come from a separate run of the same command under the profiler:
 

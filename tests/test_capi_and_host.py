@@ -9,14 +9,9 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amd_lib import ROOT, load
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
+from amd_lib import ROOT
+from fixtures_built import amd  # noqa: F401
+from struct_layout import check_ctypes_layout, header_layout
 
 
 def declared_symbols():
@@ -37,27 +32,15 @@ def test_library_exports_every_declared_symbol(amd):
 
 def test_struct_layouts_match_header(amd, tmp_path):
     """sizes and field offsets of the ctypes / numpy mirrors against what gcc makes of include/opv_demod.h"""
-    import subprocess
-    fields = {"opv_cfg": [f[0] for f in amd.Cfg._fields_], "opv_stream_state": [f[0] for f in amd.StreamState._fields_],
-              "opv_frame_meta": list(amd.META_DTYPE.names), "opv_event": list(amd.EVENT_DTYPE.names)}
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "opv_demod.h"}"', "int main(void){"]
-    for st, fs in fields.items():
-        src.append(f'printf("{st} %zu\\n", sizeof({st}));')
-        src += [f'printf("{st}.{f} %zu\\n", offsetof({st}, {f}));' for f in fs]
-    src.append("return 0;}")
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["opv_cfg"]) == C.sizeof(amd.Cfg) and int(got["opv_stream_state"]) == C.sizeof(amd.StreamState)
-    assert int(got["opv_frame_meta"]) == amd.META_DTYPE.itemsize == 32 and int(got["opv_event"]) == amd.EVENT_DTYPE.itemsize == 32
-    for f in fields["opv_cfg"]:
-        assert int(got[f"opv_cfg.{f}"]) == getattr(amd.Cfg, f).offset, f
-    for f in fields["opv_stream_state"]:
-        assert int(got[f"opv_stream_state.{f}"]) == getattr(amd.StreamState, f).offset, f
-    for f in fields["opv_frame_meta"]:
-        assert int(got[f"opv_frame_meta.{f}"]) == amd.META_DTYPE.fields[f][1], f
-    for f in fields["opv_event"]:
-        assert int(got[f"opv_event.{f}"]) == amd.EVENT_DTYPE.fields[f][1], f
+    for cls, c_name in ((amd.Cfg, "opv_cfg"), (amd.StreamState, "opv_stream_state")):     # (no size of their own to pin: gcc's == ctypes')
+        check_ctypes_layout(tmp_path, cls, c_name, C.sizeof(cls), [f[0] for f in cls._fields_])
+    dtypes = {"opv_frame_meta": amd.META_DTYPE, "opv_event": amd.EVENT_DTYPE}
+    got = header_layout(tmp_path, {st: list(dt.names) for st, dt in dtypes.items()})
+    for st, dt in dtypes.items():
+        size, offsets = got[st]
+        assert size == dt.itemsize == 32
+        for f in dt.names:
+            assert offsets[f] == dt.fields[f][1], f
 
 
 def test_no_gpu_means_loud_failure_not_fallback(amd):

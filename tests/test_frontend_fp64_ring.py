@@ -4,26 +4,18 @@ hook OPV_FRONTEND_INT16_RING). The interpolation sees the same operands either w
 for bit: soft symbols, the chunk carry {fo, tf, mu, leftover, nsym}, the stream state (origin included), frames, Viterbi
 metrics and tracker events."""
 import importlib.util
-import struct
 import sys
 from pathlib import Path
 
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
+from stream_runs import CHUNK, assert_same, base_capture, collect_bits, make_demod, state_tuple
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 PKG = ROOT / "opv-cxx-demod_amd"
-CHUNK = 86720          # OPV_CHUNK_SAMPLES
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 def workload_mod():
@@ -33,35 +25,6 @@ def workload_mod():
         sys.modules["workload"] = mod
         spec.loader.exec_module(mod)
     return sys.modules["workload"]
-
-
-def make_demod(amd, monkeypatch, int16, S, **kw):
-    if int16:
-        monkeypatch.setenv("OPV_FRONTEND_INT16_RING", "1")
-    else:
-        monkeypatch.delenv("OPV_FRONTEND_INT16_RING", raising=False)
-    try:
-        return amd.Demod(S, **kw)
-    finally:
-        monkeypatch.delenv("OPV_FRONTEND_INT16_RING", raising=False)
-
-
-def state_tuple(st):
-    # floats by their bits: est_offset_hz is NaN where no offset search ran, and NaN != NaN
-    return tuple(struct.pack("<d", v) if isinstance(v, float) else v for v in (getattr(st, f) for f, _ in st._fields_))
-
-
-def collect(d, s):
-    fr, meta = d.pop_frames(s)
-    return dict(frames=fr, meta=meta, events=d.pop_events(s), soft=d.soft(s), state=state_tuple(d.state(s)), chunks=d.chunks(s))
-
-
-def assert_same(a, b, what):
-    assert a["state"] == b["state"], what
-    for k in ("soft", "chunks", "frames", "meta", "events"):
-        x, y = a[k], b[k]
-        assert x.shape == y.shape, (what, k)
-        assert x.tobytes() == y.tobytes(), (what, k)      # bit for bit (NaN-safe, -0.0 distinct)
 
 
 def run_host(amd, monkeypatch, captures, int16, streaming=True, **kw):
@@ -86,12 +49,6 @@ def compare_host(amd, monkeypatch, captures, label, **kw):
     return got
 
 
-def base_capture(amd, frames=3, seed=0, sigma=300.0):
-    iq = amd.modulate(amd.bert_frames(frames)).astype(np.float64)
-    rng = np.random.default_rng(seed)
-    return np.clip(np.rint(iq + sigma * rng.standard_normal(iq.shape)), -32768, 32767).astype(np.int16)
-
-
 def test_fp64_ring_workload_64_streams_bit_identical(amd, monkeypatch):
     """the headline shape at 20 frames: 64 streams of workload.generate at 16 dB, the +/-2 kHz clamp streams included"""
     import torch
@@ -110,7 +67,7 @@ def test_fp64_ring_workload_64_streams_bit_identical(amd, monkeypatch):
             d.process()
             d.sync()
             assert d.frontend_kernel() == "k_msk_frontend_rb"
-            res[int16] = [collect(d, k) for k in range(S)]
+            res[int16] = [collect_bits(d, k) for k in range(S)]
             assert all(not r["state"][15] for r in res[int16])   # stalled
         finally:
             d.close()
@@ -169,7 +126,7 @@ def test_fp64_ring_odd_pushes_over_many_calls(amd, monkeypatch):
                         d.flush(s)
                 d.process()
                 d.sync()
-                rounds.append([collect(d, s) for s in range(3)])
+                rounds.append([collect_bits(d, s) for s in range(3)])
             res[int16] = rounds
         finally:
             d.close()

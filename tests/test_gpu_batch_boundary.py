@@ -20,8 +20,8 @@ batches are cut by tile events at fixed sample positions):
     them and for the symbol behind them, some 300 times, spread over the four slots of a trip by the gaps' random spacing;
  5. an out-of-range -o: the second-symbol instantiation followed directly by batches of whole trips.
 
-Bounds: test_gpu_parity.check_stream as it stands (soft symbols < 1e-9 of their mean, decisions and integer columns ==, the chunk
-log's float columns 1e-7), for the gapped capture test_gpu_mapping_matrix.check_capture's "gap" class as it stands (soft 1e-8 of
+Bounds: stream_checks.check_stream as it stands (soft symbols < 1e-9 of their mean, decisions and integer columns ==, the chunk
+log's float columns 1e-7), for the gapped capture stream_runs.check_capture's "gap" class as it stands (soft 1e-8 of
 the mean, edge_ties <= 12); against the int16 ring and between two segmentations: identity."""
 from concurrent.futures import ProcessPoolExecutor
 from functools import partial
@@ -29,25 +29,16 @@ from functools import partial
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
+from hostile_inputs import ambiguous
 from oracle_lib import impair
 from soak_inputs import host_workers, oracle_receive_job
-from test_frontend_fp64_ring import assert_same, make_demod, state_tuple
-from test_gpu_mapping_matrix import ambiguous, check_capture
-from test_gpu_parity import _gapped_capture, check_stream
-from test_gpu_stream_migration import drain, new_acc, result
-from test_gpu_symbol_body import CAP_SOFT, SMALL_M, WRAP_PIECES
+from stream_checks import _gapped_capture, check_stream
+from stream_runs import (CAP_SOFT, CHUNK, SMALL_M, WRAP_PIECES, assert_same, check_capture, drain, make_demod, new_acc, result,
+                         state_tuple)
 
 pytestmark = pytest.mark.gpu
-CHUNK = 86720
 WHOLE = [1 << 30]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -31,12 +31,12 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from link_model import CODED, check_record, link_model
 from oracle_lib import accidents, impair
-from test_frontend_fp64_ring import make_demod, state_tuple
-from test_gpu_parity import _gapped_capture, events_match, soft_err
-from test_gpu_stream_migration import CHUNK, HUNTING, LOCKED, drain, feed, held_to_the_oracle, new_acc, result, tracker_at
+from stream_checks import _gapped_capture, events_match, soft_err
+from stream_runs import (CHUNK, HUNTING, LOCKED, drain, feed, held_to_the_oracle, make_demod, new_acc, result, state_tuple,
+                         tracker_at)
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -48,13 +48,6 @@ CUT = 2 * CHUNK + 20000
 # (id, int16 ring forced, opv_set_frontend, the kernel a round must have launched)
 DESTS = [("rb_f64", False, 1, "k_msk_frontend_rb"), ("rb_i16", True, 1, "k_msk_frontend_rb"), ("x4", False, 4, "k_msk_frontend_x4_wg4"),
          ("x16", False, 16, "k_msk_frontend_x16_wg4")]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")

@@ -4,8 +4,8 @@ the automatic shape while a context has no more streams than the device has CUs)
 read by opv_create: ONE child process started with it runs all cases once, module fixture) and through the CPU oracle:
 
   fp64 ring == int16 ring   bit for bit, per round: soft symbols, the per-call carry {fo, tf, mu, leftover, nsym}, the stream
-                            state, frames, Viterbi metrics, tracker events (test_frontend_fp64_ring.assert_same)
-  fp64 ring vs the oracle   test_gpu_parity.check_stream in full (frames, metrics, sync positions, events, symbol count, every
+                            state, frames, Viterbi metrics, tracker events (stream_runs.assert_same)
+  fp64 ring vs the oracle   stream_checks.check_stream in full (frames, metrics, sync positions, events, symbol count, every
                             soft symbol < SOFT_TIGHT, carry), nothing stalled
   overflow == 0             opv_get_state / opv_pop_frames fail on a stream whose hand-over timed out (overflow = 2)
 
@@ -29,11 +29,11 @@ import numpy as np
 import pytest
 
 from amd_lib import load
-from test_frontend_fp64_ring import assert_same, base_capture, state_tuple
-from test_gpu_parity import check_stream
+from fixtures import amd  # noqa: F401
+from stream_checks import check_stream
+from stream_runs import CHUNK, assert_same, base_capture, collect_unstalled
 
 pytestmark = pytest.mark.gpu
-CHUNK = 86720                  # OPV_CHUNK_SAMPLES
 L0 = 391 * 256
 R = (0, 1, 2, 127, 128, 129, 130, 255)
 PIECE = 100003
@@ -59,14 +59,6 @@ def make_cases(amd):
     return cases
 
 
-def collect(d, s):
-    fr, meta = d.pop_frames(s)               # (fails on a stream in an error state: overflow != 0)
-    st = d.state(s)
-    assert st.stalled == 0, (s, st.stalled)
-    return dict(frames=fr, meta=meta, events=d.pop_events(s), soft=d.soft(s), state=state_tuple(st), chunks=d.chunks(s),
-                total_symbols=int(st.total_symbols), st=[getattr(st, f) for f, _ in st._fields_])
-
-
 def run_case(amd, captures, piece):
     """one context; per round (one opv_process) the results of every stream"""
     S = len(captures)
@@ -86,7 +78,7 @@ def run_case(amd, captures, piece):
             d.process()
             d.sync()
             assert d.frontend_kernel() == "k_msk_frontend_rb"
-            rounds.append([collect(d, s) for s in range(S)])
+            rounds.append([collect_unstalled(d, s) for s in range(S)])
             if at >= max(n):
                 return rounds
     finally:
@@ -95,13 +87,6 @@ def run_case(amd, captures, piece):
 
 def run_all(amd, cases):
     return {name: run_case(amd, caps, piece) for name, (caps, piece) in cases.items()}
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")

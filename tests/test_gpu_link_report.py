@@ -11,25 +11,15 @@ import numpy as np
 import pytest
 
 import soft_log_inputs as S
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from link_model import CODED, check_record, link_model
 from oracle_lib import impair
+from stream_runs import code_of
 
 pytestmark = pytest.mark.gpu
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
 SMALL = 32                                     # max_samples: cap_soft 4096, cap_frames 4
 MID = 330000                                   # cap_soft 16384, cap_frames 8
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-def code_of(err):
-    return int(str(err).split("opv error ")[1].split(":")[0])
 
 
 class DevPtr:

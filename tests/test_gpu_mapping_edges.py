@@ -6,24 +6,17 @@ name is a literal of this file (tests/test_round_rules_host.py holds the rule it
 At most one side of an edge fills its last workgroup; on the other that workgroup serves a single stream. So each context gets
 the suite's clean 10-frame capture (iq10) on its FIRST and its LAST stream only - every other stream receives nothing (idle slots
 beside running ones: what the late-armed rows of test_gpu_mapping_matrix exercise) - and both are held to the oracle with
-test_gpu_parity.check_stream in full: frames, metrics, release symbols, events, symbol count, every soft symbol, estimate, final
+stream_checks.check_stream in full: frames, metrics, release symbols, events, symbol count, every soft symbol, estimate, final
 carry and the chunk log."""
 import time
 
 import pytest
 
-from amd_lib import load
-from test_gpu_midrange_streams import collect, explain
-from test_gpu_parity import check_stream
+from fixtures import amd  # noqa: F401
+from stream_checks import check_stream
+from stream_runs import collect, explain
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")

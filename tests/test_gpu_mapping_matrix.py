@@ -17,7 +17,7 @@ NOT covered: the timing loop's clamps (timing_freq +/-0.1, timing_adj +/-2). Wit
 |timing_adj| is at most 0.105, and the largest |timing_freq| at a call boundary over this whole set is 2.4e-3: no capture
 reaches either clamp.
 
-Bounds: only what the suite already carries for the same capture class - test_gpu_parity.check_stream in full (soft symbols <
+Bounds: only what the suite already carries for the same capture class - stream_checks.check_stream in full (soft symbols <
 SOFT_TIGHT = 1e-9 of their mean, everything else ==) for ordinary, slipping, accident, clamp and short captures; 1e-8 plus the
 chunk log at 1e-7 for the pathological and gapped captures (test_pathological_inputs_match_the_oracle,
 test_many_silence_gaps_signed_zero_rule); up to the oracle's first one-tap window, and edge_ties >= 1, for the un-nudged capture
@@ -26,24 +26,12 @@ to the oracle's first one-tap window, as test_many_silence_gaps_signed_zero_rule
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from hostile_inputs import LONG, ambiguous, assert_set_is_hostile, hostile_captures, oracle_over
 from soak_inputs import host_workers
-from test_frontend_fp64_ring import make_demod
-from test_gpu_midrange_streams import PIECES, collect, explain
-from test_gpu_parity import check_stream, events_match, soft_err
+from stream_runs import PIECES, check_capture, collect, explain, make_demod
 
 pytestmark = pytest.mark.gpu
-
-SOFT_HOSTILE = 1e-8     # pathological / gapped captures (the bound their own tests carry)
-CARRY_ATOL = 1e-7       # float columns of the chunk log (fo, tf, mu), as everywhere in the suite
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 # ------------------------------------------------------------------ part 1: the set (tests/hostile_inputs.py)
@@ -64,46 +52,7 @@ def hostile():
     return dict(names=names, classes=classes, caps=caps, exp=exp, nmax=max(c.size // 2 for c in caps))
 
 
-# ------------------------------------------------------------------ the check of one stream
-def check_capture(amd, got, exp, cls, tag, streaming=True):
-    """One stream against the oracle's result for its capture, by the capture's class (module docstring); -> its soft error."""
-    st = got["state"]
-    assert st.stalled == 0, f"{tag}: stalled 0x{st.stalled:x}"
-    if cls == "full":
-        check_stream(amd, got, exp, tag, edge_ties=0, offset_ties=None)
-        return soft_err(got["soft"], exp["soft"])[0]
-    n_soft = exp["n_soft"]
-    # up to the oracle's first one-tap window. In -s mode only the un-nudged capture is cut short by that: the nudged one has none,
-    # and the pathological ones are compared in full, as test_pathological_inputs_match_the_oracle compares them (its capture 5,
-    # the signal that stops and resumes, has one such window at symbol 4249, after which that test holds the product to 1e-8 too)
-    cut = exp["amb"].size and not (cls == "patho" and streaming)
-    k_end = int(exp["amb"][0]) if cut else n_soft
-    assert st.total_symbols == n_soft and len(got["soft"]) == n_soft, f"{tag}: {st.total_symbols} symbols, oracle {n_soft}"
-    scale = np.mean(np.abs(exp["soft"])) + 1e-300
-    a = float(np.max(np.abs(got["soft"][:k_end] - exp["soft"][:k_end]))) / scale if k_end else 0.0
-    assert a < SOFT_HOSTILE, f"{tag}: soft error {a:.3e} before symbol {k_end}"
-    e0, e1 = st.est_offset_hz, exp["est_offset"]
-    assert (np.isnan(e0) and np.isnan(e1)) or e0 == e1, f"{tag}: offset estimate {e0} vs {e1}"
-    ch, ech = got["chunks"], exp["chunks"]
-    done = np.nonzero(np.cumsum(ech[:, 4]) <= k_end)[0]                    # demodulate() calls that ended before k_end
-    assert len(ch) >= done.size, f"{tag}: {len(ch)} chunk rows"
-    for c in done:
-        assert np.array_equal(ch[c, 3:], ech[c, 3:]), f"{tag}: call {c}: leftover / symbols {ch[c, 3:]} vs {ech[c, 3:]}"
-        assert np.allclose(ch[c, :3], ech[c, :3], rtol=0, atol=CARRY_ATOL), f"{tag}: call {c}: {ch[c]} vs {ech[c]}"
-    if cls == "tie" and exp["amb"].size:
-        assert st.edge_ties >= 1, f"{tag}: the oracle shows {exp['amb'].size} one-tap windows, edge_ties {st.edge_ties}"
-    if cls == "gap":
-        assert st.edge_ties <= 12, f"{tag}: edge_ties {st.edge_ties} on the nudged capture"
-    if k_end == n_soft:                                                    # nothing ambiguous: every decision too
-        assert ch.shape == ech.shape, f"{tag}: chunk log {ch.shape} vs {ech.shape}"
-        assert np.array_equal(got["frames"], exp["frames"]), f"{tag}: decoded bytes differ"
-        assert np.array_equal(got["meta"]["viterbi_metric"], exp["metrics"]), f"{tag}: Viterbi metrics differ"
-        assert np.array_equal(got["meta"]["release_symbol"], exp["frame_sym"]), f"{tag}: sync positions differ"
-        events_match(amd, got["events"], exp["events"])
-        assert abs(st.freq_offset_hz - exp["final_freq_offset"]) < 1e-6 and st.sync_state == exp["final_state"], tag
-    return a
-
-
+# ------------------------------------------------------------------ the check of one stream (stream_runs.check_capture, by the capture's class)
 def check_all(amd, d, ks, js, hostile, streaming, tag, results):
     """streams ks of context d carry captures js; results: [(soft error, label)] and the guard count, appended to"""
     for k, j in zip(ks, js):
@@ -195,7 +144,7 @@ def test_hostile_set_on_every_launch_shape(amd, hostile, monkeypatch, shape, arr
 # ------------------------------------------------------------------ part 3: rows on diverging schedules
 @pytest.mark.parametrize("shape", ["x4_wg4", "x16_wg4", "rb_int16_ring"])
 def test_rows_on_diverging_schedules_over_many_rounds(amd, hostile, monkeypatch, shape):
-    """The set through opv_push_iq in rounds (push sizes cycle through test_gpu_midrange_streams.PIECES, opv_process + opv_sync after
+    """The set through opv_push_iq in rounds (push sizes cycle through stream_runs.PIECES, opv_process + opv_sync after
     each), so that the rows of a wave are on different schedules in every launch: stream k's first push is k % 41 samples shorter;
     the streams with k % 4 == 3 get nothing before round 5 (idle rows, armed beside running ones); every stream is flushed when
     its capture runs out (900 samples to 30 chunks: rows fall idle round by round while their wave-mates go on); and in round 3 one

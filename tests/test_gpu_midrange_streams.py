@@ -2,7 +2,7 @@
 (csrc/opv_round_rules.h, frontend_choice: 128 threads and an fp64 LDS ring a helper wave fills while the context has no more streams
 than the device has CUs; 64 threads and the int16 ring beyond) - held to the ORACLE at length: every stream of every
 context, every soft symbol, the chunk carry, the tracker's lines, the estimate and the final state, with the bounds
-test_gpu_parity.check_stream / events_match already carry. No comparison here is against another mapping of the product.
+stream_checks.check_stream / events_match already carry. No comparison here is against another mapping of the product.
 
 Inputs: workload.generate (per-stream payload, carrier offsets -2000 .. +2000 Hz with the two AFC-clamp streams in every 64,
 16 dB), two sets, because a prefix of a capture has another EOF tail and therefore another oracle result:
@@ -18,30 +18,18 @@ import threading
 from concurrent.futures import ProcessPoolExecutor
 from functools import partial
 
-import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from soak_inputs import host_workers, oracle_receive_job
-from test_frontend_fp64_ring import make_demod
-from test_gpu_parity import SOFT_TIGHT, check_stream, soft_err
+from stream_checks import check_stream, soft_err
+from stream_runs import CHUNK, PIECES, collect, explain, make_demod
 
 pytestmark = pytest.mark.gpu
 
 EBN0 = 16.0
 S_LONG, F_LONG = 192, 50
 F_WIDE = 12
-CHUNK = 86720          # OPV_CHUNK_SAMPLES
-# part 3, samples per push and round: one below a symbol (40 samples), odd ones, one chunk -1 / +0 / +1, primes above 100 000,
-# multiples of 256 (what the helper wave publishes at a time)
-PIECES = [104729, 39, 86719, 262144, 86720, 7919, 86721, 1000003, 256, 20011, 524288, 3]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -80,25 +68,6 @@ def mid(amd):
     yield sets
     sets.clear()
     torch.cuda.empty_cache()
-
-
-def collect(d, k):
-    fr, meta = d.pop_frames(k)
-    return dict(frames=fr, meta=meta, events=d.pop_events(k), soft=d.soft(k), state=d.state(k), chunks=d.chunks(k))
-
-
-def explain(d, k, got, exp, tag):
-    """what a mismatch is diagnosed from: where the soft symbols part, in which demodulate() call, on which wave"""
-    a, b = got["soft"], exp["soft"]
-    m = min(len(a), len(b))
-    bad = np.nonzero(np.abs(a[:m] - b[:m]) > SOFT_TIGHT * (np.mean(np.abs(b)) + 1e-300))[0]
-    first = int(bad[0]) if bad.size else None
-    call = None if first is None else int(np.searchsorted(np.cumsum(exp["chunks"][:, 4]), first, side="right"))
-    st = got["state"]
-    hw_id, xcc_id, _cycles, _ticks = d.wave_info(k)
-    print(f"{tag}: MISMATCH. symbols {len(a)} (oracle {len(b)}), {bad.size} soft symbols off, first at {first} (demodulate() call {call} of "
-          f"{len(exp['chunks'])}); frames {len(got['frames'])} (oracle {len(exp['frames'])}); stalled 0x{st.stalled:x}, chunk_origin "
-          f"{st.chunk_origin}, n_chunks {st.n_chunks}; dbg_hw_id 0x{hw_id:x}, dbg_xcc_id {xcc_id}")
 
 
 def check_context(amd, d, exps, tag):

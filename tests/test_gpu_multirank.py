@@ -333,7 +333,7 @@ def test_512_stream_context_vs_oracle():
     import torch
     from __graft_entry__ import load_opv_amd, load_pkg_module
     from oracle_lib import Oracle
-    from test_gpu_parity import events_match, no_ties
+    from stream_checks import events_match, no_ties
     amd, workload = load_opv_amd(), load_pkg_module("workload")
     dev = torch.device("cuda", 0)
     S, F = 512, 3
@@ -387,7 +387,7 @@ def test_many_stream_contexts_on_the_automatic_mapping(S, forced):
     dev = torch.device("cuda", 0)
     D, F = 24, 3
     n = amd.lib().opv_tx_modulated_samples(F)
-    from test_gpu_parity import events_match, soft_err
+    from stream_checks import events_match, soft_err
     dm = amd.Demod(S, max_samples=n + 64, streaming=True)
     if forced:
         dm.set_frontend(forced)

@@ -13,18 +13,11 @@ destination) is not observable here; a write into another stream's buffer or sho
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LENGTHS = [1, 2, 3, 4, 5, 15, 16, 17, 1023, 1025, 4099]     # samples: below, at and beside one quad, one 16-quad row, 256 lanes x 4 / x 16
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 class PinnedPool:

@@ -13,12 +13,12 @@ import numpy as np
 import pytest
 
 import soft_log_inputs as S
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from oracle_lib import format_events
+from stream_runs import HUNTING, LOCKED, code_of
 
 pytestmark = pytest.mark.gpu
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-HUNTING, VERIFYING, LOCKED = 0, 1, 2
 SMALL = 32                                     # max_samples: cap_soft 4096, cap_frames 4, cap_events 80
 MID = 330000                                   # cap_soft 16384, cap_frames 8, cap_events 96
 
@@ -33,13 +33,6 @@ def caps_of(max_samples):
 
 
 @pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
 def logs(oracle):
     d = S.all_logs(oracle)
     d["g.edge"] = S.decoder_edge_log(oracle)[1]
@@ -50,10 +43,6 @@ def logs(oracle):
 def tracked(oracle, logs):
     """Oracle.track of every log: computed once, shared, never changed"""
     return {name: oracle.track(log.soft) for name, log in logs.items()}
-
-
-def code_of(err):
-    return int(str(err).split("opv error ")[1].split(":")[0])
 
 
 class Run:

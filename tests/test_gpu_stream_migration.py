@@ -17,22 +17,14 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from oracle_lib import accidents, impair
-from test_frontend_fp64_ring import make_demod, state_tuple
-from test_gpu_parity import SOFT_TIGHT, _visible_gpus, check_stream, events_match, soft_err
+from stream_checks import SOFT_TIGHT, _visible_gpus, check_stream, events_match, soft_err
+from stream_runs import (CHUNK, HUNTING, LOCKED, VERIFYING, drain, feed, held_to_the_oracle, make_demod, new_acc, result, state_tuple,
+                         tracker_at)
 
 pytestmark = pytest.mark.gpu
-CHUNK = 86720
 EINVAL, ECAPACITY = -1, -4
-HUNTING, VERIFYING, LOCKED = 0, 1, 2
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -47,74 +39,7 @@ def caps(oracle, iq10):
     return c, exp
 
 
-# ---- what a test keeps per stream ---------------------------------------------------------------------------------------------
-def new_acc():
-    return dict(frames=[], meta=[], events=[], soft=[], chunks=[], n_soft=0, n_chunks=0)
-
-
-def drain(d, k, acc, pop=True, soft=True):
-    """append what stream k of context d has produced since the last drain (the taps are absolute: nothing is read twice)"""
-    if pop:
-        f, m = d.pop_frames(k)
-        acc["frames"].append(f)
-        acc["meta"].append(m)
-        acc["events"].append(d.pop_events(k))
-    st = d.state(k)
-    if soft and st.total_symbols > acc["n_soft"]:
-        s = d.soft(k, first=acc["n_soft"])
-        assert len(s) == st.total_symbols - acc["n_soft"]
-        acc["soft"].append(s)
-        acc["n_soft"] = st.total_symbols
-    if st.n_chunks > acc["n_chunks"]:
-        c = d.chunks(k, first=acc["n_chunks"])
-        assert len(c) == st.n_chunks - acc["n_chunks"]
-        acc["chunks"].append(c)
-        acc["n_chunks"] = st.n_chunks
-    return st
-
-
-def result(amd, d, k, acc):
-    st = drain(d, k, acc)
-    cat = lambda xs, empty: np.concatenate(xs) if xs else empty
-    return dict(frames=cat(acc["frames"], np.zeros((0, 134), np.uint8)), meta=cat(acc["meta"], np.zeros(0, amd.META_DTYPE)),
-                events=cat(acc["events"], np.zeros(0, amd.EVENT_DTYPE)), soft=cat(acc["soft"], np.zeros(0)),
-                chunks=cat(acc["chunks"], np.zeros((0, 5))), state=st)
-
-
-def held_to_the_oracle(amd, d, k, acc, exp, tag, offset_ties=0):
-    got = result(amd, d, k, acc)
-    assert got["state"].stalled == 0, tag
-    check_stream(amd, got, exp, tag, edge_ties=0, offset_ties=offset_ties)
-    assert got["state"].frames_decoded == len(exp["frames"]) and got["state"].frames_perfect == int(np.sum(exp["metrics"] == 0)), tag
-    return got
-
-
-def feed(d, k, x, lo, hi, acc, pop=True, piece=40000):
-    """samples [lo, hi) of capture x into stream k in pieces, a round after each"""
-    for o in range(lo, hi, piece):
-        d.push(k, x[2 * o: 2 * min(o + piece, hi)])
-        d.process()
-        drain(d, k, acc, pop=pop)
-
-
-def tracker_at(exp, n_sym):
-    """where the ORACLE's tracker stands once it has consumed n_sym symbols: 'hunting', 'verifying', 'collecting' (LOCKED, a payload
-    pending release), 'miss-collecting' (the same behind a sync MISS: the pending frame is a flywheel frame) or 'between' (LOCKED,
-    the last payload released, the next sync check not made yet)"""
-    ev = [e for e in exp["events"] if e["sym_idx"] < n_sym]
-    if not ev or ev[-1]["kind"] == 5:
-        return "hunting"
-    if ev[-1]["kind"] == 1:
-        return "verifying"
-    last = ev[-1]
-    if last["kind"] == 2:                                   # VERIFYING -> LOCKED is printed AT the first release
-        return "between"
-    released = int(last["sym_idx"]) + 2144 in [int(r) for r in exp["frame_sym"] if r < n_sym]
-    if released:
-        return "between"
-    return "miss-collecting" if last["kind"] == 4 else "collecting"
-
-
+# ---- what a test keeps per stream: the accumulator of tests/stream_runs.py (new_acc, drain, result, held_to_the_oracle, feed) ------
 def symbols_after(exp, n_chunks):
     return int(np.sum(exp["chunks"][:n_chunks, 4]))
 

@@ -13,8 +13,8 @@ None of these may move a rounding, so:
     of one symbol and across an export / import, held to the oracle per demodulate() call;
  4. the fp64 ring's addressing with the chunk origin past 2^16, 2^21 (oracle and int16 ring) and 2^27 samples (int16 ring).
 
-Bounds: test_gpu_parity.check_stream as it stands (soft symbols < 1e-9 of their mean, decisions and integer columns ==, the chunk
-log's float columns 1e-7); against the int16 ring: identity (test_frontend_fp64_ring.assert_same)."""
+Bounds: stream_checks.check_stream as it stands (soft symbols < 1e-9 of their mean, decisions and integer columns ==, the chunk
+log's float columns 1e-7); against the int16 ring: identity (stream_runs.assert_same)."""
 import importlib.util
 import json
 from concurrent.futures import ProcessPoolExecutor
@@ -24,17 +24,15 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures import amd  # noqa: F401
 from oracle_lib import impair
 from soak_inputs import host_workers, oracle_receive_job
-from test_frontend_fp64_ring import assert_same, make_demod, state_tuple
-from test_gpu_parity import check_stream
-from test_gpu_stream_migration import drain, new_acc, result
+from stream_checks import check_stream
+from stream_runs import CAP_SOFT, CHUNK, SMALL_M, WRAP_PIECES, assert_same, drain, make_demod, new_acc, result, state_tuple
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden" / "symbol_body_parent.json"
-CHUNK = 86720
 WG4_S = 516                                   # the first stream counts k_msk_frontend_rb_wg4 serves: 513 ..
 WG4_SLOTS = [0, 1, 2, 3, 257, 258, 514, 515]  # every wave of a workgroup, the first, a middle and the last (full) workgroup
 
@@ -44,13 +42,6 @@ def recorder():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -112,11 +103,7 @@ def test_equals_the_parent(amd, parent_set, shape):
 
 
 # ------------------------------------------------------------------ 2. the soft ring's wrap at every position of a loop trip
-SMALL_M = 150000                              # cap_soft = the power of two >= M / 38 + 4096 = 8192 symbols, the smallest there is
-CAP_SOFT = 8192
-WRAP_PIECES = [39999, 20011, 7919, 49999, 257, 33333, 40, 45001]
-
-
+# (SMALL_M, CAP_SOFT, WRAP_PIECES: tests/stream_runs.py)
 @pytest.fixture(scope="module")
 def wrap_set(oracle):
     """four 12-frame captures (16 dB) whose starts are staggered by 0, 1, 2 and 3 symbols, and the oracle's result for each"""

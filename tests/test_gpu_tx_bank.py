@@ -2,13 +2,12 @@
 device, their state carried from round to round. The criterion is exact everywhere: what a stream's rounds wrote `==` what the
 host modulator (= `opv-mod`, tests/test_capi_and_host.py's sha256 pins) makes of the same frames. The model of the carried
 sign parity is tests/tx_bank_model.py, pinned to the host modulator by tests/test_tx_bank_host.py."""
-import re
-
 import numpy as np
 import pytest
 
 import tx_bank_model as M
-from amd_lib import load
+from fixtures_built import amd  # noqa: F401
+from stream_runs import code_raised_by
 
 pytestmark = pytest.mark.gpu
 
@@ -16,13 +15,6 @@ FS = M.FRAME_SAMPLES                     # samples per frame; 2 int16 each
 CANARY = 0x5A5B                          # int16 fill of everything a round must not touch
 GAP = 32                                 # int16 per 64-byte canary
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -57,14 +49,6 @@ class Lanes:
         x = self.buf.cpu().numpy()
         step = self.per + GAP
         return all((x[a:a + GAP] == CANARY).all() for a in range(0, x.size, step))
-
-
-def code_of(amd, fn):
-    try:
-        fn()
-    except amd.OpvError as e:
-        return int(re.match(r"opv error (-?\d+):", str(e)).group(1))
-    return 0
 
 
 def test_any_split_into_rounds_equals_one_call(amd, dev):
@@ -128,8 +112,8 @@ def test_reset_and_state_move_between_banks(amd, dev):
     assert a.state(2) == b.state(5) == (4 * M.FSYMS, M.sign_parity(amd, fr))
     # states no modulator can be in
     for bad in ((0, 2, 0), (0, -1, 0), (0, 0, 1), (65536 * M.FSYMS + 1, 0, 0)):
-        assert code_of(amd, lambda: b.set_state(0, *bad)) == EINVAL
-    assert code_of(amd, lambda: b.set_state(7, 0, 0)) == EINVAL and code_of(amd, lambda: b.reset(7)) == EINVAL
+        assert code_raised_by(amd, lambda: b.set_state(0, *bad)) == EINVAL
+    assert code_raised_by(amd, lambda: b.set_state(7, 0, 0)) == EINVAL and code_raised_by(amd, lambda: b.reset(7)) == EINVAL
     assert b.state(0) == (0, 0)
     b.reset()
     assert all(b.state(s) == (0, 0) for s in range(7))
@@ -249,7 +233,7 @@ def test_misuse_leaves_everything_usable(amd, dev):
            (EINVAL, lambda: L.opv_txb_round(bank.h, 2, None, fp, nf, op, 0)), (EINVAL, lambda: L.opv_txb_round(bank.h, 2, ids, None, nf, op, 0)),
            (EINVAL, lambda: L.opv_txb_round(bank.h, 2, ids, fp, None, op, 0)), (EINVAL, lambda: L.opv_txb_round(bank.h, 2, ids, fp, nf, None, 0))]
     for k, (want, call) in enumerate(refused):
-        assert code_of(amd, call) == want, k
+        assert code_raised_by(amd, call) == want, k
         assert [bank.state(s) for s in range(3)] == before, k
     for k, (want, call) in enumerate(raw):
         assert call() == want, k
@@ -266,7 +250,7 @@ def test_misuse_leaves_everything_usable(amd, dev):
     # the context goes first: the bank is detached
     after = [bank.state(s) for s in range(3)]
     d.close()
-    assert code_of(amd, lambda: bank.round([0], [fr[0][:1]], [p0])) == ESTATE
-    assert code_of(amd, lambda: bank.reset()) == ESTATE and code_of(amd, lambda: bank.set_state(0, 0, 0)) == ESTATE
+    assert code_raised_by(amd, lambda: bank.round([0], [fr[0][:1]], [p0])) == ESTATE
+    assert code_raised_by(amd, lambda: bank.reset()) == ESTATE and code_raised_by(amd, lambda: bank.set_state(0, 0, 0)) == ESTATE
     assert [bank.state(s) for s in range(3)] == after
     bank.close()

@@ -1,10 +1,10 @@
 """GPU: the wideband front door (opv_wb_*, csrc/k_wideband.hip + csrc/opv_wideband.hip). k_wb_ddc is integer-exact, so its outputs
-are held to the numpy int64 model of tests/test_wideband_host.py with == on every sample (read back through opv_tap_iq), for any
+are held to the numpy int64 model of tests/wideband_models.py with == on every sample (read back through opv_tap_iq), for any
 split of a capture into pushes and any mix of pinned, pageable and device sources; and the streams it feeds are held to the ORACLE
-run on the model's output, like every other pushed stream of the suite (test_gpu_parity.check_stream: frames, metrics, release
+run on the model's output, like every other pushed stream of the suite (stream_checks.check_stream: frames, metrics, release
 symbols, tracker lines, chunk log ==, soft symbols < 1e-9).
 
-The end-to-end plan (PLAN below) was chosen on the CPU so that the reference algorithm by itself decodes every transmitted frame
+The end-to-end plan (wideband_device.PLAN_D4) was chosen on the CPU so that the reference algorithm by itself decodes every transmitted frame
 of the clean channels AND of the 12 dB channel from the model's output - the precondition the fixture asserts before the product
 sees a sample:
   D = 4 (wide rate 8.672 MS/s), K = 4 slots at -1.1, 0.0, +1.6 and +2.7 MHz. A channel repeated by D (zero-order hold) has images at
@@ -20,114 +20,24 @@ The channels are made by the product's own transmit chain (amd.bert_frames / amd
 import numpy as np
 import pytest
 
-from amd_lib import load
-from oracle_lib import impair
-from test_gpu_midrange_streams import collect
-from test_gpu_parity import SOFT_TIGHT, check_stream, events_match
-from test_wideband_host import WIDE_RATE, wb_model, wb_model_inc
+from fixtures import amd, torch_dev  # noqa: F401
+from stream_checks import SOFT_TIGHT, events_match
+from stream_runs import CHUNK
+from wideband_device import (PLAN_D4, Sources, assert_exactness_preconditions, check_plan_streams_d4, exactness_inputs, make_plan_capture_d4,
+                             plan_wideband_d4)
+from wideband_models import WIDE_RATE, halved_taps, wb_model, wb_model_inc
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-CHUNK = 86720
-PLAN = dict(D=4, centres=[-1100000.0, 0.0, 1600000.0, 2700000.0], L=321, cutoff_hz=200000.0, out_shift=30,
-            channels={0: dict(amp=3000.0, f0_hz=1700.0, ebn0_db=None), 1: dict(amp=1000.0, f0_hz=600.0, ebn0_db=12.0),
-                      2: dict(amp=3000.0, f0_hz=-1900.0, ebn0_db=None)}, empty=3, seed=70)
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def plan_taps():
-    L, fs = PLAN["L"], PLAN["D"] * WIDE_RATE
-    t = np.arange(L) - (L - 1) / 2
-    h = np.sinc(2 * PLAN["cutoff_hz"] / fs * t) * np.hamming(L)
-    taps = np.rint(h / h.sum() * (1 << 15)).astype(np.int16)
-    assert np.abs(taps.astype(np.int64)).sum() <= 1 << 21
-    return taps
-
-
-def make_plan_capture(amd, oracle, n_frames, empty_is_silent=True):
-    """-> dict(wide, taps, tx[k], model[k] (int16 IQ per slot), exp[k] (the oracle on model[k]))"""
-    D, centres = PLAN["D"], PLAN["centres"]
-    fs = D * WIDE_RATE
-    tx, z = {}, None
-    for k, c in PLAN["channels"].items():
-        tx[k] = amd.bert_frames(n_frames, "WB%d" % k, first=10 * k)
-        iq = impair(amd.modulate(tx[k]), amp=c["amp"], f0_hz=c["f0_hz"], ebn0_db=c["ebn0_db"], seed=PLAN["seed"] + k)
-        zk = np.repeat(iq[0::2].astype(np.float64) + 1j * iq[1::2].astype(np.float64), D)           # repeated by D ...
-        zk = zk * np.exp(2j * np.pi * centres[k] / fs * np.arange(zk.size, dtype=np.float64))       # ... mixed up ...
-        z = zk if z is None else z + zk                                                           # ... and summed
-    assert max(np.max(np.abs(z.real)), np.max(np.abs(z.imag))) < 32767
-    wide = np.empty(2 * z.size, np.int16)
-    wide[0::2], wide[1::2] = np.rint(z.real), np.rint(z.imag)
-    taps = plan_taps()
-    model = wb_model(amd.wb_lo_table(), wide, D, wb_model_inc(D, centres), taps, PLAN["out_shift"])
-    exp = [oracle.receive(model[k], streaming=True) for k in range(len(centres))]
-    # the precondition, from the reference alone: every transmitted frame of every channel, the 12 dB one included (at least 2 each),
-    # nothing from the empty slot
-    for k in PLAN["channels"]:
-        assert np.array_equal(exp[k]["frames"], tx[k]), f"plan: the oracle alone does not decode channel {k}"
-        assert len(exp[k]["frames"]) >= 2
-    if empty_is_silent:
-        assert len(exp[PLAN["empty"]]["frames"]) == 0, "plan: the oracle releases frames on the empty slot"
-    return dict(wide=wide, taps=taps, tx=tx, model=model, exp=exp)
 
 
 @pytest.fixture(scope="module")
 def e2e(amd, oracle):
-    return make_plan_capture(amd, oracle, 2)
-
-
-def plan_wideband(amd, d, first_sample=0):
-    return amd.Wideband(d, PLAN["D"], list(range(len(PLAN["centres"]))), PLAN["centres"], plan_taps(), PLAN["out_shift"], first_sample)
-
-
-def check_plan_streams(amd, d, cap, tag):
-    for k, exp in enumerate(cap["exp"]):
-        got = collect(d, k)
-        assert got["state"].stalled == 0
-        check_stream(amd, got, exp, f"{tag} slot {k}", edge_ties=0, offset_ties=None)
-    assert len(cap["exp"][PLAN["empty"]]["frames"]) == 0 and d.state(PLAN["empty"]).frames_released == 0       # the empty slot releases none
-
-
-class Sources:
-    """one wide capture as the three kinds of source a push can take: views of a pinned copy, of a pageable copy, of a device copy"""
-
-    def __init__(self, torch_dev, wide):
-        torch, dev = torch_dev
-        self.pinned_t = torch.from_numpy(wide.copy()).pin_memory()
-        self.pinned = self.pinned_t.numpy()
-        self.pageable = wide.copy()
-        self.dev_t = self.pinned_t.to(dev)
-        torch.cuda.synchronize()
-
-    def push(self, wb, kind, lo, hi):
-        """wide samples [lo, hi)"""
-        if kind == "device":
-            wb.push_device(self.dev_t.data_ptr() + 4 * lo, hi - lo)
-        else:
-            wb.push((self.pinned if kind == "pinned" else self.pageable)[2 * lo: 2 * hi])
+    return make_plan_capture_d4(amd, oracle, 2)
 
 
 # ------------------------------------------------------------------ 1. exactness
-def random_taps(rng, L, gain_cap=1 << 21):
-    h = rng.integers(-32768, 32768, L).astype(np.int64)
-    while np.abs(h).sum() > gain_cap:
-        h = h // 2
-    return h.astype(np.int16)
-
-
 CASES = {
     # name: (D, L, K, S, first_sample, n_wide, input)
     "D1_L1_K1_S0": (1, 1, 1, 0, 0, 1000, "small"),                       # S = 0: no rounding term; products of small inputs, unclamped
@@ -145,38 +55,15 @@ def test_outputs_equal_the_integer_model_on_every_sample(amd, torch_dev, case):
     never runs opv_process; every stream's IQ read back with opv_tap_iq == the model, sample for sample."""
     D, L, K, S, first, N, kind = CASES[case]
     rng = np.random.default_rng(sum(map(ord, case)))
-    fs = D * WIDE_RATE
-    centres = list(rng.uniform(-fs / 2, fs / 2, K))
-    centres[0] = 0.0 if kind in ("small", "halfway") else centres[0]
     T = amd.wb_lo_table()
-    if kind == "random":
-        wide, taps = rng.integers(-32768, 32768, 2 * N).astype(np.int16), random_taps(rng, L)
-    elif kind == "fullscale":
-        wide = rng.choice(np.array([-32768, 32767], np.int16), 2 * N)
-        wide[: 2 * 600] = np.repeat(rng.choice(np.array([-32768, 32767], np.int16), 2 * 600 // 40), 40)     # runs: the filter's sum builds up
-        h = np.hamming(L)
-        taps = np.rint(h / h.sum() * 3.9 * (1 << 19)).astype(np.int16)     # gain 3.9 x 2^19 x 32767 / 2^34 = 3.9: runs of full scale leave the int16 range
-    elif kind == "small":
-        wide, taps = rng.integers(-9, 10, 2 * N).astype(np.int16), np.array([3], np.int16)
-    else:
-        wide, taps = rng.integers(-7, 8, 2 * N).astype(np.int16), np.array([1, 0], np.int16)          # (|32767 x 7| / 8 stays inside int16: no clamp hides the rounding)
-    assert len(taps) == L
+    (wide,), taps, centres = exactness_inputs(kind, rng, "rx", D * WIDE_RATE, K, N, L, 1, halfway_taps=(1, 0))      # (one phase: the cap is on all taps)
     inc = amd.wb_plan(D, centres, taps, S, first)
     assert np.array_equal(inc, wb_model_inc(D, centres))
     exp = wb_model(T, wide, D, inc, taps, S, first)
     n_out = amd.wb_outputs(D, N)
     assert exp.shape == (K, 2 * n_out) and n_out > 256, "more than one workgroup of outputs"
-    if kind == "fullscale":
-        assert (exp == 32767).sum() > 10 and (exp == -32768).sum() > 10 and (np.abs(exp.astype(np.int32)) < 32767).sum() > 10
-    if kind == "halfway":
-        # channel 0 sits at centre 0: acc = 32767 x I. With S = 3 an accumulator is half-way when acc = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
-        acc = 32767 * wide[0::2][::D].astype(np.int64)
-        half = (acc < 0) & (acc % 8 == 4)
-        assert half.sum() > 5
-        assert np.array_equal(exp[0, 0::2], (acc + 4) >> 3)                # floor
-        away = np.sign(acc) * ((np.abs(acc) + 4) >> 3)                     # round half away from zero / truncation of the magnitude
-        trunc = np.trunc((acc + 4) / 8.0).astype(np.int64)                 # C's division, which truncates
-        assert (away != exp[0, 0::2]).any() and (trunc != exp[0, 0::2]).any()
+    # halfway: channel 0 sits at centre 0: acc = 32767 x I. With S = 3 an accumulator is half-way when acc = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
+    assert_exactness_preconditions(kind, exp, halfway=(32767 * wide[0::2][::D].astype(np.int64), exp[0, 0::2]))
     if "wrap32" in case:
         assert first < (1 << 32) <= first + N
     d = amd.Demod(K, max_samples=n_out + 64, streaming=True)
@@ -202,15 +89,15 @@ def test_any_split_and_any_source_equals_one_shot(amd, torch_dev, e2e):
     """the plan's capture whole (pinned), and in pieces of 1, D - 1, D + 1, L - 2 and 40 001 wide samples taken in turn from pinned,
     pageable and device memory (5 sizes x 3 sources: every pair occurs): the streams' IQ == the model in both runs, and the frames,
     metrics, symbols and tracker lines of both == the oracle on the model's output"""
-    D, L = PLAN["D"], PLAN["L"]
+    D, L = PLAN_D4["D"], PLAN_D4["L"]
     wide = e2e["wide"]
     N = wide.size // 2
     src = Sources(torch_dev, wide)
     n_out = amd.wb_outputs(D, N)
     pieces, kinds = [1, D - 1, D + 1, L - 2, 40001], ["pinned", "pageable", "device"]
     for split in (False, True):
-        d = amd.Demod(len(PLAN["centres"]), max_samples=n_out + 64, streaming=True)
-        wb = plan_wideband(amd, d)
+        d = amd.Demod(len(PLAN_D4["centres"]), max_samples=n_out + 64, streaming=True)
+        wb = plan_wideband_d4(amd, d)
         try:
             if not split:
                 src.push(wb, "pinned", 0, N)
@@ -223,12 +110,12 @@ def test_any_split_and_any_source_equals_one_shot(amd, torch_dev, e2e):
                     seen.add((pieces[j % 5], kinds[j % 3]))
                     at, j = at + m, j + 1
                 assert len(seen) == 15 and j > 45
-            for k in range(len(PLAN["centres"])):
+            for k in range(len(PLAN_D4["centres"])):
                 assert np.array_equal(d.iq(k), e2e["model"][k]), (split, k)
             wb.flush()
             d.process()
             d.sync()
-            check_plan_streams(amd, d, e2e, "split" if split else "one shot")
+            check_plan_streams_d4(amd, d, e2e, "split" if split else "one shot")
         finally:
             wb.close()
             d.close()
@@ -241,8 +128,8 @@ def test_end_to_end_against_the_oracle_on_every_mapping(amd, e2e, streams_per_wa
     12 dB, one slot empty; each stream's frames, metrics, release symbols, tracker lines and chunk log == Oracle().receive(model
     output), soft symbols < 1e-9 - with the context on its automatic mapping and forced to 1, 4 and 16 streams per wave."""
     N = e2e["wide"].size // 2
-    d = amd.Demod(len(PLAN["centres"]), max_samples=amd.wb_outputs(PLAN["D"], N) + 64, streaming=True)
-    wb = plan_wideband(amd, d)
+    d = amd.Demod(len(PLAN_D4["centres"]), max_samples=amd.wb_outputs(PLAN_D4["D"], N) + 64, streaming=True)
+    wb = plan_wideband_d4(amd, d)
     try:
         if streams_per_wave:
             d.set_frontend(streams_per_wave)
@@ -250,10 +137,10 @@ def test_end_to_end_against_the_oracle_on_every_mapping(amd, e2e, streams_per_wa
         wb.flush()
         d.process()
         d.sync()
-        check_plan_streams(amd, d, e2e, f"mapping {streams_per_wave}")
-        for k in PLAN["channels"]:
+        check_plan_streams_d4(amd, d, e2e, f"mapping {streams_per_wave}")
+        for k in PLAN_D4["channels"]:
             fr = d.pop_frames(k)[0]
-            assert len(fr) == 0                                              # (check_plan_streams popped them: == the oracle's == tx)
+            assert len(fr) == 0                                              # (check_plan_streams_d4 popped them: == the oracle's == tx)
     finally:
         wb.close()
         d.close()
@@ -265,13 +152,13 @@ def test_long_run_through_small_buffers(amd, oracle, torch_dev):
     every stream's buffer is compacted several times (seen through opv_tap_iq: the samples in front of the keep point are gone). The
     IQ that is still retained == the model at its absolute indices after every round, and at the end everything == the oracle, the
     whole chunk log (read round by round) included."""
-    cap = make_plan_capture(amd, oracle, 12, empty_is_silent=False)      # (over 12 frames of leaked noise the reference's tracker false-alarms on the empty slot: the product must too)
-    D, K = PLAN["D"], len(PLAN["centres"])
+    cap = make_plan_capture_d4(amd, oracle, 12, empty_is_silent=False)      # (over 12 frames of leaked noise the reference's tracker false-alarms on the empty slot: the product must too)
+    D, K = PLAN_D4["D"], len(PLAN_D4["centres"])
     N = cap["wide"].size // 2
     push_out = 30000
     src = Sources(torch_dev, cap["wide"])
     d = amd.Demod(K, max_samples=3 * CHUNK + push_out, streaming=True)
-    wb = plan_wideband(amd, d)
+    wb = plan_wideband_d4(amd, d)
     try:
         frames = [[] for _ in range(K)]
         metas = [[] for _ in range(K)]
@@ -303,7 +190,7 @@ def test_long_run_through_small_buffers(amd, oracle, torch_dev):
                 chunks[k].append(d.chunks(k, first=sum(map(len, chunks[k]))))   # (the log is a ring: read what each round added)
             r += 1
         assert min(compactions) >= 3, compactions
-        for k in PLAN["channels"]:                                           # (the 12 dB slot included: the fixture holds the oracle to tx)
+        for k in PLAN_D4["channels"]:                                           # (the 12 dB slot included: the fixture holds the oracle to tx)
             assert len(cap["exp"][k]["frames"]) == 12
         for k, exp in enumerate(cap["exp"]):
             st = d.state(k)
@@ -333,7 +220,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
     rng = np.random.default_rng(66)
     D, L, S, K = 2, 5, 17, 3
     streams, centres = [4, 0, 2], [300000.0, -700000.0, 0.0]
-    taps = random_taps(rng, L, 1 << 17)
+    taps = halved_taps(rng, L, 1 << 17)
     piece, n_pieces = 2000, 4
     wide = rng.integers(-20000, 20000, 2 * piece * n_pieces).astype(np.int16)
     exp = wb_model(amd.wb_lo_table(), wide, D, wb_model_inc(D, centres), taps, S)
@@ -413,15 +300,15 @@ def test_async_pushes_between_rounds_equal_the_synchronous_run(amd, torch_dev, e
     """push_async -> process -> push_async -> sync for several rounds (the next block crosses PCIe while the kernels of the round in
     hand run; nothing waits on the host between a push and the opv_process behind it): same results as the synchronous run, i.e.
     the oracle's, and the same IQ in the buffers."""
-    D = PLAN["D"]
+    D = PLAN_D4["D"]
     wide = e2e["wide"]
     N = wide.size // 2
     src = Sources(torch_dev, wide)
     block = 100003
     cuts = list(range(0, N, block)) + [N]
     assert len(cuts) >= 7
-    d = amd.Demod(len(PLAN["centres"]), max_samples=amd.wb_outputs(D, N) + 64, streaming=True)
-    wb = plan_wideband(amd, d)
+    d = amd.Demod(len(PLAN_D4["centres"]), max_samples=amd.wb_outputs(D, N) + 64, streaming=True)
+    wb = plan_wideband_d4(amd, d)
     try:
         wb.push_async(src.pinned[2 * cuts[0]: 2 * cuts[1]])
         for r in range(1, len(cuts)):
@@ -433,11 +320,11 @@ def test_async_pushes_between_rounds_equal_the_synchronous_run(amd, torch_dev, e
                 wb.push_async(src.pinned[2 * cuts[r]: 2 * cuts[r + 1]])
             d.sync()
         d.push_wait()
-        for k in range(len(PLAN["centres"])):
+        for k in range(len(PLAN_D4["centres"])):
             assert np.array_equal(d.iq(k), e2e["model"][k]), k
         d.process()
         d.sync()
-        check_plan_streams(amd, d, e2e, "async rounds")
+        check_plan_streams_d4(amd, d, e2e, "async rounds")
     finally:
         wb.close()
         d.close()
@@ -450,7 +337,7 @@ def test_several_async_pushes_of_copied_blocks_and_an_object_that_outlives_its_c
     first is detached: push and flush answer OPV_ESTATE, closing it frees its own memory only."""
     rng = np.random.default_rng(8)
     D, L, S, centres = 2, 9, 18, [250000.0, -400000.0]
-    taps = random_taps(rng, L, 1 << 18)
+    taps = halved_taps(rng, L, 1 << 18)
     N = 3 * 5000
     wide = rng.integers(-20000, 20000, 2 * N).astype(np.int16)
     exp = wb_model(amd.wb_lo_table(), wide, D, wb_model_inc(D, centres), taps, S)

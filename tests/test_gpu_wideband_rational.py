@@ -1,10 +1,10 @@
 """GPU: the rational wideband front door (opv_wb_create_rational, csrc/k_wideband_rational.hip + csrc/opv_wideband.hip): a capture
 at 2 168 000 x down / up S/s. k_wbr_ddc is integer-exact, so its outputs are held to the numpy int64 model of
-tests/test_wideband_rational_host.py with == on every sample (read back through opv_tap_iq), for any split of a capture into pushes
+tests/wideband_models.py with == on every sample (read back through opv_tap_iq), for any split of a capture into pushes
 and any mix of pinned, pageable and device sources; with up = 1 it must deliver the bytes of the integer door; and the streams it
-feeds are held to the ORACLE run on the model's output like every other pushed stream (test_gpu_parity.check_stream).
+feeds are held to the ORACLE run on the model's output like every other pushed stream (stream_checks.check_stream).
 
-The end-to-end plan (PLAN below) is a 10 MS/s capture (down / up = 1250 / 271) with the channels of test_gpu_wideband.PLAN at
+The end-to-end plan (wideband_device.PLAN_10M) is a 10 MS/s capture (down / up = 1250 / 271) with the channels of PLAN_D4 at
 -3.1, 0.0 and +1.7 MHz and an empty slot at +3.9 MHz; the middle channel is at Eb/N0 = 14 dB (at 12 dB the reference alone loses
 bits behind this door, so that is no precondition to build on). Each channel is brought from 2.168 to 10 MS/s by FFT zero-padding.
 Prototype filter: 26 016 taps (J = 96 per phase) at 271 x 10 MS/s, Hamming-windowed sinc with a 200 kHz cut-off, every phase's sum
@@ -13,160 +13,26 @@ empty slot before the product sees a sample."""
 import numpy as np
 import pytest
 
-from amd_lib import load
-from oracle_lib import impair
-from test_gpu_midrange_streams import collect
-from test_gpu_parity import SOFT_TIGHT, check_stream, events_match
-from test_gpu_wideband import CHUNK, PLAN as PLAN_D4, Sources, random_taps
-from test_wideband_host import WIDE_RATE, wb_model, wb_model_inc
-from test_wideband_rational_host import per_phase_taps, wbr_model, wbr_model_inc, wbr_outputs
+from fixtures import amd, torch_dev  # noqa: F401
+from stream_checks import SOFT_TIGHT, events_match
+from stream_runs import CHUNK
+from wideband_device import (PLAN_10M, Sources, assert_exactness_preconditions, check_plan_streams_10m, check_up_to_the_first_window,
+                             exactness_inputs, first_one_tap_window, make_channel_10m, make_plan_capture_10m, plan_taps_10m, plan_wideband_10m,
+                             to_wide)
+from wideband_models import WIDE_RATE, halved_taps, per_phase_taps, wb_model, wb_model_inc, wbr_model, wbr_model_inc, wbr_outputs
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-PLAN = dict(down=1250, up=271, centres=[-3100000.0, 0.0, 1700000.0, 3900000.0], J=96, cutoff_hz=200000.0, out_shift=30,
-            channels={0: dict(PLAN_D4["channels"][0]), 1: dict(PLAN_D4["channels"][1], ebn0_db=14.0), 2: dict(PLAN_D4["channels"][2])},
-            empty=3, seed=70)
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def plan_taps(J=None):
-    U, M = PLAN["up"], PLAN["down"]
-    L = (J or PLAN["J"]) * U
-    fs = U * (M * WIDE_RATE / U)                                           # the prototype runs at up x the wide rate
-    t = np.arange(L) - (L - 1) / 2
-    h = np.sinc(2 * PLAN["cutoff_hz"] / fs * t) * np.hamming(L)
-    taps = np.rint(h / h.sum() * U * (1 << 15)).astype(np.int16)            # every phase sums to about 2^15: unity gain with out_shift = 30
-    assert max(np.abs(taps[p::U].astype(np.int64)).sum() for p in range(U)) <= 1 << 21
-    return taps
-
-
-def fft_resample(z, up_to, down_from):
-    """z at rate F -> rate F x up_to / down_from by zero-padding its spectrum (z is padded to a multiple of down_from first)"""
-    n = -(-z.size // down_from) * down_from
-    Z = np.fft.fft(np.concatenate([z, np.zeros(n - z.size, z.dtype)]))
-    m = n // down_from * up_to
-    W = np.zeros(m, np.complex128)
-    W[: n // 2], W[m - (n - n // 2):] = Z[: n // 2], Z[n // 2:]
-    return np.fft.ifft(W) * (m / n)
-
-
-def make_channel(amd, k, n_frames):
-    c = PLAN["channels"][k]
-    tx = amd.bert_frames(n_frames, "WB%d" % k, first=10 * k)
-    iq = impair(amd.modulate(tx), amp=c["amp"], f0_hz=c["f0_hz"], ebn0_db=c["ebn0_db"], seed=PLAN["seed"] + k)
-    return tx, fft_resample(iq[0::2].astype(np.float64) + 1j * iq[1::2].astype(np.float64), PLAN["down"], PLAN["up"])
-
-
-def to_wide(z):
-    assert max(np.max(np.abs(z.real)), np.max(np.abs(z.imag))) < 32767
-    wide = np.empty(2 * z.size, np.int16)
-    wide[0::2], wide[1::2] = np.rint(z.real), np.rint(z.imag)
-    return wide
-
-
-def make_plan_wide(amd, n_frames):
-    """-> (wide int16 IQ, tx[k]): the plan's channels side by side at 10 MS/s, before the door (host code only)"""
-    M, U, centres = PLAN["down"], PLAN["up"], PLAN["centres"]
-    fw = M * WIDE_RATE / U
-    tx, z = {}, None
-    for k in PLAN["channels"]:
-        tx[k], zk = make_channel(amd, k, n_frames)
-        zk = zk * np.exp(2j * np.pi * centres[k] / fw * np.arange(zk.size, dtype=np.float64))
-        z = zk if z is None else z + zk
-    return to_wide(z), tx
-
-
-def make_plan_capture(amd, oracle, n_frames):
-    """-> dict(wide, taps, tx[k], model[k] (int16 IQ per slot), exp[k] (the oracle on model[k]))"""
-    M, U, centres = PLAN["down"], PLAN["up"], PLAN["centres"]
-    wide, tx = make_plan_wide(amd, n_frames)
-    taps = plan_taps()
-    model = wbr_model(amd.wb_lo_table(), wide, M, U, wbr_model_inc(M, U, centres), taps, PLAN["out_shift"])
-    exp = [oracle.receive(model[k], streaming=True) for k in range(len(centres))]
-    for k in PLAN["channels"]:                                             # the precondition, from the reference alone
-        assert np.array_equal(exp[k]["frames"], tx[k]), f"plan: the oracle alone does not decode channel {k}"
-        assert len(exp[k]["frames"]) >= 2
-    assert len(exp[PLAN["empty"]]["frames"]) == 0, "plan: the oracle releases frames on the empty slot"
-    # which check a slot gets is read off the oracle's output alone (check_plan_streams): the noisy channel must get the full
-    # one, and on the clean ones every one-tap window must lie behind the symbols of both frames, in the modulator's tail of zeros
-    assert first_one_tap_window(exp[1])[1] == 0
-    for k in (0, 2):
-        assert first_one_tap_window(exp[k])[0] >= n_frames * 2168, f"plan: channel {k} has a one-tap window inside its frames"
-    return dict(wide=wide, taps=taps, tx=tx, model=model, exp=exp)
 
 
 @pytest.fixture(scope="module")
 def e2e(amd, oracle):
-    return make_plan_capture(amd, oracle, 2)
-
-
-def plan_wideband(amd, d, first_sample=0):
-    return amd.Wideband.rational(d, PLAN["down"], PLAN["up"], list(range(len(PLAN["centres"]))), PLAN["centres"], plan_taps(), PLAN["out_shift"], first_sample)
+    return make_plan_capture_10m(amd, oracle, 2)
 
 
 def plan_demod(amd, e2e):
-    return amd.Demod(len(PLAN["centres"]), max_samples=e2e["model"].shape[1] // 2 + 64, streaming=True)
-
-
-def first_one_tap_window(exp):
-    """the oracle's first one-tap window (soft = -/+2^-31: test_gpu_mapping_matrix.ambiguous), or n_soft if it shows none"""
-    amb = np.nonzero((exp["soft"] != 0) & (np.abs(exp["soft"]) < 1.0))[0]
-    return (int(amb[0]) if amb.size else exp["n_soft"]), amb.size
-
-
-def check_up_to_the_first_window(amd, st, frames, meta, events, log, exp, tag, soft=None):
-    """A stream whose ORACLE output shows one-tap windows (a clean channel behind this door is digitally silent wherever the
-    modulator's capture is: its 40 leading and 4000 trailing zeros - no other channel's images leak in, as they do behind the
-    zero-order hold of test_gpu_wideband's plan): there the reference's tone choice is the rounding of its own LO, which the
-    product reports in edge_ties and does not reproduce (include/opv_demod.h), so the suite's rule for that class applies
-    (test_gpu_mapping_matrix.check_capture): soft symbols, chunk rows and tracker lines up to the oracle's first such window,
-    every frame, metric and release symbol, the symbol count and the offset estimate; edge_ties at most the oracle's windows.
-    Measured on the MI355X on the plan's slot 0 (one window counted, at a symbol behind both frames): soft symbols within 2.3e-12
-    of their mean over the WHOLE run, the last chunk row's carried frequency 7.7e-4 Hz off, everything else ==."""
-    k_end, n_amb = first_one_tap_window(exp)
-    assert n_amb >= 1 and st.stalled == 0 and st.edge_ties <= n_amb, f"{tag}: edge_ties {st.edge_ties}, the oracle shows {n_amb} one-tap windows"
-    assert st.total_symbols == exp["n_soft"], f"{tag}: {st.total_symbols} symbols, oracle {exp['n_soft']}"
-    assert np.array_equal(frames, exp["frames"]), f"{tag}: decoded bytes differ"
-    assert np.array_equal(meta["viterbi_metric"], exp["metrics"]), f"{tag}: Viterbi metrics differ"
-    assert np.array_equal(meta["release_symbol"], exp["frame_sym"]), f"{tag}: sync positions differ"
-    e0, e1 = st.est_offset_hz, exp["est_offset"]
-    assert (np.isnan(e0) and np.isnan(e1)) or e0 == e1, f"{tag}: offset estimate {e0} vs {e1}"
-    events_match(amd, events[events["sym_idx"] < k_end], exp["events"][exp["events"]["sym_idx"] < k_end])
-    if soft is not None and k_end:
-        assert len(soft) == exp["n_soft"]
-        a = float(np.max(np.abs(soft[:k_end] - exp["soft"][:k_end]))) / (np.mean(np.abs(exp["soft"])) + 1e-300)
-        assert a < SOFT_TIGHT, f"{tag}: soft error {a:.3e} before symbol {k_end}"
-    ech = exp["chunks"]
-    done = np.nonzero(np.cumsum(ech[:, 4]) <= k_end)[0]                    # demodulate() calls that ended before the window
-    assert len(log) >= done.size, f"{tag}: {len(log)} chunk rows"
-    for c in done:
-        assert np.array_equal(log[c, 3:], ech[c, 3:]), f"{tag}: call {c}: leftover / symbols {log[c, 3:]} vs {ech[c, 3:]}"
-        assert np.allclose(log[c, :3], ech[c, :3], rtol=0, atol=1e-7), f"{tag}: call {c}: {log[c]} vs {ech[c]}"
-
-
-def check_plan_streams(amd, d, cap, tag):
-    """every slot whose oracle output shows no one-tap window: check_stream in full, edge_ties == 0; the others: up to the first"""
-    for k, exp in enumerate(cap["exp"]):
-        got = collect(d, k)
-        assert got["state"].stalled == 0
-        if first_one_tap_window(exp)[1] == 0:
-            check_stream(amd, got, exp, f"{tag} slot {k}", edge_ties=0, offset_ties=None)
-        else:
-            check_up_to_the_first_window(amd, got["state"], got["frames"], got["meta"], got["events"], got["chunks"], exp, f"{tag} slot {k}", got["soft"])
-    assert d.state(PLAN["empty"]).frames_released == 0
+    return amd.Demod(len(PLAN_10M["centres"]), max_samples=e2e["model"].shape[1] // 2 + 64, streaming=True)
 
 
 # ------------------------------------------------------------------ 1. exactness
@@ -191,22 +57,8 @@ def test_outputs_equal_the_integer_model_on_every_sample(amd, torch_dev, case):
     M, U, L, K, S, first, N, kind = CASES[case]
     # (the clamp case draws the centres, input and taps of test_gpu_wideband's D1_L143_K5_clamps: its seed, its order of draws)
     rng = np.random.default_rng(sum(map(ord, "D1_L143_K5_clamps" if kind == "fullscale" else case)))
-    fw = M * WIDE_RATE / U
-    centres = list(rng.uniform(-fw / 2, fw / 2, K))
-    centres[0] = 0.0 if kind in ("small", "halfway") else centres[0]
     T = amd.wb_lo_table()
-    if kind == "random":
-        wide, taps = rng.integers(-32768, 32768, 2 * N).astype(np.int16), per_phase_taps(rng, L, U, random_taps)
-    elif kind == "fullscale":
-        wide = rng.choice(np.array([-32768, 32767], np.int16), 2 * N)
-        wide[: 2 * 600] = np.repeat(rng.choice(np.array([-32768, 32767], np.int16), 2 * 600 // 40), 40)     # runs: the filter's sum builds up
-        h = np.hamming(L)
-        taps = np.rint(h / h.sum() * 3.9 * (1 << 19)).astype(np.int16)     # gain 3.9: runs of full scale leave the int16 range
-    elif kind == "small":
-        wide, taps = rng.integers(-9, 10, 2 * N).astype(np.int16), np.array([3], np.int16)
-    else:
-        wide, taps = rng.integers(-7, 8, 2 * N).astype(np.int16), np.array([1, 1], np.int16)          # phase 0 and phase 1: one tap of 1 each
-    assert len(taps) == L
+    (wide,), taps, centres = exactness_inputs(kind, rng, "rx", M * WIDE_RATE / U, K, N, L, U, halfway_taps=(1, 1))  # (phase 0 and phase 1: one tap of 1 each)
     inc = amd.wbr_plan(M, U, centres, taps, S, first)
     assert np.array_equal(inc, wbr_model_inc(M, U, centres))
     exp = wbr_model(T, wide, M, U, inc, taps, S, first)
@@ -214,19 +66,10 @@ def test_outputs_equal_the_integer_model_on_every_sample(amd, torch_dev, case):
     assert n_out == wbr_outputs(M, U, N) and exp.shape == (K, 2 * n_out) and n_out > 256, "more than one workgroup of outputs"
     if kind == "small":
         assert not exp[0, 2::4].any() and not exp[0, 3::4].any() and exp[0, 0::4].any()        # odd outputs: the empty phase
-    if kind == "fullscale":
-        assert (exp == 32767).sum() > 10 and (exp == -32768).sum() > 10 and (np.abs(exp.astype(np.int32)) < 32767).sum() > 10
-    if kind == "halfway":
-        # channel 0 sits at centre 0 and every phase holds the single tap 1: acc[r] = 32767 x I[n_r]. With S = 3 an accumulator is
-        # half-way when acc = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
-        n_r = (np.arange(n_out, dtype=np.int64) * M) // U
-        acc = 32767 * wide[0::2].astype(np.int64)[n_r]
-        half = (acc < 0) & (acc % 8 == 4)
-        assert half.sum() > 5
-        assert np.array_equal(exp[0, 0::2], (acc + 4) >> 3)                # floor
-        away = np.sign(acc) * ((np.abs(acc) + 4) >> 3)                     # round half away from zero
-        trunc = np.trunc((acc + 4) / 8.0).astype(np.int64)                 # C's division, which truncates
-        assert (away != exp[0, 0::2]).any() and (trunc != exp[0, 0::2]).any()
+    # halfway: channel 0 sits at centre 0 and every phase holds the single tap 1: acc[r] = 32767 x I[n_r]. With S = 3 an accumulator is
+    # half-way when acc = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
+    n_r = (np.arange(n_out, dtype=np.int64) * M) // U
+    assert_exactness_preconditions(kind, exp, halfway=(32767 * wide[0::2].astype(np.int64)[n_r], exp[0, 0::2]))
     if "wrap32" in case:
         assert first < (1 << 32) <= first + N
     d = amd.Demod(K, max_samples=n_out + 64, streaming=True)
@@ -256,7 +99,7 @@ def test_up_1_delivers_the_bytes_of_the_integer_door(amd, torch_dev):
     rng = np.random.default_rng(41)
     D, L, K, S, first, N = 4, 143, 5, 33, (1 << 32) - 1000, 4 * 600 + 3
     centres = list(rng.uniform(-D * WIDE_RATE / 2, D * WIDE_RATE / 2, K))
-    wide, taps = rng.integers(-32768, 32768, 2 * N).astype(np.int16), random_taps(rng, L)
+    wide, taps = rng.integers(-32768, 32768, 2 * N).astype(np.int16), halved_taps(rng, L)
     T = amd.wb_lo_table()
     inc = amd.wbr_plan(D, 1, centres, taps, S, first)
     assert np.array_equal(inc, amd.wb_plan(D, centres, taps, S, first)) and np.array_equal(inc, wb_model_inc(D, centres))
@@ -290,10 +133,10 @@ def test_any_split_and_any_source_equals_one_shot(amd, torch_dev, e2e):
     wide = e2e["wide"]
     N = wide.size // 2
     src = Sources(torch_dev, wide)
-    pieces, kinds = [1, 2, 5, PLAN["J"] - 2, 40001], ["pinned", "pageable", "device"]
+    pieces, kinds = [1, 2, 5, PLAN_10M["J"] - 2, 40001], ["pinned", "pageable", "device"]
     for split in (False, True):
         d = plan_demod(amd, e2e)
-        wb = plan_wideband(amd, d)
+        wb = plan_wideband_10m(amd, d)
         try:
             if not split:
                 src.push(wb, "pinned", 0, N)
@@ -306,12 +149,12 @@ def test_any_split_and_any_source_equals_one_shot(amd, torch_dev, e2e):
                     seen.add((pieces[j % 5], kinds[j % 3]))
                     at, j = at + m, j + 1
                 assert len(seen) == 15 and j > 45
-            for k in range(len(PLAN["centres"])):
+            for k in range(len(PLAN_10M["centres"])):
                 assert np.array_equal(d.iq(k), e2e["model"][k]), (split, k)
             wb.flush()
             d.process()
             d.sync()
-            check_plan_streams(amd, d, e2e, "split" if split else "one shot")
+            check_plan_streams_10m(amd, d, e2e, "split" if split else "one shot")
         finally:
             wb.close()
             d.close()
@@ -323,7 +166,7 @@ def test_end_to_end_against_the_oracle(amd, e2e, streams_per_wave):
     """each stream's frames, metrics, release symbols, tracker lines and chunk log == Oracle().receive(model output), soft symbols
     < 1e-9 - with the context on its automatic mapping and forced to 4 streams per wave"""
     d = plan_demod(amd, e2e)
-    wb = plan_wideband(amd, d)
+    wb = plan_wideband_10m(amd, d)
     try:
         if streams_per_wave:
             d.set_frontend(streams_per_wave)
@@ -331,7 +174,7 @@ def test_end_to_end_against_the_oracle(amd, e2e, streams_per_wave):
         wb.flush()
         d.process()
         d.sync()
-        check_plan_streams(amd, d, e2e, f"mapping {streams_per_wave}")
+        check_plan_streams_10m(amd, d, e2e, f"mapping {streams_per_wave}")
     finally:
         wb.close()
         d.close()
@@ -346,7 +189,7 @@ def test_async_pushes_between_rounds_equal_the_synchronous_run(amd, torch_dev, e
     cuts = list(range(0, N, block)) + [N]
     assert len(cuts) >= 7
     d = plan_demod(amd, e2e)
-    wb = plan_wideband(amd, d)
+    wb = plan_wideband_10m(amd, d)
     try:
         wb.push_async(src.pinned[2 * cuts[0]: 2 * cuts[1]])
         for r in range(1, len(cuts)):
@@ -358,11 +201,11 @@ def test_async_pushes_between_rounds_equal_the_synchronous_run(amd, torch_dev, e
                 wb.push_async(src.pinned[2 * cuts[r]: 2 * cuts[r + 1]])
             d.sync()
         d.push_wait()
-        for k in range(len(PLAN["centres"])):
+        for k in range(len(PLAN_10M["centres"])):
             assert np.array_equal(d.iq(k), e2e["model"][k]), k
         d.process()
         d.sync()
-        check_plan_streams(amd, d, e2e, "async rounds")
+        check_plan_streams_10m(amd, d, e2e, "async rounds")
     finally:
         wb.close()
         d.close()
@@ -377,7 +220,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
     rng = np.random.default_rng(67)
     M, U, L, S = 3, 2, 9, 17
     streams, centres = [4, 0, 2], [300000.0, -700000.0, 0.0]
-    taps = per_phase_taps(rng, L, U, random_taps, 1 << 17)
+    taps = per_phase_taps(rng, L, U, 1 << 17)
     piece, n_pieces = 3001, 4
     wide = rng.integers(-20000, 20000, 2 * piece * n_pieces).astype(np.int16)
     exp = wbr_model(amd.wb_lo_table(), wide, M, U, wbr_model_inc(M, U, centres), taps, S)
@@ -432,11 +275,11 @@ def test_long_run_through_small_buffers(amd, oracle, torch_dev):
     """12 frames of one channel at 10 MS/s in pushes of 50 001 wide samples through a context whose buffer holds 3 chunks + one
     push: a push, opv_process and a pop per round. Outputs per push take both floor and ceil of 50 001 x 271 / 1250; the IQ still
     retained == the model after every push, and at the end everything == the oracle on the model's output."""
-    M, U, J, S, centre, push = PLAN["down"], PLAN["up"], 24, PLAN["out_shift"], 1700000.0, 50001
-    tx, z = make_channel(amd, 2, 12)
+    M, U, J, S, centre, push = PLAN_10M["down"], PLAN_10M["up"], 24, PLAN_10M["out_shift"], 1700000.0, 50001
+    tx, z = make_channel_10m(amd, 2, 12)
     fw = M * WIDE_RATE / U
     wide = to_wide(z * np.exp(2j * np.pi * centre / fw * np.arange(z.size, dtype=np.float64)))
-    taps = plan_taps(J)
+    taps = plan_taps_10m(J)
     model = wbr_model(amd.wb_lo_table(), wide, M, U, wbr_model_inc(M, U, [centre]), taps, S)[0]
     exp = oracle.receive(model, streaming=True)
     assert np.array_equal(exp["frames"], tx) and len(tx) == 12              # (the reference alone decodes the channel behind this door)

@@ -1,5 +1,5 @@
 """GPU: the wideband transmit bank (opv_wbtx_*, csrc/k_wideband_tx.hip + csrc/opv_wideband_tx.hip). k_wbtx_duc is integer-exact,
-so every wide sample it writes is held to the numpy int64 model of tests/test_wideband_tx_host.py with ==, for any split of the
+so every wide sample it writes is held to the numpy int64 model of tests/wideband_models.py with ==, for any split of the
 inputs into pushes and any mix of present and absent channels; and the product's own chain - transmit bank, up-converter bank, DDC
 bank, demodulators - is closed end to end: the wide capture == the model, each received stream's IQ == the DDC model of it, and each
 stream is held to the ORACLE on that IQ like every other pushed stream of the suite.
@@ -10,81 +10,19 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from amd_lib import load
-from test_gpu_midrange_streams import collect
-from test_gpu_parity import check_stream
-from test_gpu_tx_bank import code_of
-from test_gpu_wideband import PLAN, plan_taps
-from test_wideband_host import WIDE_RATE, wb_model, wb_model_inc
-from test_wideband_tx_host import wbtx_model
+from fixtures import amd, torch_dev  # noqa: F401
+from stream_checks import check_stream
+from stream_runs import CHUNK, code_raised_by, collect
+from wideband_device import (CANARY, LOOP_D4, PLAN_D4, Inputs, Out, assert_equal, assert_exactness_preconditions, exactness_inputs,
+                             loop_taps_d4, loopback_on_the_cpu, plan_taps_d4, run_absent_channel_schedule)
+from wideband_models import WIDE_RATE, tx_phase_taps, wb_model, wb_model_inc, wbtx_model
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ESTATE = -1, -6
-CHUNK = 86720
-CANARY, GAP = 0x5A5B, 64                 # int16 fill of what a push must not touch; int16 per canary
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-class Out:
-    """a device buffer of n wide samples between two canaries; everything starts as canary"""
-
-    def __init__(self, torch_dev, n):
-        torch, dev = torch_dev
-        self.n = n
-        self.buf = torch.full((2 * n + 2 * GAP,), CANARY, dtype=torch.int16, device=dev)
-
-    def ptr(self, at=0):
-        return self.buf.data_ptr() + 2 * GAP + 4 * at
-
-    def get(self):
-        """the n samples, after asserting that both canaries are intact"""
-        x = self.buf.cpu().numpy()
-        assert (x[:GAP] == CANARY).all() and (x[-GAP:] == CANARY).all(), "a push wrote outside its output"
-        return x[GAP:-GAP]
-
-
-class Inputs:
-    """chans[k] (interleaved int16 IQ, the same length each) in one device tensor, a row per channel"""
-
-    def __init__(self, torch_dev, chans):
-        torch, dev = torch_dev
-        self.t = torch.from_numpy(np.stack(chans)).to(dev)
-        self.row = self.t.stride(0) * 2
-        torch.cuda.synchronize()
-
-    def ptr(self, k, at=0):
-        return self.t.data_ptr() + k * self.row + 4 * at
-
-
-def assert_equal(got, exp, tag):
-    assert got.size == exp.size, (tag, got.size, exp.size)
-    bad = np.nonzero(got != exp)[0]
-    assert bad.size == 0, f"{tag}: {bad.size} of {got.size} values differ, first at {bad[0]}: {got[bad[0]]} vs {exp[bad[0]]}"
 
 
 # ------------------------------------------------------------------ 1. exactness
-def random_taps(rng, L, U):
-    """random int16 taps with every phase's sum of |taps| within 65535"""
-    h = rng.integers(-32768, 32768, L).astype(np.int64)
-    for p in range(min(U, L)):
-        while np.abs(h[p::U]).sum() > 65535:
-            h[p::U] //= 2
-    return h.astype(np.int16)
-
-
 CASES = {
     # name: (U, L, K, S, first_sample, n_in, input)
     "U1_L1_K1_S0": (1, 1, 1, 0, 0, 1000, "unit"),                            # S = 0: no rounding term
@@ -103,53 +41,19 @@ def test_outputs_equal_the_integer_model_on_every_sample(amd, torch_dev, case):
     the history is longer than the first push, the zeros in front of it), more outputs than one workgroup's tile; == the model"""
     U, L, K, S, first, N, kind = CASES[case]
     rng = np.random.default_rng(sum(map(ord, case)))
-    fs = U * WIDE_RATE
-    centres = list(rng.uniform(-fs / 2, fs / 2, K))
     T = amd.wb_lo_table()
-    if kind == "random":
-        chans, taps = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)], random_taps(rng, L, U)
-    elif kind == "fullscale":
-        chans = []
-        for _ in range(K):
-            x = rng.choice(np.array([-32768, 32767], np.int16), 2 * N)
-            x[: 2 * 600] = np.repeat(rng.choice(np.array([-32768, 32767], np.int16), 2 * 600 // 40), 40)       # runs: the filter's sum builds up
-            chans.append(x)
-        h = np.hamming(L)
-        taps = np.rint(h / h.sum() * 65000).astype(np.int16)              # gain 65000 x 32767 / 2^29 = 3.97 per channel
-    elif kind == "unit":
-        chans, taps = [rng.integers(-1, 2, 2 * N).astype(np.int16)], np.array([1], np.int16)           # |I c - Q s| <= 46340: some clamp, most do not
-    elif kind == "halfway":
-        centres[0] = 0.0
-        chans, taps = [rng.integers(-7, 8, 2 * N).astype(np.int16)], np.array([1, 1], np.int16)        # (|32767 x 7| / 8 stays inside int16: no clamp hides the rounding)
-    else:
-        centres = [0.0] * K
-        chans, taps = [np.full(2 * N, -32768, np.int16) for _ in range(K)], np.array([-32768, -32767], np.int16)
-    assert len(taps) == L
+    chans, taps, centres = exactness_inputs(kind, rng, "tx", U * WIDE_RATE, K, N, L, U)
     inc = amd.wbtx_plan(U, centres, taps, S, first)
     assert np.array_equal(inc, wb_model_inc(U, centres))
     exp = wbtx_model(T, chans, U, inc, taps, S, first)
     assert exp.size == 2 * N * U and N * U > 256, "more than one workgroup of outputs"
-    inside = np.abs(exp.astype(np.int32)) < 32767
-    if kind in ("random", "unit"):
-        assert inside.mean() > 0.6 and np.unique(exp).size > 100, "the case must not hide behind the clamp"
-    if kind == "fullscale":
-        assert (exp == 32767).sum() > 10 and (exp == -32768).sum() > 10 and inside.sum() > 10
+    w = None
     if kind == "halfway":
         # centre 0: w = 32767 x I on phases 0 and 1 (a tap of 1 each), 0 on phases 2 and 3 (no tap). With S = 3 a sum is half-way when
         # w = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
         w = np.zeros(N * U, np.int64)
         w[0::U] = w[1::U] = 32767 * chans[0][0::2].astype(np.int64)
-        half = (w < 0) & (w % 8 == 4)
-        assert half.sum() > 5
-        assert np.array_equal(exp[0::2], (w + 4) >> 3)                     # floor
-        away = np.sign(w) * ((np.abs(w) + 4) >> 3)                         # round half away from zero
-        trunc = np.trunc((w + 4) / 8.0).astype(np.int64)                   # C's division, which truncates
-        assert (away != exp[0::2]).any() and (trunc != exp[0::2]).any()
-    if kind == "bound":
-        # per channel y = 65535 x 32768 = 2^31 - 2^15 (the largest |y| the limits allow), c = 32767: the sum is 256 y c, just under 2^54 per
-        # component of the 2^55 bound, and comes out unclamped
-        total = 256 * (65535 * 32768) * 32767
-        assert (1 << 53) < total < (1 << 55) and (exp[2:] == (total + (1 << 39)) >> 40).all() and 0 < exp[2] < 32767
+    assert_exactness_preconditions(kind, exp, unclamped=("random", "unit"), halfway=(w, exp[0::2]))
     if "wrap32" in case:
         assert first < (1 << 32) <= first + N * U
     H = -(-(L - 1) // U)
@@ -179,7 +83,7 @@ def test_any_split_absent_channels_shared_buffers_and_reset(amd, torch_dev):
     H = -(-(L - 1) // U)
     assert H == 6
     centres = [300000.0, -700000.0, 0.0, 300000.0]
-    taps = random_taps(rng, L, U)
+    taps = tx_phase_taps(rng, L, U)
     # (n_in, channels present): channel 3 always reads channel 0's buffer
     schedule = [(1, {0, 1, 2, 3}), (H - 2, {0, 2, 3}), (0, {0, 1, 2, 3}), (1, {0, 1, 2, 3}), (H - 1, {1, 3}), (200, {0, 1, 2, 3}),
                 (H - 3, set()), (2, {2}), (150, {0, 1, 3}), (1, {1})]
@@ -192,14 +96,8 @@ def test_any_split_absent_channels_shared_buffers_and_reset(amd, torch_dev):
         src = Inputs(torch_dev, data)
         for first in (12345, (1 << 32) - 77):
             fed = [x.copy() for x in data] + [data[0].copy()]
-            out, at = Out(torch_dev, N * U), 0
-            for n, present in schedule:
-                for k in range(K):
-                    if k not in present:
-                        fed[k][2 * at: 2 * (at + n)] = 0
-                tx.push([src.ptr(0 if k == 3 else k, at) if k in present else None for k in range(K)], n, out.ptr(at * U))
-                at += n
-                assert tx.samples() == at
+            out = Out(torch_dev, N * U)
+            run_absent_channel_schedule(tx, src, out, schedule, K, fed, lambda at: at * U)
             exp = wbtx_model(T, fed, U, wb_model_inc(U, centres), taps, S, first)
             assert N * U > 256 and (np.abs(exp.astype(np.int32)) < 32767).mean() > 0.6
             assert_equal(out.get(), exp, f"first_sample {first}")
@@ -217,7 +115,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
     torch, dev = torch_dev
     rng = np.random.default_rng(33)
     U, L, S, K = 4, 9, 31, 2
-    centres, taps = [250000.0, -400000.0], random_taps(rng, L, U)
+    centres, taps = [250000.0, -400000.0], tx_phase_taps(rng, L, U)
     N, piece = 600, 200
     data = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)]
     exp = wbtx_model(amd.wb_lo_table(), data, U, wb_model_inc(U, centres), taps, S)
@@ -244,7 +142,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
             (EINVAL, lambda: amd._chk(L_.opv_wbtx_push(None, tab, piece, C.c_void_p(scratch.ptr())))),          # null object
         ]
         for code, call in refusals:
-            assert code_of(amd, call) == code
+            assert code_raised_by(amd, call) == code
             assert tx.samples() == piece
         torch.cuda.synchronize()
         assert np.array_equal(scratch.buf.cpu().numpy(), canary) and np.array_equal(src.t.cpu().numpy(), np.stack(data))
@@ -260,8 +158,8 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
         d2.close()
         scratch.buf.fill_(CANARY)
         torch.cuda.synchronize()
-        assert code_of(amd, lambda: tx2.push(ins, piece, scratch.ptr())) == ESTATE
-        assert code_of(amd, lambda: tx2.reset(0)) == ESTATE
+        assert code_raised_by(amd, lambda: tx2.push(ins, piece, scratch.ptr())) == ESTATE
+        assert code_raised_by(amd, lambda: tx2.reset(0)) == ESTATE
         assert tx2.samples() == piece and np.array_equal(scratch.buf.cpu().numpy(), canary)
         tx2.close()
         assert amd.lib().opv_wbtx_samples(None) == 0
@@ -271,39 +169,16 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
 
 
 # ------------------------------------------------------------------ 4. loopback: transmit bank -> up-converters -> DDC bank -> demodulators
-LOOP = dict(U=4, centres=PLAN["centres"][:3], out_shift=32, frames=2, tail=4000)
-
-
-def loop_taps():
-    """PLAN's 321-tap Hamming sinc scaled to sum 4 x 2^15: unity gain through the zero-stuffing by 4 (x 32767 / 2^32 from the LO)"""
-    L, fs = PLAN["L"], PLAN["D"] * WIDE_RATE
-    t = np.arange(L) - (L - 1) / 2
-    h = np.sinc(2 * PLAN["cutoff_hz"] / fs * t) * np.hamming(L)
-    taps = np.rint(h / h.sum() * 4 * (1 << 15)).astype(np.int16)
-    assert all(np.abs(taps[p::4].astype(np.int64)).sum() <= 65535 for p in range(4))
-    return taps
-
-
 @pytest.fixture(scope="module")
 def loop(amd, oracle):
     """the chain on the CPU, from the two models and the oracle alone: -> dict(tx[k], chans[k], wide, model[k], exp[k]). All three
     channels start at sample 0 and the run ends with the modulator's 4000 silent samples. The filters delay by 2 x 160 wide samples =
     two symbols exactly, so the reference's timing loop starts on a symbol boundary."""
-    F, U = LOOP["frames"], LOOP["U"]
-    tx = [amd.bert_frames(F, "WT%d" % k, first=10 * k) for k in range(3)]
-    chans = [amd.modulate(f) for f in tx]
-    for x in chans:
-        assert x.size == 2 * (F * CHUNK + LOOP["tail"]) and not x[2 * F * CHUNK:].any()           # the tail is silence: an all-null push makes it
-    T = amd.wb_lo_table()
-    wide = wbtx_model(T, chans, U, wb_model_inc(U, LOOP["centres"]), loop_taps(), LOOP["out_shift"])
-    assert 8000 < np.max(np.abs(wide.astype(np.int32))) < 32767           # well inside int16: no clamp between the banks
-    model = wb_model(T, wide, PLAN["D"], wb_model_inc(PLAN["D"], PLAN["centres"]), plan_taps(), PLAN["out_shift"])
-    exp = [oracle.receive(model[k], streaming=True) for k in range(4)]
-    # the precondition, from the reference alone: every transmitted frame on slots 0 - 2, nothing on the empty slot
-    for k in range(3):
-        assert np.array_equal(exp[k]["frames"], tx[k]), f"loopback plan: the oracle alone does not decode channel {k}"
-    assert len(exp[3]["frames"]) == 0, "loopback plan: the oracle releases frames on the empty slot"
-    return dict(tx=tx, chans=chans, wide=wide, model=model, exp=exp)
+    U, D = LOOP_D4["U"], PLAN_D4["D"]
+    return loopback_on_the_cpu(
+        amd, oracle, LOOP_D4,
+        lambda T, chans: wbtx_model(T, chans, U, wb_model_inc(U, LOOP_D4["centres"]), loop_taps_d4(), LOOP_D4["out_shift"]),
+        lambda T, wide: wb_model(T, wide, D, wb_model_inc(D, PLAN_D4["centres"]), plan_taps_d4(), PLAN_D4["out_shift"]))
 
 
 def test_loopback_through_the_products_own_chain(amd, torch_dev, loop):
@@ -312,12 +187,12 @@ def test_loopback_through_the_products_own_chain(amd, torch_dev, loop):
     which feeds a 4-stream Demod. The wide capture == wbtx_model, each stream's IQ == wb_model of it, each stream passes
     check_stream against the oracle on that IQ, frames == the transmitted ones on slots 0 - 2 and none on slot 3."""
     torch, dev = torch_dev
-    F, U, tail = LOOP["frames"], LOOP["U"], LOOP["tail"]
+    F, U, tail = LOOP_D4["frames"], LOOP_D4["U"], LOOP_D4["tail"]
     n_wide = (F * CHUNK + tail) * U
-    d = amd.Demod(4, max_samples=n_wide // PLAN["D"] + 64, streaming=True)
+    d = amd.Demod(4, max_samples=n_wide // PLAN_D4["D"] + 64, streaming=True)
     bank = amd.TxBank(d, 3)
-    up = amd.WidebandTx(d, U, LOOP["centres"], loop_taps(), LOOP["out_shift"])
-    wb = amd.Wideband(d, PLAN["D"], [0, 1, 2, 3], PLAN["centres"], plan_taps(), PLAN["out_shift"])
+    up = amd.WidebandTx(d, U, LOOP_D4["centres"], loop_taps_d4(), LOOP_D4["out_shift"])
+    wb = amd.Wideband(d, PLAN_D4["D"], [0, 1, 2, 3], PLAN_D4["centres"], plan_taps_d4(), PLAN_D4["out_shift"])
     try:
         lanes = torch.zeros((3, 2 * CHUNK), dtype=torch.int16, device=dev)
         assert lanes.data_ptr() % 16 == 0 and (lanes.stride(0) * 2) % 16 == 0

@@ -1,6 +1,6 @@
 """GPU: the rational up-converter bank (opv_wbtx_create_rational, csrc/k_wideband_tx_rational.hip + csrc/opv_wideband_tx.hip): a
 wide capture at 2 168 000 x down / up S/s. k_wbtxr_duc is integer-exact, so every wide sample it writes is held to the numpy int64
-model of tests/test_wideband_tx_rational_host.py with ==, for any split of the inputs into pushes and any mix of present and absent
+model of tests/wideband_models.py with ==, for any split of the inputs into pushes and any mix of present and absent
 channels; with up = 1 it must deliver the bytes of the integer bank; and the product's own chain - transmit bank, rational
 up-converter bank, rational DDC bank, demodulators - is closed end to end at 10 MS/s (1250 / 271): the wide capture == the model,
 each received stream's IQ == the door's model of it, and each stream is held to the ORACLE on that IQ.
@@ -11,42 +11,20 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from amd_lib import load
-from test_gpu_tx_bank import code_of
-from test_gpu_wideband_rational import PLAN, check_plan_streams, first_one_tap_window, plan_taps
-from test_gpu_wideband_tx import CANARY, CHUNK, Inputs, Out, assert_equal, random_taps
-from test_wideband_host import WIDE_RATE
-from test_wideband_rational_host import wbr_model, wbr_model_inc
-from test_wideband_tx_host import wbtx_model
-from test_wideband_tx_rational_host import wbtxr_model, wbtxr_outputs
+from fixtures import amd, torch_dev  # noqa: F401
+from stream_runs import CHUNK, code_raised_by
+from wideband_device import (CANARY, LOOP_10M, PLAN_10M, Inputs, Out, assert_equal, assert_exactness_preconditions, check_plan_streams_10m,
+                             exactness_inputs, first_one_tap_window, loop_taps_10m, loopback_on_the_cpu, plan_taps_10m, push_pieces,
+                             run_absent_channel_schedule)
+from wideband_models import WIDE_RATE, tx_phase_taps, wbr_model, wbr_model_inc, wbtx_model, wbtxr_model, wbtxr_outputs
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ESTATE = -1, -6
 
 
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.lib()
-    return m
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
 def phase_of(M, U, n):
     return (np.arange(n, dtype=np.int64) * U) % M
-
-
-def push_pieces(tx, src, out, M, U, K, cuts):
-    """pushes inputs [cuts[i], cuts[i + 1]) of every channel in turn, each to where the rational count puts it in `out`"""
-    for lo, hi in zip(cuts, cuts[1:]):
-        tx.push([src.ptr(k, lo) for k in range(K)], hi - lo, out.ptr(wbtxr_outputs(M, U, lo)))
-        assert tx.samples() == hi
 
 
 # ------------------------------------------------------------------ 1. exactness
@@ -70,61 +48,29 @@ def test_outputs_equal_the_integer_model_on_every_sample(amd, torch_dev, case):
     phase other than 0; more outputs than one workgroup's tile; == the model"""
     M, U, L, K, S, first, N, kind = CASES[case]
     rng = np.random.default_rng(sum(map(ord, case)))
-    fw = M * WIDE_RATE / U
-    centres = list(rng.uniform(-fw / 2, fw / 2, K))
     T = amd.wb_lo_table()
-    if kind == "random":
-        chans, taps = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)], random_taps(rng, L, M)
-    elif kind == "fullscale":
-        chans = []
-        for _ in range(K):
-            x = rng.choice(np.array([-32768, 32767], np.int16), 2 * N)
-            x[: 2 * 600] = np.repeat(rng.choice(np.array([-32768, 32767], np.int16), 2 * 600 // 40), 40)       # runs: the filter's sum builds up
-            chans.append(x)
-        h = np.hamming(L)
-        taps = np.rint(h / h.sum() * 65000).astype(np.int16)              # gain 65000 x 32767 / 2^29 = 3.97 per channel
-    elif kind == "unit":
-        centres[0] = 0.0
-        chans, taps = [rng.integers(-1, 2, 2 * N).astype(np.int16)], np.array([1], np.int16)
-    elif kind == "halfway":
-        centres[0] = 0.0
-        chans, taps = [rng.integers(-7, 8, 2 * N).astype(np.int16)], np.array([1, 1], np.int16)        # (|32767 x 7| / 8 stays inside int16: no clamp hides the rounding)
-    else:
-        centres = [0.0] * K
-        chans, taps = [np.full(2 * N, -32768, np.int16) for _ in range(K)], np.array([-32768, -32767], np.int16)
-    assert len(taps) == L
+    chans, taps, centres = exactness_inputs(kind, rng, "tx", M * WIDE_RATE / U, K, N, L, M)
+    if kind == "unit":
+        centres[0] = 0.0                                                   # (the empty-phase case below reads its expectation off centre 0)
     inc = amd.wbtxr_plan(M, U, centres, taps, S, first)
     assert np.array_equal(inc, wbr_model_inc(M, U, centres))
     exp = wbtxr_model(T, chans, M, U, inc, taps, S, first)
     W = amd.wbtxr_outputs(M, U, N)
     assert W == wbtxr_outputs(M, U, N) and exp.size == 2 * W and W > 256, "more than one workgroup of outputs"
-    inside = np.abs(exp.astype(np.int32)) < 32767
     p_n = phase_of(M, U, W)
-    if kind == "random":
-        assert inside.mean() > 0.6 and np.unique(exp).size > 100, "the case must not hide behind the clamp"
     if kind == "unit":
         # centre 0, one tap of 1 at phase 0: w = 32767 x (I, Q) where p_n = 0, exactly 0 elsewhere
         assert not exp[0::2][p_n != 0].any() and not exp[1::2][p_n != 0].any() and (p_n != 0).sum() > W // 4
         q_0 = ((np.arange(W, dtype=np.int64) * U) // M)[p_n == 0]
         assert np.array_equal(exp[0::2][p_n == 0], 32767 * chans[0][0::2].astype(np.int64)[q_0]) and exp[0::2].any() and exp[1::2].any()
-    if kind == "fullscale":
-        assert (exp == 32767).sum() > 10 and (exp == -32768).sum() > 10 and inside.sum() > 10
+    w = None
     if kind == "halfway":
         # centre 0: w = 32767 x I[q_n] on phases 0 and 1 (a tap of 1 each), 0 on phase 2 (no tap). With S = 3 a sum is half-way when
         # w = 4 (mod 8), i.e. I = 4 (mod 8): I = -4
         q_n = (np.arange(W, dtype=np.int64) * U) // M
         w = np.where(p_n < 2, 32767 * chans[0][0::2].astype(np.int64)[q_n], 0)
-        half = (w < 0) & (w % 8 == 4)
-        assert half.sum() > 5 and (p_n == 2).any()
-        assert np.array_equal(exp[0::2], (w + 4) >> 3)                     # floor
-        away = np.sign(w) * ((np.abs(w) + 4) >> 3)                         # round half away from zero
-        trunc = np.trunc((w + 4) / 8.0).astype(np.int64)                   # C's division, which truncates
-        assert (away != exp[0::2]).any() and (trunc != exp[0::2]).any()
-    if kind == "bound":
-        # per channel y = 65535 x 32768 = 2^31 - 2^15 (the largest |y| the limits allow), c = 32767: the sum is 256 y c, just under 2^54 per
-        # component of the 2^55 bound, and comes out unclamped
-        total = 256 * (65535 * 32768) * 32767
-        assert (1 << 53) < total < (1 << 55) and (exp[2:] == (total + (1 << 39)) >> 40).all() and 0 < exp[2] < 32767
+        assert (p_n == 2).any()
+    assert_exactness_preconditions(kind, exp, unclamped=("random",), halfway=(w, exp[0::2]))
     if "wrap32" in case:
         assert first < (1 << 32) <= first + W
     if "all_rows" in case:
@@ -155,7 +101,7 @@ def test_up_1_delivers_the_bytes_of_the_integer_bank(amd, torch_dev, M, L):
     rng = np.random.default_rng(50 + M)
     K, S, first, N = 5, 32, (1 << 32) - 1000, 700
     centres = list(rng.uniform(-M * WIDE_RATE / 2, M * WIDE_RATE / 2, K))
-    chans, taps = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)], random_taps(rng, L, M)
+    chans, taps = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)], tx_phase_taps(rng, L, M)
     T = amd.wb_lo_table()
     inc = amd.wbtxr_plan(M, 1, centres, taps, S, first)
     assert np.array_equal(inc, amd.wbtx_plan(M, centres, taps, S, first))
@@ -191,7 +137,7 @@ def test_any_split_absent_channels_shared_buffers_and_reset(amd, torch_dev):
     assert H == 7
     fw = M * WIDE_RATE / U
     centres = [300000.0, -700000.0, 0.0, 0.3 * fw]
-    taps = random_taps(rng, L, M)
+    taps = tx_phase_taps(rng, L, M)
     # (n_in, channels present): channel 3 always reads channel 0's buffer
     everyone = {0, 1, 2, 3}
     schedule = [(1, everyone), (H - 2, {0, 2, 3}), (0, everyone), (1, everyone), (H - 1, {1, 3}), (200, everyone),
@@ -207,16 +153,10 @@ def test_any_split_absent_channels_shared_buffers_and_reset(amd, torch_dev):
         src = Inputs(torch_dev, data)
         for first in (12345, (1 << 32) - 77):
             fed = [x.copy() for x in data] + [data[0].copy()]
-            out, at, single = Out(torch_dev, W), 0, set()
-            for n, present in schedule:
-                for k in range(K):
-                    if k not in present:
-                        fed[k][2 * at: 2 * (at + n)] = 0
-                tx.push([src.ptr(0 if k == 3 else k, at) if k in present else None for k in range(K)], n, out.ptr(wbtxr_outputs(M, U, at)))
-                if n == 1:
-                    single.add(amd.wbtxr_outputs(M, U, at + 1) - amd.wbtxr_outputs(M, U, at))
-                at += n
-                assert tx.samples() == at
+            out = Out(torch_dev, W)
+            run_absent_channel_schedule(tx, src, out, schedule, K, fed, lambda at: wbtxr_outputs(M, U, at))
+            starts = np.cumsum([0] + [n for n, _ in schedule])
+            single = {amd.wbtxr_outputs(M, U, int(at) + 1) - amd.wbtxr_outputs(M, U, int(at)) for at, (n, _) in zip(starts, schedule) if n == 1}
             assert single == {4, 5}, single
             exp = wbtxr_model(T, fed, M, U, inc, taps, S, first)
             assert W > 256 and exp.size == 2 * W and (np.abs(exp.astype(np.int32)) < 32767).mean() > 0.6
@@ -237,7 +177,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
     rng = np.random.default_rng(34)
     M, U, S, K = 5, 3, 31, 2
     L = M * 4 + 2
-    centres, taps = [250000.0, -400000.0], random_taps(rng, L, M)
+    centres, taps = [250000.0, -400000.0], tx_phase_taps(rng, L, M)
     N, piece = 600, 200
     data = [rng.integers(-32768, 32768, 2 * N).astype(np.int16) for _ in range(K)]
     exp = wbtxr_model(amd.wb_lo_table(), data, M, U, wbr_model_inc(M, U, centres), taps, S)
@@ -272,7 +212,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
             (EINVAL, lambda: amd._chk(L_.opv_wbtx_push(None, tab, piece, C.c_void_p(scratch.ptr())))),          # null object
         ]
         for code, call in refusals:
-            assert code_of(amd, call) == code
+            assert code_raised_by(amd, call) == code
             assert tx.samples() == piece
         torch.cuda.synchronize()
         assert np.array_equal(scratch.buf.cpu().numpy(), canary) and np.array_equal(src.t.cpu().numpy(), np.stack(data))
@@ -281,7 +221,7 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
         tx.push(ins, piece, out.ptr(cum[1]))
         # the last push reads channel 0 from `adj`: an output one sample into that input is refused, the one that ends where it begins is taken
         last = [adj_in, src.ptr(1, 2 * piece)]
-        assert code_of(amd, lambda: tx.push(last, piece, adj.data_ptr() + 8)) == EINVAL and tx.samples() == 2 * piece
+        assert code_raised_by(amd, lambda: tx.push(last, piece, adj.data_ptr() + 8)) == EINVAL and tx.samples() == 2 * piece
         tx.push(last, piece, adj.data_ptr() + 4)
         assert tx.samples() == N
         torch.cuda.synchronize()
@@ -296,8 +236,8 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
         d2.close()
         scratch.buf.fill_(CANARY)
         torch.cuda.synchronize()
-        assert code_of(amd, lambda: tx2.push(ins, piece, scratch.ptr())) == ESTATE
-        assert code_of(amd, lambda: tx2.reset(0)) == ESTATE
+        assert code_raised_by(amd, lambda: tx2.push(ins, piece, scratch.ptr())) == ESTATE
+        assert code_raised_by(amd, lambda: tx2.reset(0)) == ESTATE
         assert tx2.samples() == piece and np.array_equal(scratch.buf.cpu().numpy(), canary)
         tx2.close()
     finally:
@@ -306,62 +246,38 @@ def test_refused_pushes_change_nothing(amd, torch_dev):
 
 
 # ------------------------------------------------------------------ 5. loopback at 10 MS/s: transmit bank -> up-converters -> rational door -> demodulators
-LOOP = dict(down=PLAN["down"], up=PLAN["up"], centres=PLAN["centres"][:3], out_shift=32, frames=2, tail=4000)
-
-
-def loop_taps():
-    """the door's prototype (Hamming-windowed sinc, cutoff 200 kHz, at 1250 x 2.168 MS/s) cut to L = 100 002 - 96 x 271 = 73 986 taps
-    (J = 60), so that the two filters' delays add to exactly one symbol, and scaled to sum 1250 x 2^15: unity gain through the
-    zero-stuffing by 1250 (x 32767 / 2^32 from the LO)"""
-    M = LOOP["down"]
-    L = 100002 - PLAN["J"] * PLAN["up"]
-    assert L == 73986 and -(-L // M) == 60 and (L - 1) + (PLAN["J"] * PLAN["up"] - 1) == 2 * 40 * M
-    t = np.arange(L) - (L - 1) / 2
-    h = np.sinc(2 * PLAN["cutoff_hz"] / (M * WIDE_RATE) * t) * np.hamming(L)
-    taps = np.rint(h / h.sum() * M * (1 << 15)).astype(np.int16)
-    assert max(np.abs(taps[p::M].astype(np.int64)).sum() for p in range(M)) <= 65535
-    return taps
-
-
 @pytest.fixture(scope="module")
 def loop(amd, oracle):
     """the chain on the CPU, from the two models and the oracle alone: -> dict(tx[k], chans[k], wide, model[k], exp[k]). All three
     channels start at sample 0 and the run ends with the modulator's 4000 silent samples."""
-    F, M, U = LOOP["frames"], LOOP["down"], LOOP["up"]
-    tx = [amd.bert_frames(F, "WT%d" % k, first=10 * k) for k in range(3)]
-    chans = [amd.modulate(f) for f in tx]
-    for x in chans:
-        assert x.size == 2 * (F * CHUNK + LOOP["tail"]) and not x[2 * F * CHUNK:].any()           # the tail is silence: an all-null push makes it
-    T = amd.wb_lo_table()
-    wide = wbtxr_model(T, chans, M, U, wbr_model_inc(M, U, LOOP["centres"]), loop_taps(), LOOP["out_shift"])
-    assert 8000 < np.max(np.abs(wide.astype(np.int32))) < 32767           # well inside int16: no clamp between the banks
-    model = wbr_model(T, wide, M, U, wbr_model_inc(M, U, PLAN["centres"]), plan_taps(), PLAN["out_shift"])
-    exp = [oracle.receive(model[k], streaming=True) for k in range(4)]
-    # the preconditions, from the reference alone: every transmitted frame on slots 0 - 2 and no one-tap window on them, nothing
-    # released on the empty slot, whose one-tap windows are why check_plan_streams' slot rule is the one to use
+    M, U = LOOP_10M["down"], LOOP_10M["up"]
+    chain = loopback_on_the_cpu(
+        amd, oracle, LOOP_10M,
+        lambda T, chans: wbtxr_model(T, chans, M, U, wbr_model_inc(M, U, LOOP_10M["centres"]), loop_taps_10m(), LOOP_10M["out_shift"]),
+        lambda T, wide: wbr_model(T, wide, M, U, wbr_model_inc(M, U, PLAN_10M["centres"]), plan_taps_10m(), PLAN_10M["out_shift"]))
+    # on top of its preconditions, from the reference alone: no one-tap window on slots 0 - 2; the empty slot's one-tap windows are why
+    # check_plan_streams_10m's slot rule is the one to use
     for k in range(3):
-        assert np.array_equal(exp[k]["frames"], tx[k]), f"loopback plan: the oracle alone does not decode channel {k}"
-        assert first_one_tap_window(exp[k])[1] == 0, f"loopback plan: channel {k} shows a one-tap window"
-    assert len(exp[3]["frames"]) == 0, "loopback plan: the oracle releases frames on the empty slot"
-    assert first_one_tap_window(exp[3])[1] >= 1
-    return dict(tx=tx, chans=chans, wide=wide, model=model, exp=exp)
+        assert first_one_tap_window(chain["exp"][k])[1] == 0, f"loopback plan: channel {k} shows a one-tap window"
+    assert first_one_tap_window(chain["exp"][3])[1] >= 1
+    return chain
 
 
 def test_loopback_at_10_msps_through_the_products_own_chain(amd, torch_dev, loop):
     """a TxBank of 3 streams modulates one frame per round; WidebandTx.rational(1250, 271) puts the three captures at -3.1, 0.0 and
     +1.7 MHz of a wide capture at 10 MS/s (an all-null push of 4000 samples is the tail); every wide block goes straight into
     Wideband.rational(1250, 271).push_device, which feeds a 4-stream Demod (the last slot, +3.9 MHz, is empty). The wide capture ==
-    wbtxr_model, each stream's IQ == wbr_model of it, each stream passes check_plan_streams against the oracle on that IQ, frames
+    wbtxr_model, each stream's IQ == wbr_model of it, each stream passes check_plan_streams_10m against the oracle on that IQ, frames
     == the transmitted ones on slots 0 - 2 and none on slot 3."""
     torch, dev = torch_dev
-    F, M, U, tail = LOOP["frames"], LOOP["down"], LOOP["up"], LOOP["tail"]
+    F, M, U, tail = LOOP_10M["frames"], LOOP_10M["down"], LOOP_10M["up"], LOOP_10M["tail"]
     n_in = F * CHUNK + tail
     n_wide = wbtxr_outputs(M, U, n_in)
     assert wbtxr_outputs(M, U, CHUNK) * U == CHUNK * M and 2 * n_wide == loop["wide"].size      # a frame is a whole number of wide samples
     d = amd.Demod(4, max_samples=loop["model"].shape[1] // 2 + 64, streaming=True)
     bank = amd.TxBank(d, 3)
-    up = amd.WidebandTx.rational(d, M, U, LOOP["centres"], loop_taps(), LOOP["out_shift"])
-    wb = amd.Wideband.rational(d, M, U, [0, 1, 2, 3], PLAN["centres"], plan_taps(), PLAN["out_shift"])
+    up = amd.WidebandTx.rational(d, M, U, LOOP_10M["centres"], loop_taps_10m(), LOOP_10M["out_shift"])
+    wb = amd.Wideband.rational(d, M, U, [0, 1, 2, 3], PLAN_10M["centres"], plan_taps_10m(), PLAN_10M["out_shift"])
     try:
         lanes = torch.zeros((3, 2 * CHUNK), dtype=torch.int16, device=dev)
         assert lanes.data_ptr() % 16 == 0 and (lanes.stride(0) * 2) % 16 == 0
@@ -382,7 +298,7 @@ def test_loopback_at_10_msps_through_the_products_own_chain(amd, torch_dev, loop
         wb.flush()
         d.process()
         d.sync()
-        check_plan_streams(amd, d, loop, "loopback")                       # (pops every slot's frames: == the oracle's)
+        check_plan_streams_10m(amd, d, loop, "loopback")                       # (pops every slot's frames: == the oracle's)
         for k in range(3):                                                 # ... which are the transmitted ones, and none on slot 3
             assert np.array_equal(loop["exp"][k]["frames"], loop["tx"][k]) and d.state(k).frames_released == len(loop["tx"][k]), k
         assert len(loop["exp"][3]["frames"]) == 0 and d.state(3).frames_released == 0

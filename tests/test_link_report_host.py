@@ -10,17 +10,11 @@ import numpy as np
 import pytest
 
 import soft_log_inputs as S
-from amd_lib import ROOT, load
+from amd_lib import ROOT
+from fixtures_built import amd  # noqa: F401
 from link_model import BOUND, CODED, link_model
 
 NAMES = ["opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads"]
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
 
 
 def test_header_declares_the_link_report_and_exports_carry_it(amd):

@@ -161,15 +161,15 @@ def test_fuzz_recipe(iq10, iq100, seed):
 
 @pytest.fixture(scope="module")
 def wideband_slot():
-    """slot 0 of test_gpu_wideband_rational's 10 MS/s plan as the numpy model of test_wideband_rational_host says the door
+    """slot 0 of the 10 MS/s plan (wideband_device.PLAN_10M) as the numpy model (wideband_models.wbr_model) says the door
     delivers it: a clean channel that is digitally silent behind its two frames"""
-    from test_gpu_wideband_rational import PLAN, make_plan_wide, plan_taps
-    from test_wideband_rational_host import wbr_model, wbr_model_inc
+    from wideband_device import PLAN_10M, make_plan_wide_10m, plan_taps_10m
+    from wideband_models import wbr_model, wbr_model_inc
     amd = load()
     amd.build()
-    wide, _tx = make_plan_wide(amd, 2)
-    inc = wbr_model_inc(PLAN["down"], PLAN["up"], PLAN["centres"][:1])
-    return wbr_model(amd.wb_lo_table(), wide, PLAN["down"], PLAN["up"], inc, plan_taps(), PLAN["out_shift"])[0]
+    wide, _tx = make_plan_wide_10m(amd, 2)
+    inc = wbr_model_inc(PLAN_10M["down"], PLAN_10M["up"], PLAN_10M["centres"][:1])
+    return wbr_model(amd.wb_lo_table(), wide, PLAN_10M["down"], PLAN_10M["up"], inc, plan_taps_10m(), PLAN_10M["out_shift"])[0]
 
 
 @pytest.mark.parametrize("streaming", [True, False], ids=["stream", "batch"])

@@ -3,16 +3,9 @@ build is OPV_EINVAL (the device half of stream migration is tests/test_gpu_strea
 import numpy as np
 import pytest
 
-from amd_lib import load
+from fixtures_built import amd  # noqa: F401
 
 EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
 
 
 def test_blob_streams_refuses_what_is_not_a_blob_without_a_device(amd):

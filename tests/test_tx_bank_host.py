@@ -9,18 +9,11 @@ import numpy as np
 import pytest
 
 import tx_bank_model as M
-from amd_lib import load
+from fixtures_built import amd  # noqa: F401
 
 EINVAL, ECAPACITY = -1, -4
 FRAME_BYTES_OUT = M.FRAME_SAMPLES * 4
 MAX_RUN_FRAMES = 65536
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
 
 
 def refusal(amd, *args):

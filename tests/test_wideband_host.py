@@ -1,61 +1,16 @@
 """CPU-only: the host half of the wideband front door (include/opv_demod.h, opv_wb_*) - plan, LO table, output count, struct
-layout - against a numpy int64 restatement of the header's arithmetic. The model lives here (wb_model_*), and
-tests/test_gpu_wideband.py holds the device to the same functions with ==."""
+layout - against a numpy int64 restatement of the header's arithmetic. The model is tests/wideband_models.py (wb_model_inc,
+wb_model), and tests/test_gpu_wideband.py holds the device to the same functions with ==."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
-from amd_lib import ROOT, load
+from fixtures_built import amd  # noqa: F401
+from struct_layout import check_ctypes_layout
+from wideband_models import WIDE_RATE, wb_model, wb_model_inc
 
 EINVAL = -1
-WIDE_RATE = 2168000.0
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
-
-
-# ------------------------------------------------------------------ the model: the header's arithmetic in numpy int64
-def wb_model_inc(decim, centre_hz):
-    """inc_k = (uint32) llrint(f_k / (D * 2 168 000) * 2^32), modulo 2^32 (python integers: no width to overflow)"""
-    return np.array([int(np.rint(np.float64(f) / (np.float64(decim) * WIDE_RATE) * 4294967296.0)) % (1 << 32) for f in centre_hz], np.uint32)
-
-
-def wb_model(T, wide, decim, inc, taps, out_shift, first_sample=0):
-    """wide: interleaved int16 IQ of the WHOLE capture (n = 0 at its first sample). Returns [K][2 * ceil(N / D)] int16: what every
-    channel's stream must hold, whatever the split into pushes. Every product and sum is exact in int64 (|acc| < 2^52)."""
-    T = np.asarray(T, np.int64)
-    I, Q = np.asarray(wide[0::2], np.int64), np.asarray(wide[1::2], np.int64)
-    N, L, D = I.size, len(taps), int(decim)
-    n_out = (N + D - 1) // D
-    h = np.asarray(taps, np.int64)
-    a = (np.arange(N, dtype=np.uint64) + np.uint64(first_sample % (1 << 64))) & np.uint64(0xFFFFFFFF)      # only the low 32 bits of a reach phi
-    out = np.zeros((len(inc), 2 * n_out), np.int16)
-    for k, w in enumerate(inc):
-        phi = (a * np.uint64(int(w))) & np.uint64(0xFFFFFFFF)              # (a < 2^32 and inc < 2^32: the product fits uint64)
-        i = (phi >> np.uint64(20)).astype(np.int64)
-        c, s = T[i], T[(i - 1024) & 4095]
-        acc = []
-        for m in (I * c + Q * s, Q * c - I * s):
-            assert np.max(np.abs(m), initial=0) < 1 << 31
-            # acc[r] = sum_t h[t] m[r D - t], taken by decimation phase (t = p + j D): sum_p (x_p * h_p)[r] with x_p[r] = m[r D - p]
-            # (0 in front of sample 0) and h_p = h[p], h[p + D], ... - the same int64 products and sums, in another order
-            tot = np.zeros(n_out, np.int64)
-            for p in range(min(D, L)):
-                x = np.concatenate([np.zeros(1 if p else 0, np.int64), m[D - p if p else 0::D]])[:n_out]
-                if x.size:
-                    tot[:x.size] += np.convolve(x, h[p::D])[:x.size]
-            acc.append(tot)
-        ar, ai = acc
-        if out_shift:
-            ar, ai = (ar + (1 << (out_shift - 1))) >> out_shift, (ai + (1 << (out_shift - 1))) >> out_shift       # numpy's >> on int64 is arithmetic: floor
-        out[k, 0::2], out[k, 1::2] = np.clip(ar, -32768, 32767), np.clip(ai, -32768, 32767)
-    return out
 
 
 # ------------------------------------------------------------------ opv_wb_plan
@@ -136,41 +91,36 @@ def test_lo_table_is_numpys_and_far_from_every_rounding_boundary(amd):
 
 def test_wb_cfg_layout_matches_header(amd, tmp_path):
     """size and field offsets of the ctypes mirror against what gcc makes of include/opv_demod.h (as test_struct_layouts_match_header)"""
-    fs = [f[0] for f in amd.WbCfg._fields_]
-    assert fs == ["decim", "n_channels", "n_taps", "out_shift", "first_sample"]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "opv_demod.h"}"', "int main(void){",
-           'printf("opv_wb_cfg %zu\\n", sizeof(opv_wb_cfg));']
-    src += [f'printf("{f} %zu\\n", offsetof(opv_wb_cfg, {f}));' for f in fs]
-    src.append("return 0;}")
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["opv_wb_cfg"]) == C.sizeof(amd.WbCfg) == 24
-    for f in fs:
-        assert int(got[f]) == getattr(amd.WbCfg, f).offset, f
+    check_ctypes_layout(tmp_path, amd.WbCfg, "opv_wb_cfg", 24, ["decim", "n_channels", "n_taps", "out_shift", "first_sample"])
 
 
 def test_model_agrees_with_a_sample_by_sample_restatement(amd):
-    """the vectorised model above against the header's formulas written out one sample and one tap at a time in python integers
+    """the vectorised model (wideband_models.wb_model) against the header's formulas written out one sample and one tap at a time in python integers
     (no numpy width anywhere), on a case with a wrapping phase product, S > 0, both clamps and negative half-way accumulators"""
     rng = np.random.default_rng(5)
     T = amd.wb_lo_table()
-    D, L, S, first, N = 3, 7, 4, (1 << 32) - 5, 41
+    D, L, first, N = 3, 7, (1 << 32) - 5, 41
     wide = rng.integers(-32768, 32768, 2 * N).astype(np.int16)
     taps = np.array([3000, -7000, 12000, 32767, 12000, -7000, 3000], np.int16)
     inc = wb_model_inc(D, [250000.0, -1234567.0])
-    got = wb_model(T, wide, D, inc, taps, S, first)
-    for k, w in enumerate(inc):
-        m = []
-        for n in range(N):
-            phi = ((first + n) * int(w)) & 0xFFFFFFFF
-            i = phi >> 20
-            c, s = int(T[i]), int(T[(i - 1024) & 4095])
-            x, y = int(wide[2 * n]), int(wide[2 * n + 1])
-            m.append((x * c + y * s, y * c - x * s))
-        for r in range(-(-N // D)):
-            for comp in (0, 1):
-                acc = sum(int(taps[t]) * m[r * D - t][comp] for t in range(L) if r * D - t >= 0)
-                v = (acc + (1 << (S - 1))) // (1 << S)                      # python's // is floor
-                assert got[k, 2 * r + comp] == min(max(v, -32768), 32767), (k, r, comp)
-    assert (got == 32767).any() and (got == -32768).any()
+    # S = 4: every output of this full-range case clamps. S = 33: none can (|acc| <= sum |taps| x 2^15 x 32767 x sqrt 2 < 2^46.8, and
+    # 2^13.8 < 32767), so the rounding term and the floor show in every value
+    for S in (4, 33):
+        got = wb_model(T, wide, D, inc, taps, S, first)
+        for k, w in enumerate(inc):
+            m = []
+            for n in range(N):
+                phi = ((first + n) * int(w)) & 0xFFFFFFFF
+                i = phi >> 20
+                c, s = int(T[i]), int(T[(i - 1024) & 4095])
+                x, y = int(wide[2 * n]), int(wide[2 * n + 1])
+                m.append((x * c + y * s, y * c - x * s))
+            for r in range(-(-N // D)):
+                for comp in (0, 1):
+                    acc = sum(int(taps[t]) * m[r * D - t][comp] for t in range(L) if r * D - t >= 0)
+                    v = (acc + (1 << (S - 1))) // (1 << S)                  # python's // is floor
+                    assert got[k, 2 * r + comp] == min(max(v, -32768), 32767), (S, k, r, comp)
+        if S == 4:
+            assert (got == 32767).any() and (got == -32768).any()
+        else:
+            assert (np.abs(got.astype(np.int32)) < 32767).all() and (got < 0).any() and (got > 0).any()

@@ -1,90 +1,18 @@
 """CPU-only: the host half of the rational wideband front door (include/opv_demod.h, opv_wbr_plan / opv_wbr_outputs /
 opv_wb_create_rational; the rules are csrc/opv_wb_rules.cpp) against a numpy int64 restatement of the header's arithmetic. The
-model lives here (wbr_model_*), and tests/test_gpu_wideband_rational.py holds the device to the same functions with ==."""
+model is tests/wideband_models.py (wbr_model_inc, wbr_outputs, wbr_model), and tests/test_gpu_wideband_rational.py holds the device
+to the same functions with ==."""
 import ctypes as C
-import subprocess
 from math import gcd
 
 import numpy as np
 import pytest
 
-from amd_lib import ROOT, load
-from test_wideband_host import WIDE_RATE, wb_model, wb_model_inc
+from fixtures_built import amd  # noqa: F401
+from struct_layout import check_ctypes_layout
+from wideband_models import WIDE_RATE, per_phase_taps, wb_model, wb_model_inc, wbr_model, wbr_model_inc
 
 EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
-
-
-# ------------------------------------------------------------------ the model: the header's arithmetic in numpy int64
-def wbr_model_inc(down, up, centre_hz):
-    """fw = (double)M x 2 168 000.0 / (double)U; inc_k = (uint32) llrint(f_k / fw x 2^32), modulo 2^32 (python integers: no width to overflow)"""
-    fw = np.float64(down) * WIDE_RATE / np.float64(up)
-    return np.array([int(np.rint(np.float64(f) / fw * 4294967296.0)) % (1 << 32) for f in centre_hz], np.uint32)
-
-
-def wbr_outputs(down, up, n):
-    return -(-(int(n) * int(up)) // int(down))
-
-
-def wbr_model(T, wide, down, up, inc, taps, out_shift, first_sample=0):
-    """wide: interleaved int16 IQ of the WHOLE capture (n = 0 at its first sample). Returns [K][2 * ceil(N U / M)] int16: what every
-    channel's stream must hold, whatever the split into pushes. acc[r] = sum_j taps[p_r + j U] m[n_r - j] by a gather of m per
-    output (rows of r, columns of j), in blocks of outputs; every product and sum is exact in int64 (|acc| < 2^52)."""
-    T = np.asarray(T, np.int64)
-    I, Q = np.asarray(wide[0::2], np.int64), np.asarray(wide[1::2], np.int64)
-    N, L, M, U = I.size, len(taps), int(down), int(up)
-    J = -(-L // U)
-    n_out = wbr_outputs(M, U, N)
-    tab = np.zeros(J * U, np.int64)
-    tab[:L] = np.asarray(taps, np.int64)
-    tab = np.ascontiguousarray(tab.reshape(J, U).T)                        # tab[p, j] = taps[p + j U]
-    r = np.arange(n_out, dtype=np.int64)
-    n_r, p_r = (r * M) // U, (r * M) % U
-    assert n_out == 0 or n_r[-1] < N
-    jj = np.arange(J, dtype=np.int64)
-    a = (np.arange(N, dtype=np.uint64) + np.uint64(first_sample % (1 << 64))) & np.uint64(0xFFFFFFFF)      # only the low 32 bits of a reach phi
-    out = np.zeros((len(inc), 2 * n_out), np.int16)
-    block = max(1, (1 << 21) // J)
-    for k, w in enumerate(inc):
-        phi = (a * np.uint64(int(w))) & np.uint64(0xFFFFFFFF)
-        i = (phi >> np.uint64(20)).astype(np.int64)
-        c, s = T[i], T[(i - 1024) & 4095]
-        acc = []
-        for m in (I * c + Q * s, Q * c - I * s):
-            assert np.max(np.abs(m), initial=0) < 1 << 31
-            mp = np.concatenate([np.zeros(J - 1, np.int64), m])           # m[n] = 0 for n < 0: sample n sits at n + J - 1
-            tot = np.zeros(n_out, np.int64)
-            for b in range(0, n_out, block):
-                e = min(b + block, n_out)
-                tot[b:e] = (tab[p_r[b:e]] * mp[(n_r[b:e, None] + (J - 1)) - jj[None, :]]).sum(axis=1)
-            acc.append(tot)
-        ar, ai = acc
-        if out_shift:
-            ar, ai = (ar + (1 << (out_shift - 1))) >> out_shift, (ai + (1 << (out_shift - 1))) >> out_shift       # numpy's >> on int64 is arithmetic: floor
-        out[k, 0::2], out[k, 1::2] = np.clip(ar, -32768, 32767), np.clip(ai, -32768, 32767)
-    return out
-
-
-def halved_taps(rng, L, gain_cap=1 << 21):
-    """random int16 taps, halved until sum |.| <= gain_cap (test_gpu_wideband.random_taps, restated: that module needs a device)"""
-    h = rng.integers(-32768, 32768, L).astype(np.int64)
-    while np.abs(h).sum() > gain_cap:
-        h = h // 2
-    return h.astype(np.int16)
-
-
-def per_phase_taps(rng, L, up, random_taps, cap=1 << 21):
-    """random int16 taps whose EVERY phase (taps[p::up]) keeps sum |.| <= cap: random_taps' halving, applied per phase"""
-    taps = np.zeros(L, np.int16)
-    for p in range(min(up, L)):
-        taps[p::up] = random_taps(rng, len(taps[p::up]), cap)
-    return taps
 
 
 # ------------------------------------------------------------------ the model against a literal restatement, and against the integer door's
@@ -126,7 +54,7 @@ def test_up_1_is_the_integer_doors_model(amd, D, L, S, N):
     inc = wbr_model_inc(D, 1, centres)
     assert np.array_equal(inc, wb_model_inc(D, centres))
     wide = rng.integers(-32768, 32768, 2 * N).astype(np.int16)
-    taps = per_phase_taps(rng, L, 1, halved_taps) if L > 1 else np.array([3], np.int16)
+    taps = per_phase_taps(rng, L, 1) if L > 1 else np.array([3], np.int16)
     if S == 0:
         wide = rng.integers(-9, 10, 2 * N).astype(np.int16)
     a, b = wbr_model(T, wide, D, 1, inc, taps, S, first), wb_model(T, wide, D, inc, taps, S, first)
@@ -250,16 +178,5 @@ def test_outputs_is_ceil_n_u_over_m_at_the_edges(amd):
 
 def test_wbr_cfg_layout_matches_header(amd, tmp_path):
     """size and field offsets of the ctypes mirror against what gcc makes of include/opv_demod.h (as test_wb_cfg_layout_matches_header)"""
-    fs = [f[0] for f in amd.WbrCfg._fields_]
-    assert fs == ["down", "up", "n_channels", "n_taps", "out_shift", "reserved", "first_sample"]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "opv_demod.h"}"', "int main(void){",
-           'printf("opv_wbr_cfg %zu\\n", sizeof(opv_wbr_cfg));']
-    src += [f'printf("{f} %zu\\n", offsetof(opv_wbr_cfg, {f}));' for f in fs]
-    src.append("return 0;}")
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["opv_wbr_cfg"]) == C.sizeof(amd.WbrCfg) == 32
-    for f in fs:
-        assert int(got[f]) == getattr(amd.WbrCfg, f).offset, f
-    assert amd.WbrCfg.first_sample.offset == 24
+    offsets = check_ctypes_layout(tmp_path, amd.WbrCfg, "opv_wbr_cfg", 32, ["down", "up", "n_channels", "n_taps", "out_shift", "reserved", "first_sample"])
+    assert offsets["first_sample"] == amd.WbrCfg.first_sample.offset == 24

@@ -1,66 +1,21 @@
 """CPU-only: the host half of the wideband transmit bank (include/opv_demod.h, opv_wbtx_*) - plan, limits, struct layout - against
-a numpy int64 restatement of the header's arithmetic. The model lives here (wbtx_model), and tests/test_gpu_wideband_tx.py holds
-the device to it with ==. The increment rule and the LO table are the receive bank's (test_wideband_host.wb_model_inc,
-opv_wb_lo_table): one definition serves both directions."""
+a numpy int64 restatement of the header's arithmetic. The model is tests/wideband_models.py (wbtx_model), and
+tests/test_gpu_wideband_tx.py holds the device to it with ==. The increment rule and the LO table are the receive bank's
+(wideband_models.wb_model_inc, opv_wb_lo_table): one definition serves both directions."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
-from amd_lib import ROOT, load
-from test_wideband_host import WIDE_RATE, wb_model_inc
+from fixtures_built import amd  # noqa: F401
+from struct_layout import check_ctypes_layout
+from wideband_models import WIDE_RATE, wb_model_inc, wbtx_model
 
 EINVAL = -1
 
 
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
-
-
-# ------------------------------------------------------------------ the model: the header's arithmetic in numpy int64
-def wbtx_model(T, chans, U, inc, taps, S, first_sample=0):
-    """chans[k]: interleaved int16 IQ of channel k's WHOLE input (every channel N samples; None = N zeros, N taken from the others
-    or, if all are None, an int N in its place). Returns the 2 * N * U interleaved int16 values of the wide capture, whatever the
-    split into pushes. Every product and sum is exact in int64 (|y| < 2^31, |sum| < 2^55)."""
-    T = np.asarray(T, np.int64)
-    U = int(U)
-    sizes = {c if isinstance(c, (int, np.integer)) else len(c) // 2 for c in chans if c is not None}
-    assert len(sizes) == 1, "every channel delivers the same number of samples"
-    N = int(sizes.pop())
-    h = np.asarray(taps, np.int64)
-    n = np.arange(N * U, dtype=np.uint64)
-    a = (n + np.uint64(first_sample % (1 << 64))) & np.uint64(0xFFFFFFFF)                                   # only the low 32 bits of a reach phi
-    wr, wi = np.zeros(N * U, np.int64), np.zeros(N * U, np.int64)
-    for k, w in enumerate(inc):
-        if chans[k] is None or isinstance(chans[k], (int, np.integer)):
-            continue                                                       # zeros in, zeros out: nothing to add
-        y = []
-        for x in (np.asarray(chans[k][0::2], np.int64), np.asarray(chans[k][1::2], np.int64)):
-            # y[q U + p] = sum_j h[p + j U] x[q - j]: by phase, the convolution of x with h[p::U] (a phase without a tap gives zeros)
-            v = np.zeros(N * U, np.int64)
-            for p in range(min(U, len(h))):
-                v[p::U] = np.convolve(x, h[p::U])[:N]
-            assert np.max(np.abs(v), initial=0) < 1 << 31
-            y.append(v)
-        yr, yi = y
-        phi = (a * np.uint64(int(w))) & np.uint64(0xFFFFFFFF)              # (a < 2^32 and inc < 2^32: the product fits uint64)
-        i = (phi >> np.uint64(20)).astype(np.int64)
-        c, s = T[i], T[(i - 1024) & 4095]
-        wr += yr * c - yi * s
-        wi += yi * c + yr * s
-    if S:
-        wr, wi = (wr + (1 << (S - 1))) >> S, (wi + (1 << (S - 1))) >> S    # numpy's >> on int64 is arithmetic: floor
-    out = np.empty(2 * N * U, np.int16)
-    out[0::2], out[1::2] = np.clip(wr, -32768, 32767), np.clip(wi, -32768, 32767)
-    return out
-
-
 def test_model_agrees_with_a_sample_by_sample_restatement(amd):
-    """the vectorised model above against the header's formulas written out one sample and one tap at a time in python integers
+    """the vectorised model (wideband_models.wbtx_model) against the header's formulas written out one sample and one tap at a time in python integers
     (no numpy width anywhere), on a case with a wrapping phase product, S > 0, both clamps, negative half-way sums, L % U != 0 and
     an absent channel"""
     rng = np.random.default_rng(11)
@@ -152,15 +107,8 @@ def test_plan_refuses_what_lies_outside_the_limits(amd):
 
 def test_wbtx_cfg_layout_matches_header(amd, tmp_path):
     """size and field offsets of the ctypes mirror against what gcc makes of include/opv_demod.h (as test_wb_cfg_layout_matches_header)"""
-    fs = [f[0] for f in amd.WbtxCfg._fields_]
-    assert fs == ["interp", "n_channels", "n_taps", "out_shift", "first_sample"]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "opv_demod.h"}"', "int main(void){",
-           'printf("opv_wbtx_cfg %zu\\n", sizeof(opv_wbtx_cfg));']
-    src += [f'printf("{f} %zu\\n", offsetof(opv_wbtx_cfg, {f}));' for f in fs]
-    src.append("return 0;}")
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["opv_wbtx_cfg"]) == C.sizeof(amd.WbtxCfg) == C.sizeof(amd.WbCfg) == 24
+    fs = ["interp", "n_channels", "n_taps", "out_shift", "first_sample"]
+    offsets = check_ctypes_layout(tmp_path, amd.WbtxCfg, "opv_wbtx_cfg", 24, fs)
+    assert C.sizeof(amd.WbtxCfg) == C.sizeof(amd.WbCfg) == 24
     for f, g in zip(fs, [f[0] for f in amd.WbCfg._fields_]):
-        assert int(got[f]) == getattr(amd.WbtxCfg, f).offset == getattr(amd.WbCfg, g).offset, f
+        assert offsets[f] == getattr(amd.WbtxCfg, f).offset == getattr(amd.WbCfg, g).offset, f

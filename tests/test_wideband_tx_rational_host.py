@@ -1,78 +1,19 @@
 """CPU-only: the host half of the rational up-converter bank (include/opv_demod.h, opv_wbtxr_plan / opv_wbtxr_outputs /
 opv_wbtx_create_rational; the rules are csrc/opv_wb_rules.cpp) against a numpy int64 restatement of the header's arithmetic.
-The model lives here (wbtxr_model), and tests/test_gpu_wideband_tx_rational.py holds the device to it with ==. The increment rule
-is the rational door's (opv_wbr_plan): one definition serves both directions."""
+The model is tests/wideband_models.py (wbtxr_outputs, wbtxr_model), and tests/test_gpu_wideband_tx_rational.py holds the device to
+it with ==. The increment rule is the rational door's (opv_wbr_plan): one definition serves both directions."""
 import ctypes as C
-import subprocess
 from math import gcd
 
 import numpy as np
 import pytest
 
-from amd_lib import ROOT, load
-from test_wideband_host import WIDE_RATE, wb_model_inc
-from test_wideband_rational_host import wbr_model_inc
-from test_wideband_tx_host import wbtx_model
+from fixtures_built import amd  # noqa: F401
+from struct_layout import check_ctypes_layout
+from wideband_models import WIDE_RATE, wb_model_inc, wbr_model_inc, wbtx_model, wbtxr_model, wbtxr_outputs
 
 EINVAL = -1
 MAX_INPUTS = 1 << 50
-
-
-@pytest.fixture(scope="module")
-def amd():
-    m = load()
-    m.build()
-    return m
-
-
-# ------------------------------------------------------------------ the model: the header's arithmetic in numpy int64
-def wbtxr_outputs(down, up, n):
-    """W(N) = ceil(N M / U) in python integers"""
-    return -(-(int(n) * int(down)) // int(up))
-
-
-def wbtxr_model(T, chans, down, up, inc, taps, S, first_sample=0):
-    """chans[k]: interleaved int16 IQ of channel k's WHOLE input (every channel N samples; None = N zeros, N taken from the others
-    or, if all are None, an int N in its place). Returns the 2 * ceil(N M / U) interleaved int16 values of the wide capture, whatever
-    the split into pushes. y[n] = sum_j taps[p_n + j M] x[q_n - j] by a gather of x per output (rows of n, columns of j) from the
-    (M, J) table, in blocks of outputs; every product and sum is exact in int64 (|y| < 2^31, |sum| < 2^55)."""
-    T = np.asarray(T, np.int64)
-    M, U, L = int(down), int(up), len(taps)
-    sizes = {c if isinstance(c, (int, np.integer)) else len(c) // 2 for c in chans if c is not None}
-    assert len(sizes) == 1, "every channel delivers the same number of samples"
-    N = int(sizes.pop())
-    J = -(-L // M)
-    W = wbtxr_outputs(M, U, N)
-    tab = np.zeros(J * M, np.int64)
-    tab[:L] = np.asarray(taps, np.int64)
-    tab = np.ascontiguousarray(tab.reshape(J, M).T)                        # tab[p, j] = taps[p + j M]
-    n = np.arange(W, dtype=np.int64)
-    q_n, p_n = (n * U) // M, (n * U) % M
-    assert W == 0 or q_n[-1] < N
-    jj = np.arange(J, dtype=np.int64)
-    a = (n.astype(np.uint64) + np.uint64(first_sample % (1 << 64))) & np.uint64(0xFFFFFFFF)               # only the low 32 bits of a reach phi
-    live = [k for k in range(len(inc)) if chans[k] is not None and not isinstance(chans[k], (int, np.integer))]
-    # x[m] = 0 for m < 0: sample m sits at m + J - 1
-    xs = {k: [np.concatenate([np.zeros(J - 1, np.int64), np.asarray(chans[k][c::2], np.int64)]) for c in (0, 1)] for k in live}
-    wr, wi = np.zeros(W, np.int64), np.zeros(W, np.int64)
-    block = max(1, (1 << 21) // J)
-    for b in range(0, W, block):
-        e = min(b + block, W)
-        rows = tab[p_n[b:e]]                                               # the gathers are the same for every channel: once per block
-        at = (q_n[b:e, None] + (J - 1)) - jj[None, :]
-        for k in live:
-            yr, yi = ((rows * x[at]).sum(axis=1) for x in xs[k])
-            assert max(np.max(np.abs(yr), initial=0), np.max(np.abs(yi), initial=0)) < 1 << 31
-            phi = (a[b:e] * np.uint64(int(inc[k]))) & np.uint64(0xFFFFFFFF)        # (a < 2^32 and inc < 2^32: the product fits uint64)
-            i = (phi >> np.uint64(20)).astype(np.int64)
-            c, s = T[i], T[(i - 1024) & 4095]
-            wr[b:e] += yr * c - yi * s
-            wi[b:e] += yi * c + yr * s
-    if S:
-        wr, wi = (wr + (1 << (S - 1))) >> S, (wi + (1 << (S - 1))) >> S    # numpy's >> on int64 is arithmetic: floor
-    out = np.empty(2 * W, np.int16)
-    out[0::2], out[1::2] = np.clip(wr, -32768, 32767), np.clip(wi, -32768, 32767)
-    return out
 
 
 # ------------------------------------------------------------------ the model against a literal restatement, and against the integer bank's
@@ -262,15 +203,9 @@ def test_outputs_is_ceil_n_m_over_u_at_the_edges(amd):
 
 def test_wbtxr_cfg_layout_matches_header(amd, tmp_path):
     """size and field offsets of the ctypes mirror against what gcc makes of include/opv_demod.h (as test_wbr_cfg_layout_matches_header)"""
-    fs = [f[0] for f in amd.WbtxrCfg._fields_]
-    assert fs == ["down", "up", "n_channels", "n_taps", "out_shift", "reserved", "first_sample"] == [f[0] for f in amd.WbrCfg._fields_]
-    src = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT / "include" / "opv_demod.h"}"', "int main(void){",
-           'printf("opv_wbtxr_cfg %zu\\n", sizeof(opv_wbtxr_cfg));']
-    src += [f'printf("{f} %zu\\n", offsetof(opv_wbtxr_cfg, {f}));' for f in fs]
-    src.append("return 0;}")
-    (tmp_path / "l.c").write_text("\n".join(src))
-    subprocess.run(["gcc", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
-    got = dict(ln.split() for ln in subprocess.run([str(tmp_path / "l")], capture_output=True, text=True, check=True).stdout.splitlines())
-    assert int(got["opv_wbtxr_cfg"]) == C.sizeof(amd.WbtxrCfg) == C.sizeof(amd.WbrCfg) == 32
+    fs = ["down", "up", "n_channels", "n_taps", "out_shift", "reserved", "first_sample"]
+    assert fs == [f[0] for f in amd.WbrCfg._fields_]
+    offsets = check_ctypes_layout(tmp_path, amd.WbtxrCfg, "opv_wbtxr_cfg", 32, fs)
+    assert C.sizeof(amd.WbtxrCfg) == C.sizeof(amd.WbrCfg) == 32
     for f in fs:
-        assert int(got[f]) == getattr(amd.WbtxrCfg, f).offset == getattr(amd.WbrCfg, f).offset, f
+        assert offsets[f] == getattr(amd.WbtxrCfg, f).offset == getattr(amd.WbrCfg, f).offset, f

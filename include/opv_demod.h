@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_div_* (receive diversity: the soft symbols of several streams combined per frame);
+                               still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
                                still 7, additive: + opv_wbr_plan/ opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
                                still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
                                still 7, additive: + opv_txb_* (the transmit bank: N live modulators on the device, state carried from round to round), opv_tap_txb_patch;
@@ -413,6 +414,80 @@ int opv_enable_link_report(opv_ctx* ctx, int enable);
 long opv_pop_frames_link(opv_ctx* ctx, int stream, uint8_t* out134, size_t cap_frames, opv_frame_meta* meta, opv_link* link);
 int opv_device_link(opv_ctx* ctx, const opv_link** d_link);
 int opv_link_payloads(opv_ctx* ctx, const double* soft, size_t n_frames, opv_link* out);
+
+/* ---- receive diversity: several streams of one context that carry the SAME transmission, decoded as one ------------------
+ * (RHCP + LHCP feeds, two antennas, the voting receivers of a repeater; no counterpart in the reference, which decodes every stream
+ * alone). The soft value is |c2|^2 - |c1|^2, so summing it over branches is post-detection (square-law) combining; a frame that only
+ * some branches found is decoded from those (selection diversity). The front-end, the trackers and the per-stream decoder are not
+ * touched: the branches stay ordinary streams - opv_pop_frames, the taps, export and the wideband door behave on them as ever - and
+ * a context without a diversity object allocates and launches nothing for it.
+ *
+ * An object holds n_groups GROUPS of 1..8 BRANCH streams each. opv_div_round, enqueued on the context's stream behind the rounds
+ * (opv_process) launched so far, never waiting, does per group:
+ *   match    From each branch's cursor into its frame records (payload_symbol, sync_quality, sync_ok: what opv_frame_meta shows):
+ *            ANCHOR p0 = the smallest payload_symbol among the branches' next unconsumed records. The group frame is FINAL once every
+ *            branch without an unconsumed record can no longer release a payload starting at or before p0 + window - its earliest
+ *            possible future payload E_b (read off its tracker: a pending payload's start; behind the next window a HUNTING tracker
+ *            will examine; behind the next sync word a LOCKED one will check; infinite once the stream is flushed and its tracker is
+ *            done) is > p0 + window. Until then the group waits for a later round. MEMBERS are the branches whose next record starts
+ *            within `window` symbols of p0; their records are consumed. Frames are 2168 symbols apart and window <= 64, so the match is
+ *            unambiguous, and the emitted sequence is a pure function of the branches' complete record lists: how the input was
+ *            split into pushes and rounds decides only WHEN a frame appears.
+ *   combine  payload[i] = e_b0 soft_b0[p_b0 + i], then + e_b soft_b[p_b + i] for the other summed members in ascending branch order,
+ *            i < 2144: separate IEEE multiplications and additions (no FMA), so the same doubles in give the same bits out. e_b = w_b
+ *            (opv_div_set_weights, 1 at creation), in normalised mode w_b / scale_b with scale_b the branch frame's own quantiser scale
+ *            (mean |soft| of its payload). A member with w_b == 0, in normalised mode one whose scale is not positive and finite, and
+ *            one whose payload has already left its soft ring (counted in softs_lost) stays in `members` and is left out of `summed`.
+ *            A frame with summed == 0 is emitted with a zero payload and metric -1.
+ *   decode   scale, decoder and link record of the combined payload: the very code of opv_decode_payloads / opv_link_payloads.
+ * Losses are counted, never silent: records_lost = branch records overwritten in the stream's record ring before the group consumed
+ * them (the caller popped that branch and it ran more than frame_capacity records ahead of the group); the cursor moves forward.
+ * Each group's output ring has the context's frame_capacity slots; when it is full of unpopped frames the group STALLS (stalled = 1 in
+ * its state, nothing emitted, nothing lost) and resumes with the first round after a pop.
+ * opv_div_pop_frames implies opv_sync; it hands out the unpopped group frames in order, skipping those the decoder dropped (metric
+ * -1) exactly as opv_pop_frames does; `link` may be null. opv_div_tap_payload (parity tap): the 2144 combined doubles of group frame
+ * `frame` (0 = the first ever emitted, dropped ones count) while it is among the last frame_capacity; returns 2144.
+ * Weights (finite, >= 0) apply to frames emitted by rounds enqueued after the call.
+ * Reset and import: after opv_reset_stream or opv_import_streams on a branch the group's cursor for that branch restarts at the
+ * stream's new frame count (0 after a reset, the imported stream's count of released frames after an import): the context notes
+ * the restart per stream, and the next opv_div_round carries it to the device in front of its match. Frames already emitted stay;
+ * nothing is combined across the restart. The object does not migrate: rebuild it at the destination, as with opv_wb.
+ * Refusals, OPV_EINVAL: null arguments, n_groups < 1, a branch count outside 1..8, window outside 0..64, a stream out of range,
+ * a stream named twice or already in a live diversity object of the context, weights that are not finite or negative, a group out
+ * of range. An object that outlives its context is detached like an opv_wb: its calls answer OPV_ESTATE and opv_div_destroy frees
+ * only what is the object's own.
+ * opv_div_match: the matching rule alone, on the host, no device needed: branch b has n_recs[b] records recs[b] (ascending
+ * payload_symbol) and the earliest future payload earliest[b] (OPV_DIV_ENDED: none will come); from cursors[b] (in / out) it writes
+ * the final group frames in order, at most cap, and returns their number. opv_div_earliest: E_b off a tracker's carry. */
+#define OPV_DIV_MAX_BRANCHES 8
+#define OPV_DIV_MAX_WINDOW 64
+#define OPV_DIV_ENDED 0xFFFFFFFFFFFFFFFFull
+typedef struct opv_div opv_div;
+typedef struct opv_div_cfg { int32_t n_groups, window, normalise, reserved; } opv_div_cfg;   /* window in symbols, 0..64 (8 is a good default) */
+typedef struct opv_div_meta {            /* 88 bytes */
+    uint64_t payload_symbol[8];          /* per branch; valid where the members bit is set */
+    uint32_t members, summed;            /* bit b = branch b */
+    int32_t  viterbi_metric, sync_ok;    /* sync_ok = OR over the summed members */
+    double   sync_quality;               /* max over the summed members */
+} opv_div_meta;
+typedef struct opv_div_state {           /* 24 bytes */
+    uint32_t frames_emitted;             /* group frames matched so far (dropped ones included) */
+    uint32_t frames_decoded, frames_perfect;   /* among them: metric >= 0, metric == 0 */
+    uint32_t records_lost, softs_lost;
+    int32_t  stalled;                    /* the last round stopped in front of a full output ring */
+} opv_div_state;
+typedef struct opv_div_rec { uint64_t payload_symbol; double sync_quality; int32_t sync_ok, reserved; } opv_div_rec;
+typedef struct opv_div_frame { uint64_t anchor; uint64_t payload_symbol[8]; uint32_t members, reserved; } opv_div_frame;
+int  opv_div_create(opv_div** out, opv_ctx* ctx, const opv_div_cfg* cfg, const int* n_branches /*[n_groups]*/, const int* streams /*concatenated*/);
+void opv_div_destroy(opv_div* div);
+int  opv_div_set_weights(opv_div* div, int group, const double* w /*[branches of the group]*/);
+int  opv_div_round(opv_div* div);
+long opv_div_pop_frames(opv_div* div, int group, uint8_t* out134, size_t cap_frames, opv_div_meta* meta, opv_link* link);
+int  opv_div_get_state(opv_div* div, int group, opv_div_state* out);
+long opv_div_tap_payload(opv_div* div, int group, uint32_t frame, double* out2144);
+long opv_div_match(int n_branches, uint32_t window, const opv_div_rec* const* recs, const uint32_t* n_recs, const uint64_t* earliest,
+                   uint32_t* cursors, opv_div_frame* out, size_t cap);
+uint64_t opv_div_earliest(int32_t collecting, int32_t sync_state, uint64_t anchor_symbol, uint64_t next_symbol, int32_t ended);
 
 /* ---- multi-GPU (BASELINE configs[4]; no counterpart in the reference, whose streams are separate processes) -----------
  * Streams shard contiguously over GPUs - one context per GPU, no data-path collective - and the decoded frames return to one

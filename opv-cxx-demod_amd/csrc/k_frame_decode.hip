@@ -41,7 +41,7 @@
 
 #include <type_traits>
 
-#include "opv_device.h"
+#include "opv_div_rules.h"   // (brings opv_device.h)
 #include "opv_frame_code.h"
 
 namespace {
@@ -485,4 +485,33 @@ extern "C" __global__ __launch_bounds__(64) void k_decode_payloads(const double*
     };
     const bool two = f + 1u < n;
     decode_two(io(f, true), io(two ? f + 1u : f, two), lds);
+}
+
+// ---- receive diversity (k_diversity.hip, opv_diversity.hip): the same scale pre-pass and decoder over a group's ring of COMBINED
+// payloads [cap][2144], group frames dec_from .. n_frames-1 flattened and strided like k_frame_scale / k_frame_decode above
+extern "C" __global__ __launch_bounds__(64) void k_div_scale(OpvDivGroup* __restrict__ groups, uint32_t per_group, uint32_t n_groups) {
+    const uint32_t id = blockIdx.x * 64u + threadIdx.x;
+    const uint32_t gidx = id / per_group;
+    if (gidx >= n_groups) return;
+    OpvDivGroup& g = groups[gidx];
+    const uint32_t n_frames = g.n_frames;
+    for (uint32_t f = g.dec_from + id % per_group; f < n_frames; f += per_group) {
+        const uint32_t slot = f % g.cap;
+        g.scale[slot] = payload_scale(g.payload + (size_t)slot * OPV_CODED, 0u, 0xFFFFFFFFu);
+    }
+}
+extern "C" __global__ __launch_bounds__(64) void k_div_decode(OpvDivGroup* __restrict__ groups, uint32_t pairs_per_group) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[kDecodeLds];
+    OpvDivGroup& g = groups[blockIdx.x / pairs_per_group];
+    const uint32_t n_frames = g.n_frames;
+    for (uint32_t f = g.dec_from + 2u * (blockIdx.x % pairs_per_group); f < n_frames; f += 2u * pairs_per_group) {
+        const uint32_t sa = f % g.cap, sb = (f + 1u) % g.cap;
+        const bool two = f + 1u < n_frames;
+        const FrameIo A{g.payload + (size_t)sa * OPV_CODED, 0u, 0xFFFFFFFFu, g.scale[sa], g.frames + (size_t)sa * OPV_FB, g.metrics + sa,
+                        nullptr, nullptr, nullptr, true};
+        const FrameIo B{g.payload + (size_t)sb * OPV_CODED, 0u, 0xFFFFFFFFu, two ? g.scale[sb] : 0.0, g.frames + (size_t)sb * OPV_FB, g.metrics + sb,
+                        nullptr, nullptr, nullptr, two};
+        decode_two(A, B, lds);
+        __syncthreads();                          // the next pair reuses this workgroup's LDS
+    }
 }

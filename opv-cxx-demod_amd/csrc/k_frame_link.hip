@@ -26,6 +26,7 @@
 
 #include "../../include/opv_demod.h"
 #include "opv_device.h"
+#include "opv_div_rules.h"
 #include "opv_frame_code.h"
 
 static_assert(sizeof(opv_link) == 40, "opv_link is 40 bytes");
@@ -123,4 +124,17 @@ extern "C" __global__ __launch_bounds__(64, 4) void k_link_payloads(const double
     const uint32_t f = blockIdx.x;
     if (f >= n) return;
     link_one(soft + (size_t)f * OPV_CODED, 0u, 0xFFFFFFFFu, scales[f], metrics[f], frames + (size_t)f * OPV_FB, out + f, s_bits);
+}
+
+// receive diversity (k_diversity.hip): the record of every combined payload of the round, behind k_div_decode; flattened and
+// strided like k_frame_link
+extern "C" __global__ __launch_bounds__(64, 4) void k_div_link(OpvDivGroup* __restrict__ groups, uint32_t per_group) {
+    __shared__ uint8_t s_bits[kLinkLds];
+    const OpvDivGroup& g = groups[blockIdx.x / per_group];
+    const uint32_t n_frames = g.n_frames;
+    for (uint32_t f = g.dec_from + blockIdx.x % per_group; f < n_frames; f += per_group) {
+        const uint32_t slot = f % g.cap;
+        link_one(g.payload + (size_t)slot * OPV_CODED, 0u, 0xFFFFFFFFu, g.scale[slot], g.metrics[slot], g.frames + (size_t)slot * OPV_FB,
+                 (opv_link*)g.link + slot, s_bits);
+    }
 }

@@ -376,6 +376,7 @@ extern "C" int opv_process(opv_ctx* c) {
     const uint64_t fr = round_frames(ri.max_new, ri.max_tapped, c->cap_frames);
     if (!round_fits_grid(fr, S)) return fail(OPV_EINVAL, "opv_process: streams x frames per round exceeds the grid limit");
     commit_host_view(c, slot);
+    c->div.launched(fr);
     const OpvGlobalCfg g{c->cfg.streaming, c->cfg.have_init_offset, c->cfg.init_offset_hz};
     if (int r = upload_inputs(c, in, slot)) return r;
     if (int r = launch_search(c, g)) return r;
@@ -406,6 +407,7 @@ extern "C" int opv_reset_stream(opv_ctx* c, int s) {
     HIPCHK(hipStreamSynchronize(c->stream));
     const int lo = (s == -1) ? 0 : s, hi = (s == -1) ? c->n_streams : s + 1;
     for (int i = lo; i < hi; ++i) c->hs[i] = reset_host_stream(c->hs[i]);
+    for (int i = lo; i < hi; ++i) c->div.restarted(i, 0u);     // (a diversity group's cursor for the stream restarts at frame 0)
     HIPCHK(hipMemcpyAsync(c->d_streams + lo, &c->initial[lo], sizeof(OpvStream) * (hi - lo), hipMemcpyHostToDevice, c->stream));
     k_fill_i32<<<256, 256, 0, c->stream>>>(c->d_metrics + (size_t)c->cap_frames * lo, INT32_MIN,
                                           (size_t)c->cap_frames * (hi - lo));

@@ -11,6 +11,7 @@
 
 #include "../../include/opv_demod.h"
 #include "opv_device.h"
+#include "opv_div_rules.h"
 #include "opv_wb_internal.h"
 
 extern "C" __global__ void k_offset_search(OpvStream*, OpvGlobalCfg, const double*, uint32_t*);
@@ -31,6 +32,11 @@ extern "C" __global__ void k_payload_scale(const double*, uint32_t, double*);
 extern "C" __global__ void k_decode_payloads(const double*, uint32_t, const double*, uint8_t*, int32_t*, int8_t*, int8_t*, uint8_t*);
 extern "C" __global__ void k_frame_link(OpvStream*, opv_link*, uint32_t, uint32_t);
 extern "C" __global__ void k_link_payloads(const double*, uint32_t, const double*, const uint8_t*, const int32_t*, opv_link*);
+extern "C" __global__ void k_div_match(OpvDivGroup*, const OpvStream*);
+extern "C" __global__ void k_div_combine(const OpvDivGroup*, const OpvStream*, uint32_t);
+extern "C" __global__ void k_div_scale(OpvDivGroup*, uint32_t, uint32_t);
+extern "C" __global__ void k_div_decode(OpvDivGroup*, uint32_t);
+extern "C" __global__ void k_div_link(OpvDivGroup*, uint32_t);
 extern "C" __global__ void k_stream_pack(const OpvMove*, uint32_t);
 extern "C" __global__ void k_stream_unpack(OpvStream*, int32_t*, const OpvUnpackItem*, uint32_t, const OpvMove*, uint32_t);
 extern "C" __global__ void k_channel(const int4*, int4*, uint64_t, double, double, double, uint64_t);
@@ -73,6 +79,22 @@ struct GrowBuf {
         return OPV_OK;
     }
     ~GrowBuf() { if (p) (void)(kPinned ? hipHostFree(p) : hipFree(p)); }   // (opv_destroy: behind its waits, on the context's device)
+};
+
+// What a context and its diversity objects (opv_diversity.hip) share, and what outlives whichever goes first - the arrangement of
+// OpvWbShared. Created by the first opv_div_create: a context without a diversity object holds a null pointer.
+struct OpvDivShared {
+    std::vector<uint8_t> owned;       // [n_streams]: 1 while a live diversity object has the stream as a branch
+    std::vector<uint32_t> epoch;      // [n_streams]: bumped by every opv_reset_stream / opv_import_streams of the stream ...
+    std::vector<uint32_t> restart;    // ... which leaves the stream's new count of released frames here: where a group's cursor restarts
+    uint64_t frames_budget = 0;       // sum of the frame budgets (round_frames) of the rounds launched: what a diversity round sizes its grids by
+    bool ctx_alive = true;
+};
+struct OpvDivTie {                    // the context's end
+    std::shared_ptr<OpvDivShared> p;
+    ~OpvDivTie() { if (p) p->ctx_alive = false; }
+    void restarted(int s, uint32_t n_frames) { if (p) { ++p->epoch[s]; p->restart[s] = n_frames; } }
+    void launched(uint64_t fr) { if (p) p->frames_budget += fr; }
 };
 
 struct StreamIn {  // host -> device per-round update
@@ -171,6 +193,7 @@ struct opv_ctx {
     bool push_pending = false;
     hipEvent_t push_ev = nullptr;
     OpvWbTie wb;                        // which streams live wideband objects feed (opv_wideband.hip); outlives the context for them
+    OpvDivTie div;                      // which streams are branches of live diversity objects (opv_diversity.hip); null until one is created
     // stream migration (opv_export_streams / opv_import_streams): device staging buffer + pinned tables of k_stream_pack.hip, grow-only
     GrowBuf<char> mig;
     GrowBuf<char, true> mig_tab;

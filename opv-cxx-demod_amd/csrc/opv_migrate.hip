@@ -250,6 +250,7 @@ extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const v
         n.iq_seen = true;                                  // (its soft symbols came out of a front-end)
         n.chunk_floor = e.chunks_first + (uint32_t)(e.seg_n[SEG_CHUNKS] - (e.seg_n[SEG_CHUNKS] < c->cap_chunks ? e.seg_n[SEG_CHUNKS] : c->cap_chunks));
         c->hs[dst[i]] = n;
+        c->div.restarted(dst[i], e.st.n_frames);           // (a diversity group combines only what the stream releases from here on)
     }
     c->mirror_valid = false;
     c->maybe_stalled = true;

@@ -45,6 +45,8 @@ EXPORTS = [
     "opv_tap_txb_patch",
     "opv_wbtx_plan", "opv_wbtx_create", "opv_wbtx_destroy", "opv_wbtx_push", "opv_wbtx_samples", "opv_wbtx_reset",
     "opv_wbtxr_plan", "opv_wbtxr_outputs", "opv_wbtx_create_rational",
+    "opv_div_create", "opv_div_destroy", "opv_div_set_weights", "opv_div_round", "opv_div_pop_frames", "opv_div_get_state",
+    "opv_div_tap_payload", "opv_div_match", "opv_div_earliest",
 ]
 
 
@@ -85,6 +87,25 @@ class TxbState(C.Structure):
 TXB_MAX_RUN_FRAMES = 65536
 
 
+class DivCfg(C.Structure):
+    _fields_ = [("n_groups", C.c_int32), ("window", C.c_int32), ("normalise", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DivState(C.Structure):
+    _fields_ = [("frames_emitted", C.c_uint32), ("frames_decoded", C.c_uint32), ("frames_perfect", C.c_uint32),
+                ("records_lost", C.c_uint32), ("softs_lost", C.c_uint32), ("stalled", C.c_int32)]
+
+
+class DivMeta(C.Structure):
+    _fields_ = [("payload_symbol", C.c_uint64 * 8), ("members", C.c_uint32), ("summed", C.c_uint32),
+                ("viterbi_metric", C.c_int32), ("sync_ok", C.c_int32), ("sync_quality", C.c_double)]
+
+
+DIV_MAX_BRANCHES = 8
+DIV_MAX_WINDOW = 64
+DIV_ENDED = 0xFFFFFFFFFFFFFFFF
+
+
 class FrameMeta(C.Structure):
     _fields_ = [("viterbi_metric", C.c_int32), ("sync_ok", C.c_int32), ("sync_quality", C.c_double),
                 ("release_symbol", C.c_uint64), ("payload_symbol", C.c_uint64)]
@@ -103,6 +124,10 @@ EVENT_DTYPE = np.dtype(
     [("kind", "<i4"), ("count", "<i4"), ("sym_idx", "<u8"), ("corr", "<f8"), ("raw", "<f8")], align=True)
 META_DTYPE = np.dtype([("viterbi_metric", "<i4"), ("sync_ok", "<i4"), ("sync_quality", "<f8"),
                        ("release_symbol", "<u8"), ("payload_symbol", "<u8")], align=True)
+DIV_META_DTYPE = np.dtype([("payload_symbol", "<u8", (8,)), ("members", "<u4"), ("summed", "<u4"), ("viterbi_metric", "<i4"),
+                           ("sync_ok", "<i4"), ("sync_quality", "<f8")], align=True)                 # opv_div_meta, 88 bytes
+DIV_REC_DTYPE = np.dtype([("payload_symbol", "<u8"), ("sync_quality", "<f8"), ("sync_ok", "<i4"), ("reserved", "<i4")], align=True)
+DIV_FRAME_DTYPE = np.dtype([("anchor", "<u8"), ("payload_symbol", "<u8", (8,)), ("members", "<u4"), ("reserved", "<u4")], align=True)
 LINK_DTYPE = np.dtype([("valid", "<i4"), ("bit_errors", "<i4"), ("weak", "<i4"), ("nonfinite", "<i4"),
                        ("m1", "<f8"), ("m2", "<f8"), ("ma", "<f8")], align=True)          # opv_link, 40 bytes
 
@@ -273,6 +298,20 @@ def lib():
         L.opv_wbtxr_outputs.restype = C.c_uint64
         L.opv_wbtxr_outputs.argtypes = [C.POINTER(WbtxrCfg), C.c_uint64]
         L.opv_wbtx_create_rational.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbtxrCfg), C.c_void_p, C.c_void_p]
+        L.opv_div_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(DivCfg), C.c_void_p, C.c_void_p]
+        L.opv_div_destroy.restype = None
+        L.opv_div_destroy.argtypes = [C.c_void_p]
+        L.opv_div_set_weights.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.opv_div_round.argtypes = [C.c_void_p]
+        L.opv_div_pop_frames.restype = C.c_long
+        L.opv_div_pop_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.opv_div_get_state.argtypes = [C.c_void_p, C.c_int, C.POINTER(DivState)]
+        L.opv_div_tap_payload.restype = C.c_long
+        L.opv_div_tap_payload.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+        L.opv_div_match.restype = C.c_long
+        L.opv_div_match.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_div_earliest.restype = C.c_uint64
+        L.opv_div_earliest.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32]
         _lib = L
     return _lib
 
@@ -459,6 +498,91 @@ class TxBank:
     def close(self):
         if getattr(self, "h", None):
             lib().opv_txb_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def div_match(records, earliest, window=8, cursors=None, cap=None):
+    """opv_div_match (host only, no device): records[b] = the frame records of branch b (DIV_REC_DTYPE, or a plain sequence of
+    payload symbols), earliest[b] = E_b (DIV_ENDED: the branch has ended). Returns (group frames as DIV_FRAME_DTYPE, cursors)."""
+    recs = []
+    for r in records:
+        r = np.asarray(r)
+        if r.dtype != DIV_REC_DTYPE:
+            q = np.zeros(len(r), DIV_REC_DTYPE)
+            q["payload_symbol"] = r
+            r = q
+        recs.append(np.ascontiguousarray(r))
+    nb = len(recs)
+    ptrs = (C.c_void_p * max(nb, 1))(*[r.ctypes.data if len(r) else 0 for r in recs])
+    n_recs = np.array([len(r) for r in recs], np.uint32)
+    e = np.array([int(v) for v in earliest], np.uint64)
+    cur = np.zeros(nb, np.uint32) if cursors is None else np.array(cursors, np.uint32)
+    cap = int(n_recs.sum()) + 1 if cap is None else int(cap)
+    out = np.zeros(cap, DIV_FRAME_DTYPE)
+    n = _chk(lib().opv_div_match(nb, int(window), ptrs, n_recs.ctypes.data, e.ctypes.data, cur.ctypes.data, out.ctypes.data, cap))
+    return out[:n].copy(), cur
+
+
+def div_earliest(collecting, sync_state, anchor, next_symbol, ended=False):
+    """opv_div_earliest: a branch's earliest possible future payload symbol off its tracker's carry (DIV_ENDED once it has ended)"""
+    return int(lib().opv_div_earliest(int(collecting), int(sync_state), int(anchor), int(next_symbol), int(bool(ended))))
+
+
+class Diversity:
+    """Receive diversity over streams of `demod` (opv_div_*, include/opv_demod.h): groups = [[stream, ...], ...], 1..8 branch
+    streams each, that carry the same transmission and are decoded as one. round() after demod.process(); close it before its
+    Demod (one that outlives it answers OpvError -6)."""
+
+    def __init__(self, demod, groups, window=8, normalise=False):
+        self.demod = demod
+        self.groups = [[int(s) for s in g] for g in groups]
+        cfg = DivCfg(len(self.groups), int(window), int(bool(normalise)), 0)
+        nb = (C.c_int * max(len(self.groups), 1))(*[len(g) for g in self.groups])
+        flat = [s for g in self.groups for s in g]
+        st = (C.c_int * max(len(flat), 1))(*flat)
+        self.cap = int(demod.cfg.max_samples) // (FRAME_SYMBOLS * 38) + 8
+        self.h = C.c_void_p()
+        _chk(lib().opv_div_create(C.byref(self.h), demod.h, C.byref(cfg), nb, st))
+
+    def round(self):
+        """opv_div_round: match, combine and decode what the rounds launched so far have released; never waits"""
+        _chk(lib().opv_div_round(self.h))
+
+    def set_weights(self, group, w):
+        w = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if w.size != len(self.groups[group]):
+            raise OpvError("one weight per branch of the group")
+        _chk(lib().opv_div_set_weights(self.h, int(group), w.ctypes.data))
+
+    def pop_frames(self, group, link=False, cap=None):
+        """(frames, meta as DIV_META_DTYPE); with link=True (frames, meta, link records as LINK_DTYPE)"""
+        cap = cap or self.cap
+        out = np.zeros((cap, FRAME_BYTES), np.uint8)
+        meta = np.zeros(cap, DIV_META_DTYPE)
+        rec = np.zeros(cap, LINK_DTYPE)
+        n = _chk(lib().opv_div_pop_frames(self.h, int(group), out.ctypes.data, cap, meta.ctypes.data, rec.ctypes.data if link else None))
+        return (out[:n].copy(), meta[:n].copy(), rec[:n].copy()) if link else (out[:n].copy(), meta[:n].copy())
+
+    def state(self, group):
+        s = DivState()
+        _chk(lib().opv_div_get_state(self.h, int(group), C.byref(s)))
+        return s
+
+    def tap_payload(self, group, frame):
+        """opv_div_tap_payload (parity tap): the 2144 combined soft symbols of group frame `frame`"""
+        out = np.empty(ENCODED_BITS, np.float64)
+        _chk(lib().opv_div_tap_payload(self.h, int(group), int(frame), out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().opv_div_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_div_* (receive diversity: the soft symbols of several streams combined per frame);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_scan_* (wideband scan: an exact probe bank on a wide capture, and the carriers in a row of its powers);
+                               still 7, additive: + opv_div_* (receive diversity: the soft symbols of several streams combined per frame);
                                still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
                                still 7, additive: + opv_wbr_plan/ opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
                                still 7, additive: + opv_wbtx_* (wideband transmit: an exact integer up-converter bank, K channels to one wide capture);
@@ -275,6 +276,79 @@ typedef struct opv_wbr_cfg {
 int opv_wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
 size_t opv_wbr_outputs(const opv_wbr_cfg* cfg, uint64_t n_wide_total);
 int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_cfg* cfg, const int* streams, const double* centre_hz, const int16_t* taps);
+/* ---- wideband scan: which carriers are in a wide capture, and where ------------------------------------------------------
+ * The doors above take their channels' centres as given, and the receive chain behind them acquires a carrier only within the
+ * reference's coarse search (-1500 .. +1500 Hz) of where it is told to look; a radio's oscillator is off by far more. An opv_scan
+ * object is a bank of P probes on the wide capture - a Welch periodogram at P arbitrary frequencies - and opv_scan_carriers turns
+ * a row of probe powers into carrier centres good enough to hand to opv_wb_create / opv_wb_create_rational. Same contract as the
+ * doors: integer-exact, independent of summation order and of the split into pushes, held to a numpy int64 model with ==
+ * (tests/scan_model.py, tests/test_gpu_scan.py). Write P = n_probes, Lw = n_window, H = hop, A = n_avg, S = out_shift; wide samples
+ * x[n] = (I, Q) int16 at Fw = 2 168 000 x down / up S/s (the doors' pair; up = 1 is the integer door's decim = down), n = 0 at the
+ * first sample pushed into the object, a = first_sample + n:
+ *   increment: inc_p from probe_hz[p] by opv_wbr_plan's rule for the same (down, up), bit for bit (one definition serves both);
+ *   mix (the DDC's): phi = (uint32)(a x inc_p), i = phi >> 20, c = T[i], s = T[(i - 1024) & 4095] (opv_wb_lo_table),
+ *     mr = I c + Q s, mi = Q c - I s (int32);
+ *   segments: segment s >= 0 covers samples [s H, s H + Lw): z_p[s] = sum over t < Lw of window[t] x m_p[s H + t] (int64; sum |window|
+ *     <= 2^21, so |z| < 2^52); it exists once sample s H + Lw - 1 has arrived. Per component y = clamp(floor((z + 2^(S-1)) / 2^S),
+ *     -2^24, 2^24 - 1) (S = 0: no rounding term), and e_p[s] = yr^2 + yi^2 (<= 2^49);
+ *   blocks: block b is segments [b A, b A + A): E[b][p] = sum of e_p[s] over them (uint64, <= 2^61), and exists once its last segment
+ *     does. After N samples there are segs = N < Lw ? 0 : (N - Lw) / H + 1 segments and segs / A blocks (opv_scan_blocks). Samples
+ *     behind the last whole block never produce output: there is no flush;
+ *   state between pushes: N and the samples from the start of the first unfinished block on (fewer than a block's span,
+ *     (A - 1) H + Lw): any split of a capture into pushes gives the same rows.
+ *   Limits (anything else is OPV_EINVAL, decided on the host by opv_scan_plan): down and up as opv_wbr_plan's, 1 <= P <= 1024,
+ *     1 <= Lw <= 4096, 1 <= H <= 65536, 1 <= A <= 4096, (A - 1) H + Lw <= 2^20, 0 <= S <= 40, 1 <= ring_blocks <= 4096,
+ *     sum |window| <= 2^21, finite probe frequencies.
+ * opv_scan_plan (validates cfg, probes and window and writes the P increments), opv_scan_blocks (0 for a bad cfg): host only.
+ * opv_scan_create: the object belongs to ctx - its device and its copy stream, like a wideband object, so that a block of device
+ * memory can be scanned and pushed through a door in stream order - and owns no stream of it. Destroy it before its context; one
+ * that outlives it is detached: push, pop and reset answer OPV_ESTATE, and opv_scan_destroy frees only what is the object's own.
+ * opv_scan_push / _device: n_wide samples, as opv_wb_push (4-byte aligned, fewer than 2^31; pinned memory is read in place, pageable
+ * memory is staged). The blocks a push completes go to a ring of ring_blocks rows; a push whose completed blocks do not fit its free
+ * rows is OPV_ECAPACITY and has changed NOTHING, as is a push that would take N beyond 2^63. Both return when the block has been read;
+ * there is no asynchronous push.
+ * opv_scan_pop: waits for the object's queued work, copies the oldest completed rows (at most cap_blocks, P uint64 each) and frees
+ * them; returns their count, and in *first_block (may be null) the block index of the first.
+ * opv_scan_reset: empties the carry and the ring, sets N = 0 (blocks count from 0 again) and takes a new first_sample.
+ * opv_scan_carriers (host only, plain C++): the probes are uniformly spaced, f_p = f0_hz + p x step_hz (step_hz > 0), and `row` is
+ * one row or several rows added together. floor = element P / 2 of the ascending sort of the row; W = max(1, ceil(half_width_hz /
+ * step_hz)); box[i] = the sum of row[j] over |j - i| <= W inside the row, n_i terms (128-bit integers). Probe i is a candidate
+ * when box[i] x 256 > ratio_q8 x n_i x floor (integers). Candidates are taken in descending box order, the lower index first on a tie,
+ * skipping any with |i - i'| <= 2 W of one already taken, until cap. For each one taken, over the same j in ascending order and in
+ * double: e_j = row[j] > floor ? row[j] - floor : 0, num += (double)e_j x (double)(j - i), den += (double)e_j, and centre_hz =
+ * f0_hz + ((double)i + (den > 0 ? num / den : 0.0)) x step_hz, probe = i, excess = den. Returns the count, strongest first;
+ * OPV_EINVAL for P outside 1..1024, an f0_hz that is not finite, a step that is not finite and positive, a half width that is not finite and >= 0, or a null pointer.
+ *   With a 1024-tap window the probes should lie no more than about 17 kHz apart for the centre to land inside the reference's
+ *   +/-1500 Hz search (float experiment, four MSK carriers 4 - 11 kHz off their raster in an 8.672 MS/s capture, 20 - 80 ms: worst
+ *   error 786 Hz with probes 8.5 or 16.9 kHz apart, 1.3 - 3.1 kHz with probes 33.9 kHz apart: too coarse).
+ *   A noise-free capture has floor = 0, so every probe with any power is a candidate: cap is what bounds the list. */
+typedef struct opv_scan_cfg {
+    int32_t down, up;          /* wide rate = 2 168 000 x down / up */
+    int32_t n_probes;          /* P */
+    int32_t n_window;          /* Lw */
+    int32_t hop;               /* H */
+    int32_t n_avg;             /* A: segments per block */
+    int32_t out_shift;         /* S */
+    int32_t ring_blocks;       /* rows the object holds until they are popped */
+    uint64_t first_sample;
+} opv_scan_cfg;                /* 40 bytes */
+typedef struct opv_scan_carrier {
+    double centre_hz;
+    double excess;             /* den: the power above the floor inside the box */
+    int32_t probe;             /* i */
+    int32_t reserved;          /* 0 */
+} opv_scan_carrier;            /* 24 bytes */
+typedef struct opv_scan opv_scan;
+int opv_scan_plan(const opv_scan_cfg* cfg, const double* probe_hz, const int16_t* window, uint32_t* inc_out);
+uint64_t opv_scan_blocks(const opv_scan_cfg* cfg, uint64_t n_wide_total);
+int opv_scan_create(opv_scan** out, opv_ctx* ctx, const opv_scan_cfg* cfg, const double* probe_hz, const int16_t* window);
+void opv_scan_destroy(opv_scan* scan);
+int opv_scan_push(opv_scan* scan, const int16_t* iq_wide, size_t n_wide);
+int opv_scan_push_device(opv_scan* scan, const int16_t* d_iq_wide, size_t n_wide);
+long opv_scan_pop(opv_scan* scan, uint64_t* rows, size_t cap_blocks, uint64_t* first_block);
+int opv_scan_reset(opv_scan* scan, uint64_t first_sample);
+long opv_scan_carriers(const uint64_t* row, int n_probes, double f0_hz, double step_hz, double half_width_hz, uint32_t ratio_q8,
+                       opv_scan_carrier* out, size_t cap);
 /* EOF on a stream: enables the tail processing of :1088-1113 (streaming) or the single
  * whole-capture demodulate of :1166-1173 (batch) at the next opv_process. */
 int opv_flush(opv_ctx* ctx, int stream);

@@ -10,6 +10,8 @@
 #include <memory>
 #include <vector>
 
+#include "../../include/opv_demod.h"
+
 struct opv_ctx;
 
 // What both front-door kernels are handed, by value, filled once by wb_push (opv_wideband.hip). Sample n of the object (0 = the first
@@ -68,6 +70,42 @@ int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // se
         hipError_t _e = (expr);                                           \
         if (_e != hipSuccess) return opv_int_fail(OPV_EHIP, #expr, _e);   \
     } while (0)
+// ---- the source of a push, for every object that reads a caller's block on the copy stream (opv_wideband.hip, opv_scan.hip)
+enum class OpvSrc { Host, Device };
+struct OpvStage {                 // pageable sources: the block is copied here first (grow-only)
+    int* d = nullptr;
+    size_t cap = 0;
+};
+// The block of n samples as the device sees it, in *src: a device pointer as it is; pinned host memory through its device address
+// (the kernel reads the caller's block across PCIe, once); pageable memory through the staging buffer, grown here if it is too
+// small, after a wait for the copy stream. *staged then tells the caller to enqueue the copy into stage->d in front of its launch.
+// Nothing is enqueued here, and nothing of the object's state changes.
+inline int opv_int_source(const int16_t* iq, size_t n, OpvSrc kind, int device, hipStream_t copy_stream, OpvStage* stage, const int** src,
+                          bool* staged) {
+    *staged = false;
+    if (kind == OpvSrc::Device) {
+        *src = (const int*)iq;
+        return 0;
+    }
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, iq) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer && at.device == device) {
+        *src = (const int*)at.devicePointer;
+        return 0;
+    }
+    (void)hipGetLastError();                                            // (pageable memory: "invalid value" - not an error of ours)
+    if (stage->cap < n) {
+        HIPCHK(hipStreamSynchronize(copy_stream));
+        if (stage->d) HIPCHK(hipFree(stage->d));
+        stage->d = nullptr;
+        stage->cap = 0;
+        HIPCHK(hipMalloc(&stage->d, n * 4));
+        stage->cap = n;
+    }
+    *src = stage->d;
+    *staged = true;
+    return 0;
+}
+
 // What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
 // (or used) after its context finds ctx_alive false and touches nothing of the context.
 struct OpvWbShared {

@@ -11,11 +11,13 @@ int refuse(const char** why, int code, const char* text) {
     return code;
 }
 
+}  // namespace
+
 // A plan's last step, the increment rule of a wide rate of 2 168 000 x down / up S/s: inc_out[k] = (uint32) llrint(centre_hz[k] /
 // rate x 2^32). One rule for both directions - what goes up comes down - and for the integer kinds, which have up = 1. The two
-// refusals come in the words of the plan that asks.
-int plan_increments(int32_t down, int32_t up, int32_t n_channels, const double* centre_hz, uint32_t* inc_out, const char** why,
-                    const char* not_finite, const char* out_of_range) {
+// refusals come in the words of the plan that asks. (opv_scan_rules.cpp's plan ends with it too.)
+int wb_plan_increments(int32_t down, int32_t up, int32_t n_channels, const double* centre_hz, uint32_t* inc_out, const char** why,
+                       const char* not_finite, const char* out_of_range) {
     const double fw = (double)down * 2168000.0 / (double)up;
     for (int k = 0; k < n_channels; ++k) {
         const double f = centre_hz[k];
@@ -26,8 +28,6 @@ int plan_increments(int32_t down, int32_t up, int32_t n_channels, const double* 
     }
     return OPV_OK;
 }
-
-}  // namespace
 
 extern "C" void opv_wb_lo_table(int16_t out4096[4096]) {
     if (!out4096) return;
@@ -60,15 +60,24 @@ int wb_plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps,
     if (cfg->out_shift < 0 || cfg->out_shift > 40) return refuse(why, OPV_EINVAL, "opv_wb: out_shift outside 0..40");
     if (!centre_hz || !taps || !inc_out) return refuse(why, OPV_EINVAL, "opv_wb: null pointer");
     if (!wb_phase_gain_within(taps, cfg->n_taps, 1, 1ll << 21)) return refuse(why, OPV_EINVAL, "opv_wb: sum of |taps| exceeds 2^21");
-    return plan_increments(cfg->decim, 1, cfg->n_channels, centre_hz, inc_out, why, "opv_wb: non-finite centre frequency",
-                           "opv_wb: centre frequency out of range");
+    return wb_plan_increments(cfg->decim, 1, cfg->n_channels, centre_hz, inc_out, why, "opv_wb: non-finite centre frequency",
+                              "opv_wb: centre frequency out of range");
+}
+
+int wbr_ratio_fault(int32_t down, int32_t up) {
+    if (up < 1 || up > 1024) return 1;
+    if (down < up || (int64_t)down > 32 * (int64_t)up) return 2;
+    if (std::gcd(down, up) != 1) return 3;
+    return 0;
 }
 
 const char* wbr_cfg_refusal(const opv_wbr_cfg* cfg) {
     if (!cfg) return "opv_wbr: null configuration";
-    if (cfg->up < 1 || cfg->up > 1024) return "opv_wbr: up outside 1..1024";
-    if (cfg->down < cfg->up || (int64_t)cfg->down > 32 * (int64_t)cfg->up) return "opv_wbr: down outside up..32 up";
-    if (std::gcd(cfg->down, cfg->up) != 1) return "opv_wbr: down and up share a factor";
+    switch (wbr_ratio_fault(cfg->down, cfg->up)) {
+        case 1: return "opv_wbr: up outside 1..1024";
+        case 2: return "opv_wbr: down outside up..32 up";
+        case 3: return "opv_wbr: down and up share a factor";
+    }
     if (cfg->n_taps < 1 || wb_taps_per_phase(cfg->n_taps, cfg->up) > 1024) return "opv_wbr: n_taps outside 1..1024 per phase";
     if (cfg->n_channels < 1 || cfg->n_channels > 256) return "opv_wbr: n_channels outside 1..256";
     if (cfg->out_shift < 0 || cfg->out_shift > 40) return "opv_wbr: out_shift outside 0..40";
@@ -80,8 +89,8 @@ int wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* tap
     if (const char* bad = wbr_cfg_refusal(cfg)) return refuse(why, OPV_EINVAL, bad);
     if (!centre_hz || !taps || !inc_out) return refuse(why, OPV_EINVAL, "opv_wbr: null pointer");
     if (!wb_phase_gain_within(taps, cfg->n_taps, cfg->up, 1ll << 21)) return refuse(why, OPV_EINVAL, "opv_wbr: sum of |taps| of one phase exceeds 2^21");
-    return plan_increments(cfg->down, cfg->up, cfg->n_channels, centre_hz, inc_out, why, "opv_wbr: non-finite centre frequency",
-                           "opv_wbr: centre frequency out of range");
+    return wb_plan_increments(cfg->down, cfg->up, cfg->n_channels, centre_hz, inc_out, why, "opv_wbr: non-finite centre frequency",
+                              "opv_wbr: centre frequency out of range");
 }
 
 uint64_t wbr_outputs(uint32_t down, uint32_t up, uint64_t n_wide_total) {
@@ -107,8 +116,8 @@ int wbtx_plan(const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* t
     if (cfg->out_shift < 0 || cfg->out_shift > 40) return refuse(why, OPV_EINVAL, "opv_wbtx: out_shift outside 0..40");
     if (!centre_hz || !taps || !inc_out) return refuse(why, OPV_EINVAL, "opv_wbtx: null pointer");
     if (!wb_phase_gain_within(taps, cfg->n_taps, cfg->interp, 65535)) return refuse(why, OPV_EINVAL, "opv_wbtx: sum of |taps| of one phase exceeds 65535");
-    return plan_increments(cfg->interp, 1, cfg->n_channels, centre_hz, inc_out, why, "opv_wbtx: non-finite centre frequency",
-                           "opv_wbtx: centre frequency out of range");
+    return wb_plan_increments(cfg->interp, 1, cfg->n_channels, centre_hz, inc_out, why, "opv_wbtx: non-finite centre frequency",
+                              "opv_wbtx: centre frequency out of range");
 }
 
 const char* wbtxr_cfg_refusal(const opv_wbtxr_cfg* cfg) {
@@ -128,8 +137,8 @@ int wbtxr_plan(const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t*
     if (const char* bad = wbtxr_cfg_refusal(cfg)) return refuse(why, OPV_EINVAL, bad);
     if (!centre_hz || !taps || !inc_out) return refuse(why, OPV_EINVAL, "opv_wbtxr: null pointer");
     if (!wb_phase_gain_within(taps, cfg->n_taps, cfg->down, 65535)) return refuse(why, OPV_EINVAL, "opv_wbtxr: sum of |taps| of one phase exceeds 65535");
-    return plan_increments(cfg->down, cfg->up, cfg->n_channels, centre_hz, inc_out, why, "opv_wbtxr: non-finite centre frequency",
-                           "opv_wbtxr: centre frequency out of range");
+    return wb_plan_increments(cfg->down, cfg->up, cfg->n_channels, centre_hz, inc_out, why, "opv_wbtxr: non-finite centre frequency",
+                              "opv_wbtxr: centre frequency out of range");
 }
 
 uint64_t wbtxr_outputs(uint32_t down, uint32_t up, uint64_t n_in_total) {

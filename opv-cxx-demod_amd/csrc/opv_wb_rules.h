@@ -24,9 +24,15 @@ void wb_phase_table(const int16_t* taps, int64_t n_taps, uint32_t stride, uint32
 // the taps per phase of a rational kind, J = ceil(L / stride), and the row length of its table: J rounded up to a multiple of 4
 inline uint32_t wb_taps_per_phase(int32_t n_taps, int32_t stride) { return (uint32_t)(((int64_t)n_taps + stride - 1) / stride); }
 inline uint32_t wb_row_len(uint32_t J) { return (J + 3u) & ~3u; }
+// A plan's last step: inc_out[k] = (uint32) llrint(centre_hz[k] / (2 168 000 x down / up) x 2^32), the refusals in the asking plan's words
+int wb_plan_increments(int32_t down, int32_t up, int32_t n_channels, const double* centre_hz, uint32_t* inc_out, const char** why,
+                       const char* not_finite, const char* out_of_range);
 
 // ---- the front doors
 int wb_plan(const opv_wb_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out, const char** why);
+// the limits of a wide rate's pair (the rational door's, and the scan's): 0 if 1 <= up <= 1024, up <= down <= 32 up and the two share no
+// factor; else which of the three fails (1: up, 2: down, 3: a common factor)
+int wbr_ratio_fault(int32_t down, int32_t up);
 // nullptr if cfg lies inside the limits, else why not (every refusal is OPV_EINVAL)
 const char* wbr_cfg_refusal(const opv_wbr_cfg* cfg);
 int wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out, const char** why);

@@ -43,8 +43,7 @@ struct opv_wb {
     int16_t* d_lo = nullptr;
     void* d_taps = nullptr;              // Integer: h[L] widened to int32; Rational: the phase-major int16 table
     uint32_t* d_inc = nullptr;
-    int* d_stage = nullptr;              // pageable sources: the block is copied here first (grow-only)
-    size_t stage_cap = 0;
+    OpvStage stage;                      // pageable sources: the block is copied here first (grow-only)
     int** h_tab = nullptr;               // pinned: kTabSlots x K destination pointers, read in place by the kernel
     hipEvent_t tab_ev[kTabSlots] = {};
     unsigned pushes = 0;
@@ -126,7 +125,7 @@ extern "C" void opv_wb_destroy(opv_wb* w) {
     for (auto& e : w->tab_ev)
         if (e) (void)hipEventDestroy(e);
     if (w->h_tab) (void)hipHostFree(w->h_tab);
-    void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->d_stage};
+    void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->stage.d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete w;
@@ -183,7 +182,7 @@ extern "C" int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_
 
 namespace {
 
-enum class Src { Host, Device };
+using Src = OpvSrc;
 
 int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null object");
@@ -209,29 +208,10 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
         r1 = (w->n_total + n_new + D - 1) / D;
     }
     const uint32_t n_out = (uint32_t)(r1 - r0);
-    // ---- the source as the device sees it
+    // ---- the source as the device sees it (a staging buffer grown at most so far: nothing enqueued, nothing of the object's state changed)
     const int* src = nullptr;
     bool stage = false;
-    if (kind == Src::Device) {
-        src = (const int*)iq;
-    } else {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, iq) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer && at.device == w->door.device) {
-            src = (const int*)at.devicePointer;                         // pinned: the kernel reads the caller's block across PCIe, once
-        } else {
-            (void)hipGetLastError();                                    // (pageable memory: "invalid value" - not an error of ours)
-            if (w->stage_cap < n_new) {
-                HIPCHK(hipStreamSynchronize(w->door.copy_stream));
-                if (w->d_stage) HIPCHK(hipFree(w->d_stage));
-                w->d_stage = nullptr;
-                w->stage_cap = 0;
-                HIPCHK(hipMalloc(&w->d_stage, n_new * 4));
-                w->stage_cap = n_new;
-            }
-            src = w->d_stage;                                           // (grown at most so far: nothing enqueued, nothing of the object's state changed)
-            stage = true;
-        }
-    }
+    if (int r = opv_int_source(iq, n_new, kind, w->door.device, w->door.copy_stream, &w->stage, &src, &stage)) return r;
     // ---- this push's destination table: a slot of the pinned ring, free once the launch that read it last has finished
     const unsigned slot = w->pushes % kTabSlots;
     if (w->tab_ev[slot]) HIPCHK(hipEventSynchronize(w->tab_ev[slot]));
@@ -240,7 +220,7 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     std::vector<uint32_t> counts(K, n_out);
     std::vector<int*> dst(K);
     if (int r = opv_int_push_reserve(w->ctx, (int)K, w->streams.data(), counts.data(), dst.data())) return r;
-    if (stage) HIPCHK(hipMemcpyAsync(w->d_stage, iq, n_new * 4, hipMemcpyHostToDevice, w->door.copy_stream));
+    if (stage) HIPCHK(hipMemcpyAsync(w->stage.d, iq, n_new * 4, hipMemcpyHostToDevice, w->door.copy_stream));
     int** tab = w->h_tab + (size_t)slot * K;
     std::memcpy(tab, dst.data(), (size_t)K * sizeof(int*));
     void* d_tab = nullptr;

@@ -47,6 +47,8 @@ EXPORTS = [
     "opv_wbtxr_plan", "opv_wbtxr_outputs", "opv_wbtx_create_rational",
     "opv_div_create", "opv_div_destroy", "opv_div_set_weights", "opv_div_round", "opv_div_pop_frames", "opv_div_get_state",
     "opv_div_tap_payload", "opv_div_match", "opv_div_earliest",
+    "opv_scan_plan", "opv_scan_blocks", "opv_scan_create", "opv_scan_destroy", "opv_scan_push", "opv_scan_push_device", "opv_scan_pop",
+    "opv_scan_reset", "opv_scan_carriers",
 ]
 
 
@@ -78,6 +80,15 @@ class WbtxCfg(C.Structure):
 class WbtxrCfg(C.Structure):
     _fields_ = [("down", C.c_int32), ("up", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("reserved", C.c_int32), ("first_sample", C.c_uint64)]
+
+
+class ScanCfg(C.Structure):
+    _fields_ = [("down", C.c_int32), ("up", C.c_int32), ("n_probes", C.c_int32), ("n_window", C.c_int32), ("hop", C.c_int32),
+                ("n_avg", C.c_int32), ("out_shift", C.c_int32), ("ring_blocks", C.c_int32), ("first_sample", C.c_uint64)]
+
+
+class ScanCarrier(C.Structure):
+    _fields_ = [("centre_hz", C.c_double), ("excess", C.c_double), ("probe", C.c_int32), ("reserved", C.c_int32)]
 
 
 class TxbState(C.Structure):
@@ -312,6 +323,19 @@ def lib():
         L.opv_div_match.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.opv_div_earliest.restype = C.c_uint64
         L.opv_div_earliest.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, C.c_int32]
+        L.opv_scan_plan.argtypes = [C.POINTER(ScanCfg), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_scan_blocks.restype = C.c_uint64
+        L.opv_scan_blocks.argtypes = [C.POINTER(ScanCfg), C.c_uint64]
+        L.opv_scan_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(ScanCfg), C.c_void_p, C.c_void_p]
+        L.opv_scan_destroy.restype = None
+        L.opv_scan_destroy.argtypes = [C.c_void_p]
+        L.opv_scan_push.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_scan_push_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_scan_pop.restype = C.c_long
+        L.opv_scan_pop.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        L.opv_scan_reset.argtypes = [C.c_void_p, C.c_uint64]
+        L.opv_scan_carriers.restype = C.c_long
+        L.opv_scan_carriers.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -703,6 +727,76 @@ class Wideband:
             lib().opv_wb_destroy(self.h)                                     # (waits for the copy stream: nothing reads the blocks any more)
             self.h = C.c_void_p()
         self._inflight = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---------------------------------------------------------------- wideband scan (opv_scan_*)
+def _scan_cfg(down, up, probe_hz, window, hop, n_avg, out_shift, ring_blocks, first_sample):
+    probes = np.ascontiguousarray(probe_hz, np.float64).reshape(-1)
+    window = np.ascontiguousarray(window, np.int16).reshape(-1)
+    cfg = ScanCfg(down=int(down), up=int(up), n_probes=probes.size, n_window=window.size, hop=int(hop), n_avg=int(n_avg),
+                  out_shift=int(out_shift), ring_blocks=int(ring_blocks), first_sample=int(first_sample))
+    return cfg, probes, window
+
+
+def scan_plan(down, up, probe_hz, window, hop, n_avg, out_shift, ring_blocks=1, first_sample=0):
+    """opv_scan_plan: validates a scan's plan and returns its P phase increments (uint32): wbr_plan's for the same (down, up,
+    frequencies); host only, needs no device"""
+    return _wb_plan(lib().opv_scan_plan, *_scan_cfg(down, up, probe_hz, window, hop, n_avg, out_shift, ring_blocks, first_sample))
+
+
+def scan_blocks(n_window, hop, n_avg, n_wide_total, down=1, up=1):
+    """opv_scan_blocks: blocks completed after n_wide_total wide samples, ((N - Lw) / H + 1) / A (0 while N < Lw)"""
+    cfg = ScanCfg(int(down), int(up), 1, int(n_window), int(hop), int(n_avg), 0, 1, 0)
+    return int(lib().opv_scan_blocks(C.byref(cfg), int(n_wide_total)))
+
+
+def scan_carriers(row, f0_hz, step_hz, half_width_hz, ratio_q8, cap):
+    """opv_scan_carriers: the carriers in one row of probe powers (or several rows added), probes at f0_hz + p step_hz; returns a
+    list of (centre_hz, probe, excess), strongest first; host only"""
+    row = np.ascontiguousarray(row, np.uint64).reshape(-1)
+    out = (ScanCarrier * max(int(cap), 1))()
+    n = _chk(lib().opv_scan_carriers(row.ctypes.data, row.size, float(f0_hz), float(step_hz), float(half_width_hz), int(ratio_q8), out, int(cap)))
+    return [(out[i].centre_hz, out[i].probe, out[i].excess) for i in range(n)]
+
+
+class Scan:
+    """A bank of probes on the device of `demod`: the power of one wide capture at probe_hz[p], per block of n_avg windowed segments
+    (opv_scan_*, include/opv_demod.h). Close it before its Demod."""
+
+    def __init__(self, demod, down, up, probe_hz, window, hop, n_avg, out_shift, ring_blocks=16, first_sample=0):
+        self.demod = demod
+        self.cfg, probes, window = _scan_cfg(down, up, probe_hz, window, hop, n_avg, out_shift, ring_blocks, first_sample)
+        self.h = C.c_void_p()
+        _chk(lib().opv_scan_create(C.byref(self.h), demod.h, C.byref(self.cfg), probes.ctypes.data, window.ctypes.data))
+
+    def push(self, iq_wide):
+        iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
+        _chk(lib().opv_scan_push(self.h, iq.ctypes.data, iq.size // 2))
+
+    def push_device(self, dev_ptr, n_wide):
+        _chk(lib().opv_scan_push_device(self.h, C.c_void_p(dev_ptr), int(n_wide)))
+
+    def pop(self, cap=None):
+        """opv_scan_pop: (rows uint64 [n][P], index of the first block); at most `cap` blocks (default: the ring)"""
+        cap = self.cfg.ring_blocks if cap is None else int(cap)
+        rows = np.zeros((cap, self.cfg.n_probes), np.uint64)
+        first = C.c_uint64()
+        n = _chk(lib().opv_scan_pop(self.h, rows.ctypes.data, cap, C.byref(first)))
+        return rows[:n], int(first.value)
+
+    def reset(self, first_sample=0):
+        _chk(lib().opv_scan_reset(self.h, int(first_sample)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().opv_scan_destroy(self.h)
+            self.h = C.c_void_p()
 
     def __del__(self):
         try:

@@ -79,11 +79,11 @@ def seq_scale(payload):
 
 
 def branch_records(oracle, soft):
-    """oracle.track of one branch log -> dict(sym, quality, sync_ok, fscale, payloads, metrics, frames)"""
+    """oracle.track of one branch log -> dict(sym, quality, sync_ok, fscale, payloads, metrics, frames, final_state)"""
     t = oracle.track(soft)
     return dict(sym=[int(v) - (CODED - 1) for v in t["frame_sym"]], quality=[float(v) for v in t["quality"]],
                 sync_ok=[int(v) for v in t["sync_ok"]], fscale=[seq_scale(p) for p in t["payloads"]], payloads=t["payloads"],
-                metrics=t["metrics"], frames=t["frames"])
+                metrics=t["metrics"], frames=t["frames"], final_state=t["final_state"])
 
 
 def factor(w, normalise, fscale):

@@ -1,7 +1,9 @@
 """CPU-only: receive diversity's matching rule (opv_div_match, the host entry of csrc/opv_div_rules.h) held to the numpy model
 tests/diversity_model.py; the struct layouts against gcc; the refusals that need no device; and - with the oracle alone - that
 the made branch logs of the GPU tests (tests/diversity_inputs.py) are not vacuous: a group frame that every member branch decodes
-wrongly alone and the combination decodes to the transmitted frame, and a frame with a strict subset of the branches."""
+wrongly alone and the combination decodes to the transmitted frame, and a frame with a strict subset of the branches; and that
+the logs of tests/test_gpu_diversity_limits.py reach the edges they are named after (eight branches that need each other and show
+the order of the sum, windows of 0 and 64 met and missed by one symbol, unequal losses on all eight lanes)."""
 import re
 
 import numpy as np
@@ -213,3 +215,60 @@ def test_iq_noise_level_of_the_gpu_test_shows_the_gain(oracle):
     assert all(min(s) > 0 for s in single) and all(c <= min(s) for c, s in zip(comb, single)), (single, comb)
     assert any(c < min(s) for c, s in zip(comb, single))
     assert all(np.array_equal(f["frame"], tx[k]) for k, f in enumerate(fr))
+
+
+# ---- the limits: what tests/test_gpu_diversity_limits.py runs on the device is not vacuous --------------------------------------
+def test_eight_scattered_branches_need_each_other_and_the_order_of_the_sum_shows(oracle):
+    """the group of eight (diversity_inputs.eight_groups): with unit weights every branch alone decodes frames 1-4 wrongly and the
+    combination decodes all six; with EIGHT_WEIGHTS the sum in DESCENDING branch order - and the sum in stream order - differs in
+    bits of the payload of every frame that carries a signal"""
+    (g8, g5), _ = DI.eight_groups(oracle)
+    recs = [DM.branch_records(oracle, b.soft) for b in g8]
+    tx = oracle.bert_frames(DI.N_FRAMES)
+    fr = DM.group_frames(oracle, recs, 8, want_link=False)
+    assert [f["members"] for f in fr] == [0xFF] * 10 and [f["metric"] >= 0 for f in fr] == [True] * 6 + [False] * 4
+    for k in range(DI.N_FRAMES):
+        assert np.array_equal(fr[k]["frame"], tx[k]), k
+        if k in DI.EIGHT_LOUD:
+            assert all(not np.array_equal(recs[b]["frames"][k], tx[k]) for b in range(8)), k
+    w = DI.EIGHT_WEIGHTS
+    for k, f in enumerate(DM.group_frames(oracle, recs, 8, weights=w, want_link=False)[:DI.N_FRAMES]):
+        for order in (sorted(f["index"], reverse=True), sorted(f["index"], key=lambda b: DI.EIGHT_STREAMS[b])):
+            other = DM.combine([recs[b]["payloads"][f["index"][b]] for b in order], [w[b] for b in order])
+            assert np.sum(other != f["payload"]) > 100, (k, order)
+    assert sorted(DI.EIGHT_STREAMS) != DI.EIGHT_STREAMS and sorted(DI.FIVE_STREAMS) != DI.FIVE_STREAMS
+    assert not set(DI.EIGHT_STREAMS) & set(DI.FIVE_STREAMS) and DI.NEIGHBOUR not in DI.EIGHT_STREAMS + DI.FIVE_STREAMS
+    # the group of five: a strict subset while branch 1 hunts, another once branch 2 has ended
+    f5 = DM.group_frames(oracle, [DM.branch_records(oracle, b.soft) for b in g5], 8, want_link=False)
+    assert [f["members"] for f in f5] == [0x1D] * 2 + [0x1F] * 6 + [0x1B] * 2
+
+
+def window_masks(W, shifts):
+    inside = abs(shifts[0] - shifts[1]) <= W
+    return [3] * 10 if inside else ([1, 2] if shifts[0] < shifts[1] else [2, 1]) * 10
+
+
+@pytest.mark.parametrize("W,shifts", DI.WINDOW_CASES)
+def test_window_0_and_64_logs_sit_on_both_sides_of_the_window(oracle, amd, W, shifts):
+    recs = [DM.branch_records(oracle, b.soft) for b in DI.window_pair(oracle, shifts)]
+    fr = both(amd, [r["sym"] for r in recs], W, tag=(W, shifts))
+    assert [f["members"] for f in fr] == window_masks(W, shifts)
+    assert all(f["syms"][1] - f["syms"][0] == shifts[1] - shifts[0] for f in fr if f["members"] == 3)
+
+
+def test_eight_branches_that_ran_ahead_lose_unequally(oracle):
+    """diversity_inputs.ahead_group in a context of 8 frame slots and 16 384 soft symbols: the per-branch record losses differ,
+    lanes 4..7 contribute, and one emitted frame has members that are summed next to members whose payload has left its ring"""
+    from diversity_runs import ahead_model
+    g = DI.ahead_group(oracle)
+    recs = [DM.branch_records(oracle, b.soft) for b in g]
+    logs = [b.soft for b in g]
+    alone = [ahead_model([r], [log], 1, 8, 16384)[0].records_lost for r, log in zip(recs, logs)]
+    assert alone == [8, 8, 6, 8, 8, 5, 7, 8] and len(set(alone[4:])) > 1
+    m, per = ahead_model(recs, logs, 3, 8, 16384)
+    assert m.records_lost == sum(alone) == 58 and sum(alone[:4]) != m.records_lost
+    assert [(len(out), lost, gone, stalled) for out, lost, gone, stalled in per] == [(8, 58, 17, 1), (3, 58, 17, 0), (0, 58, 17, 0)]
+    assert len(set(len(log) for log in logs)) == 8
+    mixed = [f for f in m.frames if f["soft_gone"] and f["members"] & ~f["soft_gone"]]
+    assert [(f["members"], f["soft_gone"]) for f in mixed] == [(0xFF, 0x92)]
+    assert any(f["members"] == f["soft_gone"] for f in m.frames) and any(f["members"] not in (0, 0xFF) and not f["soft_gone"] for f in m.frames)

@@ -10,103 +10,12 @@ import pytest
 import diversity_inputs as DI
 import diversity_model as DM
 import soft_log_inputs as S
+from diversity_runs import BIG, CODED, FSYMS, MID, SMALL, Run, check_group, same
 from fixtures import amd  # noqa: F401
-from link_model import check_record
 from stream_runs import code_of
 
 pytestmark = pytest.mark.gpu
 EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-SMALL = 32                                     # max_samples: cap_soft 4096, cap_frames 4
-MID = 330000                                   # cap_soft 16384, cap_frames 8
-BIG = 1000000                                  # cap_soft 32768, cap_frames 16: a whole branch log in one push
-CODED, FSYMS = 2144, 2168
-
-
-def same(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.shape == b.shape and (np.array_equal(a, b, equal_nan=True) if a.dtype.kind == "f" else np.array_equal(a, b))
-
-
-class Run:
-    """one context, one diversity object: pushes branch logs in pieces, a process + round after each, and keeps what came out"""
-
-    def __init__(self, amd, groups, max_samples, window=8, normalise=False):
-        self.amd = amd
-        self.logs = [b.soft for g in groups for b in g]
-        ids, self.streams = iter(range(len(self.logs))), []
-        for g in groups:
-            self.streams.append([next(ids) for _ in g])
-        self.d = amd.Demod(len(self.logs), max_samples=max_samples, streaming=True)
-        self.div = amd.Diversity(self.d, self.streams, window=window, normalise=normalise)
-        G = len(groups)
-        self.frames, self.meta, self.link = [[] for _ in range(G)], [[] for _ in range(G)], [[] for _ in range(G)]
-        self.payloads, self.tapped, self.pops = [[] for _ in range(G)], [0] * G, [[] for _ in range(G)]
-        self.own = [([], []) for _ in self.logs]            # the branches' own pops
-        self.at = 0
-
-    def close(self):
-        self.div.close()
-        self.d.close()
-
-    def pop_branches(self):
-        for s in range(len(self.logs)):
-            f, m = self.d.pop_frames(s)
-            self.own[s][0].append(f)
-            self.own[s][1].append(m)
-
-    def collect(self, pop=True):
-        for g in range(len(self.streams)):
-            st = self.div.state(g)
-            for f in range(self.tapped[g], st.frames_emitted):
-                self.payloads[g].append(self.div.tap_payload(g, f))
-            self.tapped[g] = st.frames_emitted
-            if pop:
-                f, m, l = self.div.pop_frames(g, link=True)
-                self.frames[g].append(f)
-                self.meta[g].append(m)
-                self.link[g].append(l)
-                self.pops[g].append(len(f))
-
-    def step(self, upto, rounds=True, pop=True, pop_branches=True):
-        """symbols [at, upto) of every log, one process, one diversity round"""
-        for s, log in enumerate(self.logs):
-            if log[self.at:upto].size:
-                self.d.push_soft(s, log[self.at:upto])
-        self.at = upto
-        self.d.process()
-        if pop_branches:
-            self.pop_branches()
-        if rounds:
-            self.div.round()
-            self.collect(pop)
-
-    def feed(self, piece, **kw):
-        n = max(len(log) for log in self.logs)
-        while self.at < n:
-            self.step(min(n, self.at + piece), **kw)
-
-    def result(self, g):
-        return (np.concatenate(self.frames[g]), np.concatenate(self.meta[g]), np.concatenate(self.link[g]), self.payloads[g])
-
-
-def check_group(oracle, got, exp, tag, moments=True):
-    """what a group handed out == the model's frames `exp` (diversity_model.finish): payloads of EVERY emitted frame, the rest for
-    the frames the decoder did not drop"""
-    fr, meta, link, payloads = got
-    assert len(payloads) == len(exp), (tag, len(payloads), len(exp))
-    for i, (p, e) in enumerate(zip(payloads, exp)):
-        assert same(p, e["payload"]), (tag, i, "payload")
-    kept = [e for e in exp if e["metric"] >= 0]
-    assert len(fr) == len(kept), (tag, len(fr), len(kept))
-    for i, e in enumerate(kept):
-        m = meta[i]
-        assert int(m["members"]) == e["members"] and int(m["summed"]) == e["summed"], (tag, i, m, e["members"], e["summed"])
-        assert [int(v) for v in m["payload_symbol"]] == e["syms"], (tag, i)
-        assert int(m["sync_ok"]) == e["sync_ok"] and same(m["sync_quality"], np.float64(e["sync_quality"])), (tag, i, m)
-        assert int(m["viterbi_metric"]) == e["metric"] and same(fr[i], e["frame"]), (tag, i, "decode")
-        if "link" in e:
-            check_record(link[i], e["link"], (tag, i))
-    return kept
 
 
 @pytest.fixture(scope="module")
@@ -364,7 +273,7 @@ def test_reset_of_a_branch_mid_run(amd, oracle, pair_group):
 
 
 # ------------------------------------------------------------------------------------------------ 5. real IQ
-@pytest.mark.parametrize("frontend", [0, 4])
+@pytest.mark.parametrize("frontend", [0, 4, 16])
 def test_two_noisy_receptions_of_one_transmission(amd, oracle, frontend):
     """The same six frames through the device channel with two noise seeds, at a level where a single branch shows channel-bit
     errors in every frame (tests/oracle_lib.channel_model + the oracle on the CPU: 10 .. 26 per branch frame, 0 .. 2 combined).

@@ -23,14 +23,12 @@ product sees a sample. Two cases deviate from a 40 000-sample schedule because w
 payload_2p32 feeds the rest in 300 000-sample pieces (three frames decoded in one round: the decoder pairs two of them in a wave),
 and hunting_window_2p32 is cut at 100 000 samples of the capture whose first sync word lies at symbol 2177 - a stream cut at
 50 000 samples has produced no symbol yet, which the shift refuses (test_refusals)."""
-import ctypes as C
 import struct
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
 
+from far_probe import probe, shifted_blob  # noqa: F401
 from fixtures import amd  # noqa: F401
 from link_model import CODED, check_record, link_model
 from oracle_lib import accidents, impair
@@ -39,8 +37,6 @@ from stream_runs import (CHUNK, HUNTING, LOCKED, drain, feed, held_to_the_oracle
                          tracker_at)
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "opv-cxx-demod_amd" / "csrc"
 EINVAL = -1
 SLOT = 5
 NEIGHBOURS = (("shifted", 4), ("noisy", 6))
@@ -48,24 +44,6 @@ CUT = 2 * CHUNK + 20000
 # (id, int16 ring forced, opv_set_frontend, the kernel a round must have launched)
 DESTS = [("rb_f64", False, 1, "k_msk_frontend_rb"), ("rb_i16", True, 1, "k_msk_frontend_rb"), ("x4", False, 4, "k_msk_frontend_x4_wg4"),
          ("x16", False, 16, "k_msk_frontend_x16_wg4")]
-
-
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    so = tmp_path_factory.mktemp("far") / "libprobe.so"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-Wall", "-ffp-contract=off", "-shared", "-I", str(CSRC), "-o", str(so),
-                    str(ROOT / "tests" / "stream_rules_probe.cpp"), str(CSRC / "opv_stream_rules.cpp")], check=True)
-    L = C.CDLL(str(so))
-    L.probe_blob_shift.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64]
-    L.probe_offset.restype = C.c_long
-    L.probe_offset.argtypes = [C.c_char_p]
-    return L
-
-
-def shifted_blob(probe, blob, d_sym, d_samp):
-    buf = (C.c_char * len(blob)).from_buffer_copy(bytes(blob))
-    rc = probe.probe_blob_shift(buf, len(blob), d_sym, d_samp)
-    return rc, bytes(buf.raw)
 
 
 @pytest.fixture(scope="module")

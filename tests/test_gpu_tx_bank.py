@@ -8,47 +8,10 @@ import pytest
 import tx_bank_model as M
 from fixtures_built import amd  # noqa: F401
 from stream_runs import code_raised_by
+from tx_bank_runs import CANARY, ECAPACITY, EINVAL, ESTATE, FS, GAP, Lanes, stream_frames
+from tx_bank_runs import dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-FS = M.FRAME_SAMPLES                     # samples per frame; 2 int16 each
-CANARY = 0x5A5B                          # int16 fill of everything a round must not touch
-GAP = 32                                 # int16 per 64-byte canary
-EINVAL, ECAPACITY, ESTATE = -1, -4, -6
-
-
-@pytest.fixture(scope="module")
-def dev():
-    import torch
-    return torch.device("cuda", 0)
-
-
-def stream_frames(amd, k, n, first=0):
-    """n BERT frames of stream k: its own callsign and token"""
-    return amd.bert_frames(n, callsign=f"TXB{k}-{k}", token=0x10F0F0 + 0x010203 * k, first=first)
-
-
-class Lanes:
-    """one device buffer of `lanes` outputs of `frames` frames each, back to back with a 64-byte canary in front of, between
-    and behind them; everything starts as canary"""
-
-    def __init__(self, dev, lanes, frames):
-        import torch
-        self.per = 2 * FS * frames
-        self.buf = torch.full(((self.per + GAP) * lanes + GAP,), CANARY, dtype=torch.int16, device=dev)
-        assert self.buf.data_ptr() % 64 == 0
-
-    def ptr(self, lane, frame=0):
-        return self.buf.data_ptr() + 2 * (GAP + lane * (self.per + GAP) + 2 * FS * frame)
-
-    def lane(self, lane):
-        a = GAP + lane * (self.per + GAP)
-        return self.buf[a:a + self.per].cpu().numpy()
-
-    def canaries_intact(self):
-        x = self.buf.cpu().numpy()
-        step = self.per + GAP
-        return all((x[a:a + GAP] == CANARY).all() for a in range(0, x.size, step))
 
 
 def test_any_split_into_rounds_equals_one_call(amd, dev):

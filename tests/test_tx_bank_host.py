@@ -1,7 +1,8 @@
 """CPU-only: the host half of the transmit bank (include/opv_demod.h, opv_txb_*; csrc/opv_txb_rules.cpp) - what a round
 refuses and the geometry of its launches (opv_txb_plan_round), the tests' own model of the carried sign parity pinned to the
-host modulator (tests/tx_bank_model.py; tests/test_gpu_tx_bank.py relies on it), and the host's evaluation of one entry of the
-device's list of ambiguous samples (opv_tap_txb_patch) against the host modulator's sample at that position."""
+host modulator (tests/tx_bank_model.py; tests/test_gpu_tx_bank.py relies on it), the model's samples of a modulator that
+stands anywhere in its run (tests/test_gpu_tx_bank_limits.py relies on them) pinned to the host modulator and to the patch tap,
+and the host's evaluation of one entry of the device's list of ambiguous samples (opv_tap_txb_patch) against the host modulator's sample at that position."""
 import ctypes as C
 import re
 
@@ -10,6 +11,7 @@ import pytest
 
 import tx_bank_model as M
 from fixtures_built import amd  # noqa: F401
+from tx_bank_runs import drawn_frames, stream_frames
 
 EINVAL, ECAPACITY = -1, -4
 FRAME_BYTES_OUT = M.FRAME_SAMPLES * 4
@@ -129,6 +131,64 @@ def test_sign_parity_model_is_the_host_modulators(amd, callsign, token):
     want = np.sign(codes)[:, None] * np.stack([np.sin(p), np.cos(p)], axis=1) * 16383.0
     assert np.all(np.abs(first[1:] - want[1:]) <= 1.0 + 1e-6)                                # (truncation, flat tops: within one count)
     assert set(np.unique(codes[1:]).tolist()) == {-2, -1, 1, 2}
+
+
+def test_samples_model_is_the_host_modulators(amd):
+    """M.samples - the model's samples of a modulator that stands anywhere - against the host modulator: a run from symbol 0
+    (silent symbol included), and frames 2..3 of a 4-frame run from the position and the sign parity the first two leave."""
+    frames = amd.bert_frames(4, callsign="KB5MU", token=0x123456)
+    host = amd.modulate(frames)[:2 * 4 * M.FRAME_SAMPLES]
+    first = M.samples(amd, frames[:3])
+    assert first.dtype == np.int16 and first.size == 2 * 3 * M.FRAME_SAMPLES
+    assert np.array_equal(first, amd.modulate(frames[:3])[:2 * 3 * M.FRAME_SAMPLES])
+    assert not first[:2 * M.SPS].any() and first[2 * M.SPS:4 * M.SPS].any()
+    assert np.array_equal(M.samples(amd, frames[2:4], 2 * M.FSYMS, M.sign_parity(amd, frames[:2])), host[2 * 2 * M.FRAME_SAMPLES:])
+    assert M.samples(amd, frames[:0], 5).size == 0
+    # the parity matters: the other one is the same signal with the other sign
+    flipped = M.samples(amd, frames[2:3], 2 * M.FSYMS, 1 - M.sign_parity(amd, frames[:2]))
+    assert np.array_equal(flipped, -host[2 * 2 * M.FRAME_SAMPLES:2 * 3 * M.FRAME_SAMPLES])
+
+
+def test_a_frames_parity_is_its_first_bytes(amd):
+    """Why tests/test_gpu_tx_bank_limits.py draws its frames: a frame's on-air parity is a function of the low six bits of its
+    first byte alone, in a BERT frame a byte of the callsign - every frame of one tx_bank_runs.stream_frames stream has the same
+    parity. Drawn frames have both."""
+    for k in (0, 7, 9, 10, 30):
+        assert len(set(M.frame_parities(amd, stream_frames(amd, k, 6)).tolist())) == 1, k
+    fr = drawn_frames(0, 256)
+    par = M.frame_parities(amd, fr)
+    assert 64 < par.sum() < 192
+    other = fr.copy()
+    other[:, 1:] = drawn_frames(1, 256)[:, 1:]
+    other[:, 0] ^= 0xC0
+    assert np.array_equal(M.frame_parities(amd, other), par)
+    by_byte = {}
+    for b, p in zip((fr[:, 0] & 63).tolist(), par.tolist()):
+        by_byte.setdefault(b, set()).add(p)
+    assert all(len(v) == 1 for v in by_byte.values()) and len(by_byte) > 50
+
+
+# first symbol of a frame's worth of samples far into a run: inside the flat-top bit zone, either side of the end of the
+# build-time checkpoint table (4096 frames), and an odd position that is no frame start (b_n and the phases follow the symbol)
+FAR_STARTS = [1600 * M.FSYMS, 4095 * M.FSYMS, 4097 * M.FSYMS, 777 * M.FSYMS + 1001]
+
+
+@pytest.mark.parametrize("first_symbol", FAR_STARTS)
+def test_samples_model_far_positions_are_the_patch_taps(amd, first_symbol):
+    """Far into a run the host modulator is no cheap yardstick (its cost grows with the position); opv_tap_txb_patch is, one
+    sample at a time, and test_patch_tap_is_the_host_modulators_sample holds it to the host modulator. 200 drawn
+    (symbol, sample) pairs of one frame at each position, all four tone / sign codes among them, both parities over the cases."""
+    frame = amd.bert_frames(1, callsign="FAR", token=first_symbol & 0xFFFFFF)
+    parity = (first_symbol // 7) & 1
+    got = M.samples(amd, frame, first_symbol, parity).reshape(M.FSYMS, M.SPS, 2)
+    codes = M.symbol_codes(M.onair_bits(amd, frame), first_symbol, parity)
+    rng = np.random.default_rng(first_symbol)
+    syms = np.concatenate([[0, M.FSYMS - 1], rng.integers(0, M.FSYMS, 198)])
+    smps = np.concatenate([[0, M.SPS - 1], rng.integers(0, M.SPS, 198)])
+    assert set(codes[syms].tolist()) == {-2, -1, 1, 2}
+    for k, i in zip(syms.tolist(), smps.tolist()):
+        assert np.array_equal(got[k, i], amd.txb_patch(first_symbol + k, i, int(codes[k]))), (k, i)
+    assert {(s // 7) & 1 for s in FAR_STARTS} == {0, 1}
 
 
 def test_patch_tap_is_the_host_modulators_sample(amd):

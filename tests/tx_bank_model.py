@@ -1,6 +1,6 @@
 """The tests' own model of a transmit-bank modulator (tests/test_tx_bank_host.py pins it to the host modulator, the GPU tests
 rely on it): the on-air bits of a frame, the sign parity they carry, the tone / sign code of every symbol, the NCO phases at a
-symbol start. Pure numpy over the library's parity taps (opv_tap_tx_frame, opv_tap_tx_checkpoints); nothing here needs a GPU."""
+symbol start, and from these the samples of a modulator that stands anywhere in its run (libm, plain Python floats). Numpy over the library's parity taps (opv_tap_tx_frame, opv_tap_tx_checkpoints); nothing here needs a GPU."""
 import math
 
 import numpy as np
@@ -63,6 +63,39 @@ def symbol_phases(amd, first_symbol, n_symbols):
     flat = out.reshape(-1, 2)
     a = first_symbol - j0 * CKPT_SYMS
     return flat[a:a + n_symbols]
+
+
+def sample_phases(p, inc):
+    """the 40 phases of one symbol's samples from its start phase `p`: the reference's add and wrap (src/opv-mod.cpp:274-279)
+    in plain Python floats"""
+    out = []
+    for _ in range(SPS):
+        out.append(p)
+        p += inc
+        if p > PI:
+            p -= 2.0 * PI
+        elif p < -PI:
+            p += 2.0 * PI
+    return out
+
+
+def samples(amd, frames, first_symbol=0, parity=0):
+    """int16[2 * 40 * n_symbols]: what a modulator that stands at symbol `first_symbol` of its run with sign parity `parity`
+    makes of the whole frames `frames` - wherever it stands: first_symbol need not be a multiple of 2168, the symbol's index
+    only drives b_n and the phases. Each sample is int(16383.0 * (sgn * math.sin(ph))) / math.cos: THIS process's libm and
+    truncation toward zero (reference src/opv-mod.cpp:268-279), not numpy's vector paths; silent symbol 0 gives zeros."""
+    codes = symbol_codes(onair_bits(amd, frames), first_symbol, parity)
+    ph = symbol_phases(amd, first_symbol, codes.size) if codes.size else np.zeros((0, 2))
+    flat = []
+    for a, (p1, p2) in zip(codes.tolist(), ph.tolist()):
+        if a == 0:
+            flat += [0] * (2 * SPS)
+            continue
+        sgn = 1.0 if a > 0 else -1.0
+        for p in sample_phases(p1, INC1) if abs(a) == 1 else sample_phases(p2, INC2):
+            flat.append(int(16383.0 * (sgn * math.sin(p))))
+            flat.append(int(16383.0 * (sgn * math.cos(p))))
+    return np.array(flat, np.int16)
 
 
 def flat_bits(ph):

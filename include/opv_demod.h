@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_scan_* (wideband scan: an exact probe bank on a wide capture, and the carriers in a row of its powers);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wb_seg_phase / opv_wb_seg_next / opv_wb_retune / opv_wb_segments / opv_wbtx_retune / opv_wbtx_segments (per-channel retune and Doppler ramps: an LO schedule per channel of the four wideband converters);
+                               still 7, additive: + opv_scan_* (wideband scan: an exact probe bank on a wide capture, and the carriers in a row of its powers);
                                still 7, additive: + opv_div_* (receive diversity: the soft symbols of several streams combined per frame);
                                still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
                                still 7, additive: + opv_wbr_plan/ opv_wbr_outputs / opv_wb_create_rational (the wideband front door at any radio rate: an exact rational resampler bank);
@@ -276,6 +277,59 @@ typedef struct opv_wbr_cfg {
 int opv_wbr_plan(const opv_wbr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
 size_t opv_wbr_outputs(const opv_wbr_cfg* cfg, uint64_t n_wide_total);
 int opv_wb_create_rational(opv_wb** out, opv_ctx* ctx, const opv_wbr_cfg* cfg, const int* streams, const double* centre_hz, const int16_t* taps);
+/* ---- per-channel retune and Doppler ramps: an LO schedule per channel -------------------------------------------------------
+ * The four converters above and below (opv_wb_create, opv_wb_create_rational, opv_wbtx_create, opv_wbtx_create_rational) fix a
+ * channel's LO at creation. A schedule lets it move while the object runs - a carrier found by opv_scan_carriers handed to a running
+ * door, a LEO pass followed through tens of kHz, an uplink pre-compensated - without emptying the filter history and without a
+ * jump of the LO's phase: piecewise-linear frequency, continuous phase, closed form, no carried accumulator. Same contract:
+ * integer-exact, held to a numpy model with == (tests/test_gpu_wideband_tune.py), any split into pushes gives the same bytes
+ * provided each retune is made before its `at` is pushed, and an object that is never retuned produces the bytes it produced
+ * before, from the same kernels.
+ *   schedule: per channel a list of segments with ascending `start`, an ABSOLUTE wide-sample index: the a = first_sample + n of
+ *     the formulas above, on the transmit side the absolute index of the wide sample WRITTEN. Sample a uses the last segment with
+ *     start <= a.
+ *   phase, in turns / 2^64, with d = a - start: phi64(a) = phase + d x inc + ramp x tri(d), all modulo 2^64;
+ *     tri(d) = d (d - 1) / 2 as an integer (the even factor halved first), then modulo 2^64: defined for every uint64 d.
+ *     phi64(a + 1) - phi64(a) = inc + ramp x d: a frequency that moves linearly.
+ *   mix: i = phi64 >> 52, c = T[i], s = T[(i - 1024) & 4095] (opv_wb_lo_table); mix, filter, round, clamp, output counts and
+ *     history of each converter are exactly as written for it.
+ *   creation: one segment {start 0, phase 0, inc = (uint64)inc_k << 32, ramp 0}: ((a x inc_k << 32) mod 2^64) >> 52 ==
+ *     ((a x inc_k) mod 2^32) >> 20, the phase of the formulas above. The new rule contains the old one.
+ * opv_wb_seg_phase (host only): phi64(a) of a segment. opv_wb_seg_next (host only, no device): the segment that follows `prev`
+ *   from sample `at` on: start = at; phase = opv_wb_seg_phase(prev, at), which is what makes the phase continuous;
+ *   inc = (uint64)inc32 << 32 with inc32 by opv_wbr_plan's increment rule for (down, up, centre_hz), bit for bit (the integer
+ *   door and the integer bank: down = decim resp. interp, up = 1: one definition serves all converters);
+ *   ramp = (int64) llrint(rate_hz_s / fw / fw x 18446744073709551616.0), fw = (double)down x 2 168 000.0 / (double)up, these double
+ *   operations in this order. From `at` on the channel sits at centre_hz + rate_hz_s x (a - at) / fw. OPV_EINVAL for a null
+ *   pointer, down or up below 1, a centre or rate that is not finite, |rate_hz_s| > OPV_WB_TUNE_MAX_RATE.
+ * opv_wb_retune / opv_wbtx_retune (both kinds of either object): appends one segment per entry, opv_wb_seg_next's from the
+ *   channel's last segment; with phase_given != 0 the entry's `phase` is taken as is instead (a rebuilt object at a migration
+ *   destination continues in phase; a deliberate phase reset). It never waits and enqueues nothing, applies to pushes enqueued
+ *   after the call, and may be called between opv_wb_push_async calls without opv_push_wait: pushes in flight keep the tables
+ *   they were launched with. Write A for the next wide sample the object reads or writes: first_sample + N on the receive side,
+ *   first_sample + W(N) on the transmit side. Decided on the host before anything changes; a batch applies whole or not at all:
+ *     OPV_ESTATE for at < A (the past cannot be retuned) and for a detached object;
+ *     OPV_EINVAL for at < start of the channel's last segment + OPV_WB_TUNE_GAP (the creation segment imposes no gap; on an
+ *       object with N = 0 a tune at at = first_sample replaces it), a channel out of range, two entries for one channel that
+ *       violate the gap, a centre or rate that is not finite, |rate_hz_s| > OPV_WB_TUNE_MAX_RATE, a null pointer, count < 0;
+ *     OPV_ECAPACITY when a channel would hold more than OPV_WB_TUNE_SEGS segments. A segment is dropped, at a push or a retune,
+ *       once its successor starts at or before the oldest sample the object can still mix: A - min(N, carry) on the receive
+ *       side, which mixes its carried history again every push, and A on the transmit side.
+ *   So every segment with a successor, except the creation segment, is at least OPV_WB_TUNE_GAP samples long, and a workgroup,
+ *   whose span is at most 4096 wide samples, meets at most two segments of a channel.
+ * opv_wb_segments / opv_wbtx_segments: copies the channel's live segments, oldest first, at most `cap` of them, and returns
+ *   their count (negative: OPV_EINVAL for a null object or a channel out of range).
+ * opv_wbtx_reset returns every channel to its creation schedule. The schedule does not migrate: rebuild the object at the
+ *   destination and retune it with phase_given. */
+#define OPV_WB_TUNE_GAP  4096      /* wide samples between the starts of two segments of a channel (= a workgroup's largest span) */
+#define OPV_WB_TUNE_SEGS 16        /* segments a channel holds at a time */
+#define OPV_WB_TUNE_MAX_RATE 1.0e7 /* |rate_hz_s| */
+typedef struct opv_wb_seg  { uint64_t start, phase, inc; int64_t ramp; } opv_wb_seg;                  /* 32 bytes */
+typedef struct opv_wb_tune { int32_t channel, phase_given; uint64_t at; double centre_hz, rate_hz_s; uint64_t phase; } opv_wb_tune; /* 40 bytes */
+uint64_t opv_wb_seg_phase(const opv_wb_seg* seg, uint64_t a);
+int opv_wb_seg_next(const opv_wb_seg* prev, int32_t down, int32_t up, uint64_t at, double centre_hz, double rate_hz_s, opv_wb_seg* out);
+int opv_wb_retune(opv_wb* wb, int count, const opv_wb_tune* tunes);
+int opv_wb_segments(opv_wb* wb, int channel, opv_wb_seg* out, size_t cap);
 /* ---- wideband scan: which carriers are in a wide capture, and where ------------------------------------------------------
  * The doors above take their channels' centres as given, and the receive chain behind them acquires a carrier only within the
  * reference's coarse search (-1500 .. +1500 Hz) of where it is told to look; a radio's oscillator is off by far more. An opv_scan
@@ -821,6 +875,10 @@ typedef struct opv_wbtxr_cfg {
 int opv_wbtxr_plan(const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out);
 uint64_t opv_wbtxr_outputs(const opv_wbtxr_cfg* cfg, uint64_t n_in_total);
 int opv_wbtx_create_rational(opv_wbtx** out, opv_ctx* ctx, const opv_wbtxr_cfg* cfg, const double* centre_hz, const int16_t* taps);
+/* the LO schedule of an up-converter bank of either kind: the rule, the refusals and the structs are opv_wb_retune's above, with
+ * A = first_sample + W(N) (the integer bank: N interp), the next wide sample the object writes */
+int opv_wbtx_retune(opv_wbtx* wbtx, int count, const opv_wb_tune* tunes);
+int opv_wbtx_segments(opv_wbtx* wbtx, int channel, opv_wb_seg* out, size_t cap);
 /* Device-side channel tool for synthetic multi-stream workloads:
  * d_out[n] = clip(rint(gain * d_in[n] * exp(j 2 pi f0 n / Fs) + sigma * N(0,1)+jN(0,1))),
  * noise from a counter-based generator keyed by (seed, n). d_in/d_out: device int16 IQ. */

@@ -24,9 +24,9 @@ __device__ __forceinline__ uint32_t lds_slot(uint32_t j, uint32_t D, uint32_t m,
     return (j - row * D) * rowlen + row;
 }
 
-}  // namespace
-
-extern "C" __global__ __launch_bounds__(256) void k_wb_ddc(OpvWbArgs a) {
+// the kernel's body, once for both sources of the LO (k_wideband_common.h: WbLoFixed, WbLoTuned)
+template <class Lo>
+__device__ __forceinline__ void wb_ddc(const OpvWbArgs a, const typename Lo::Table* lo_table, uint32_t lo_base) {
     __shared__ int raw[OPV_WB_SPAN];          // packed int16 I | Q << 16
     __shared__ int2 mixed[OPV_WB_SPAN];       // (mr, mi) of the channel in hand
     __shared__ int16_t lo[4096];
@@ -46,17 +46,17 @@ extern "C" __global__ __launch_bounds__(256) void k_wb_ddc(OpvWbArgs a) {
     wb_fetch_span<OPV_WB_THREADS>(raw, a.hist_in, a.hist_len, a.src, a.n_new, base_i, span, tid, [=](uint32_t j) { return lds_slot(j, D, recip, rowlen); });
     __syncthreads();
 
-    // phase of local sample j: phi = (uint32)((first_sample + n) * inc) - the low 32 bits only, so 32-bit arithmetic that wraps
-    const uint32_t a_base = a.a0_lo + (uint32_t)(uint64_t)base_i;
+    // phase of local sample j: Lo's for sample base_i + j of the push (WbLoFixed: phi = (uint32)((first_sample + n) * inc) - the
+    // low 32 bits only, so 32-bit arithmetic that wraps)
     const uint32_t k_end = (blockIdx.y + 1) * a.kper < a.K ? (blockIdx.y + 1) * a.kper : a.K;
     const int* taps = (const int*)a.taps;                               // the integer door's image: h[L] widened to int32
     const uint32_t u_lo = a.lpad - (L - 1);                             // tap t reads local sample lane * D + (lpad - t)
     for (uint32_t k = blockIdx.y * a.kper; k < k_end; ++k) {
-        const uint32_t inc = a.inc[k];
+        const auto lo_of = Lo::channel(lo_table, lo_base, k, (uint32_t)(uint64_t)base_i);
         for (uint32_t p = 0; p < D; ++p) {
             for (uint32_t row = tid; row < rowlen; row += OPV_WB_THREADS) {
                 int c, s;
-                wb_lo_at(lo, (a_base + row * D + p) * inc, c, s);
+                lo_of(lo, row * D + p, c, s);
                 mixed[p * rowlen + row] = wb_mix_down(raw[p * rowlen + row], c, s);
             }
         }
@@ -76,3 +76,10 @@ extern "C" __global__ __launch_bounds__(256) void k_wb_ddc(OpvWbArgs a) {
         __syncthreads();
     }
 }
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(256) void k_wb_ddc(OpvWbArgs a) { wb_ddc<WbLoFixed>(a, a.inc, a.a0_lo); }
+
+// the same door behind an LO schedule (opv_wb_retune): sched[K] is this push's table, its origin kWbSchedBack samples in front of src[0]
+extern "C" __global__ __launch_bounds__(256) void k_wb_ddc_tuned(OpvWbArgs a, const OpvWbDevSched* sched) { wb_ddc<WbLoTuned>(a, sched, kWbSchedBack); }

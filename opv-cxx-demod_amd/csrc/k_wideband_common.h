@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "opv_wb_rules.h"
+
 // the LO table T[4096] (opv_wb_lo_table), from global memory into LDS
 template <uint32_t T>
 __device__ __forceinline__ void wb_load_lo(int16_t* lo, const int16_t* table, uint32_t tid) {
@@ -24,6 +26,64 @@ __device__ __forceinline__ void wb_lo_at(const int16_t* lo, uint32_t phi, int& c
     c = lo[ix];
     s = lo[(ix - 1024u) & 4095u];
 }
+
+// the same pair from a phase in turns / 2^64 (the LO schedule's phi64): the one place that takes an index from it
+__device__ __forceinline__ void wb_lo_at64(const int16_t* lo, uint64_t phi, int& c, int& s) {
+    const uint32_t ix = (uint32_t)(phi >> 52);
+    c = lo[ix];
+    s = lo[(ix - 1024u) & 4095u];
+}
+
+// ---- where a kernel's LO comes from: a phase functor. Lo::channel(table, base, k, first) is asked once per (workgroup, channel)
+// with `first`, the workgroup's first sample as an index within the push (wrapping 32 bits; the front door's may lie in front of the
+// push); what it returns gives (c, s) of the workgroup's sample j: lo_of(lo, j, c, s). The bodies of the kernels are written once
+// against it. `table` and `base` are handed over as plain values, like everything else here, not kept in members.
+//
+// WbLoFixed: the LO of an object that was never retuned, phi = (uint32)(a x inc_k) with a = a0_lo + first + j; table = inc[K], base = a0_lo
+struct WbLoFixed {
+    typedef uint32_t Table;
+    struct Chan {
+        uint32_t inc, a_base;
+        __device__ __forceinline__ void operator()(const int16_t* lo, uint32_t j, int& c, int& s) const { wb_lo_at(lo, (a_base + j) * inc, c, s); }
+    };
+    static __device__ __forceinline__ Chan channel(const uint32_t* inc, uint32_t a0_lo, uint32_t k, uint32_t first) { return Chan{inc[k], a0_lo + first}; }
+};
+
+// WbLoTuned: the LO schedule; table = sched[K], channel k's table for this push (opv_wb_rules.h, OpvWbDevSched), base = back: local
+// index first + back + j of the table is the workgroup's sample j. A workgroup spans at most OPV_WB_TUNE_GAP samples, so it meets at most
+// two segments: both are fetched here, uniform per (workgroup, channel) - scalar loads - and a sample selects by one compare
+// against the boundary. Per sample: d < 2^32, tri(d) = d (d - 1) / 2 < 2^63 exactly, then the low 64 bits of d x inc (32 x 64) and
+// of ramp x tri (64 x 64).
+struct WbLoTuned {
+    typedef OpvWbDevSched Table;
+    struct Chan {
+        uint32_t base, start0, start1;
+        uint64_t phase0, inc0, ramp0, phase1, inc1, ramp1;
+        __device__ __forceinline__ void operator()(const int16_t* lo, uint32_t j, int& c, int& s) const {
+            const uint32_t jj = base + j;
+            const bool late = jj >= start1;
+            const uint32_t d = jj - (late ? start1 : start0);
+            const uint64_t tri = ((uint64_t)d * (uint64_t)(d - 1u)) >> 1;      // (d = 0: 0 x (2^32 - 1))
+            wb_lo_at64(lo, (late ? phase1 : phase0) + (uint64_t)d * (late ? inc1 : inc0) + (late ? ramp1 : ramp0) * tri, c, s);
+        }
+    };
+    static __device__ __forceinline__ Chan channel(const OpvWbDevSched* sched, uint32_t back, uint32_t k, uint32_t first) {
+        const OpvWbDevSched* t = sched + k;
+        Chan ch;
+        ch.base = first + back;
+        uint32_t n = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < (uint32_t)OPV_WB_TUNE_SEGS; ++i) n += t->start[i] <= ch.base ? 1u : 0u;
+        const uint32_t s0 = n ? n - 1u : 0u;                               // (nothing begins at or before the first sample: only
+                                                                           // samples in front of the object's history, which are zeros)
+        const uint32_t s1 = s0 + 1u < (uint32_t)OPV_WB_TUNE_SEGS ? s0 + 1u : s0;
+        ch.start0 = t->start[s0];
+        ch.start1 = s1 != s0 ? t->start[s1] : 0xFFFFFFFFu;
+        ch.phase0 = t->phase[s0]; ch.inc0 = t->inc[s0]; ch.ramp0 = (uint64_t)t->ramp[s0];
+        ch.phase1 = t->phase[s1]; ch.inc1 = t->inc[s1]; ch.ramp1 = (uint64_t)t->ramp[s1];
+        return ch;
+    }
+};
 
 // down: packed (I | Q << 16) times (c - i s)
 __device__ __forceinline__ int2 wb_mix_down(int x, int c, int s) {

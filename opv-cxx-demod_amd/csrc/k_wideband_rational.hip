@@ -28,9 +28,9 @@ constexpr uint32_t kMixedLen = OPV_WB_SPAN + OPV_WB_SPAN / 32;
 
 __device__ __forceinline__ uint32_t mixed_slot(uint32_t j) { return j + (j >> 5); }
 
-}  // namespace
-
-extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
+// the kernel's body, once for both sources of the LO (k_wideband_common.h: WbLoFixed, WbLoTuned)
+template <class Lo>
+__device__ __forceinline__ void wbr_ddc(const OpvWbrArgs a, const typename Lo::Table* lo_table, uint32_t lo_base) {
     __shared__ int raw[OPV_WB_SPAN];          // packed int16 I | Q << 16, in sample order
     __shared__ int2 mixed[kMixedLen];         // (mr, mi) of the channel in hand, padded (above)
     __shared__ int16_t lo[4096];
@@ -58,8 +58,8 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
     wb_fetch_span<OPV_WB_THREADS>(raw, a.hist_in, a.hist_len, a.src, a.n_new, base_i, span, tid, [](uint32_t j) { return j; });
     __syncthreads();
 
-    // phase of local sample j: phi = (uint32)((first_sample + n) * inc) - the low 32 bits only, so 32-bit arithmetic that wraps
-    const uint32_t a_base = a.a0_lo + (uint32_t)(uint64_t)base_i;
+    // phase of local sample j: Lo's for sample base_i + j of the push (WbLoFixed: phi = (uint32)((first_sample + n) * inc) - the
+    // low 32 bits only, so 32-bit arithmetic that wraps)
     const uint32_t k_end = (blockIdx.y + 1) * a.kper < a.K ? (blockIdx.y + 1) * a.kper : a.K;
     const uint32_t tl = pbase + (tid < cnt ? tid : 0u) * M;
     const uint32_t dn = tl / U;
@@ -67,10 +67,10 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
     const int16_t* tab = (const int16_t*)a.taps;                        // the rational door's image: the phase-major int16 table
     const int2* row = (const int2*)(tab + (size_t)(tl - dn * U) * rowlen);   // 4 taps per 8 bytes
     for (uint32_t k = blockIdx.y * a.kper; k < k_end; ++k) {
-        const uint32_t inc = a.inc[k];
+        const auto lo_of = Lo::channel(lo_table, lo_base, k, (uint32_t)(uint64_t)base_i);
         for (uint32_t j = tid; j < span; j += OPV_WB_THREADS) {
             int c, s;
-            wb_lo_at(lo, (a_base + j) * inc, c, s);
+            lo_of(lo, j, c, s);
             mixed[mixed_slot(j)] = wb_mix_down(raw[j], c, s);
         }
         __syncthreads();
@@ -91,3 +91,10 @@ extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) {
         __syncthreads();
     }
 }
+
+}  // namespace
+
+extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc(OpvWbrArgs a) { wbr_ddc<WbLoFixed>(a, a.inc, a.a0_lo); }
+
+// the same door behind an LO schedule (opv_wb_retune): sched[K] is this push's table, its origin kWbSchedBack samples in front of src[0]
+extern "C" __global__ __launch_bounds__(256) void k_wbr_ddc_tuned(OpvWbrArgs a, const OpvWbDevSched* sched) { wbr_ddc<WbLoTuned>(a, sched, kWbSchedBack); }

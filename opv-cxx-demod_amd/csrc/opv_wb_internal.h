@@ -43,6 +43,8 @@ struct OpvWbArgs : OpvWbHead {
     uint32_t rowlen;         // tile + lpad / D: entries per decimation phase of the workgroup's span; D * rowlen <= OPV_WB_SPAN
 };
 extern "C" __global__ void k_wb_ddc(OpvWbArgs a);
+struct OpvWbDevSched;        // opv_wb_rules.h: one channel's LO schedule as the kernels of one push read it
+extern "C" __global__ void k_wb_ddc_tuned(OpvWbArgs a, const OpvWbDevSched* sched);      // the same behind an LO schedule; a.inc is not read
 
 // Arguments of k_wbr_ddc (csrc/k_wideband_rational.hip): the rational door, wide rate 2 168 000 x M / U, carry = J - 1. Output r of
 // the object reads wide samples n_r - j, j = 0 .. J - 1, with n_r = floor(r M / U), against row p_r = (r M) mod U of the phase-major
@@ -55,6 +57,7 @@ struct OpvWbrArgs : OpvWbHead {
     uint32_t tile;           // outputs per workgroup (<= 256): rowlen + floor(tile M / U) <= OPV_WB_SPAN
 };
 extern "C" __global__ void k_wbr_ddc(OpvWbrArgs a);
+extern "C" __global__ void k_wbr_ddc_tuned(OpvWbrArgs a, const OpvWbDevSched* sched);
 
 // ---- what the context offers (defined at the end of opv_push.hip; opv_int_fail in opv_capi.hip)
 int opv_int_fail(int code, const char* what, hipError_t e = hipSuccess);   // sets opv_last_error, returns code

@@ -29,6 +29,146 @@ int wb_plan_increments(int32_t down, int32_t up, int32_t n_channels, const doubl
     return OPV_OK;
 }
 
+// ---- the LO schedule
+int wb_seg_next(const opv_wb_seg* prev, int32_t down, int32_t up, uint64_t at, double centre_hz, double rate_hz_s, opv_wb_seg* out, const char** why) {
+    if (!prev || !out) return refuse(why, OPV_EINVAL, "opv_wb_seg_next: null pointer");
+    if (down < 1 || up < 1) return refuse(why, OPV_EINVAL, "opv_wb_seg_next: down or up below 1");
+    if (!std::isfinite(rate_hz_s)) return refuse(why, OPV_EINVAL, "opv_wb_seg_next: non-finite rate");
+    if (std::fabs(rate_hz_s) > OPV_WB_TUNE_MAX_RATE) return refuse(why, OPV_EINVAL, "opv_wb_seg_next: |rate_hz_s| above OPV_WB_TUNE_MAX_RATE");
+    uint32_t inc32 = 0;
+    if (int r = wb_plan_increments(down, up, 1, &centre_hz, &inc32, why, "opv_wb_seg_next: non-finite centre frequency",
+                                   "opv_wb_seg_next: centre frequency out of range"))
+        return r;
+    const double fw = (double)down * 2168000.0 / (double)up;
+    opv_wb_seg s;
+    s.start = at;
+    s.phase = wb_seg_phase(*prev, at);
+    s.inc = (uint64_t)inc32 << 32;
+    s.ramp = (int64_t)std::llrint(rate_hz_s / fw / fw * 18446744073709551616.0);   // |.| <= 1e7 / 2 168 000^2 x 2^64 < 2^46
+    *out = s;
+    return OPV_OK;
+}
+
+void wb_sched_reset(WbSchedule& s, int32_t down, int32_t up, uint32_t K, const uint32_t* inc) {
+    s.down = down;
+    s.up = up;
+    s.inc.assign(inc, inc + K);
+    s.seg.assign(K, std::vector<opv_wb_seg>());
+    for (uint32_t k = 0; k < K; ++k) s.seg[k].push_back(opv_wb_seg{0, 0, (uint64_t)inc[k] << 32, 0});
+    s.created.assign(K, 1);
+}
+
+bool wb_sched_plain(const WbSchedule& s) {
+    for (size_t k = 0; k < s.seg.size(); ++k)
+        if (!s.created[k] || s.seg[k].size() != 1) return false;
+    return true;
+}
+
+namespace {
+
+// one channel's list: the segments in front of the last one that starts at or before `oldest` go. A start is compared as a
+// distance from `oldest`, so that a first_sample near 2^64 would wrap like every other index here.
+void prune_channel(std::vector<opv_wb_seg>& seg, uint8_t& created, uint64_t oldest) {
+    size_t keep = 0;
+    for (size_t i = 1; i < seg.size(); ++i)
+        if ((int64_t)(seg[i].start - oldest) <= 0) keep = i;
+    if (keep) {
+        seg.erase(seg.begin(), seg.begin() + (ptrdiff_t)keep);
+        created = 0;
+    }
+}
+
+}  // namespace
+
+void wb_sched_prune(WbSchedule& s, uint64_t oldest) {
+    for (size_t k = 0; k < s.seg.size(); ++k) prune_channel(s.seg[k], s.created[k], oldest);
+}
+
+int wb_sched_retune(WbSchedule& s, uint64_t A, uint64_t oldest, int count, const opv_wb_tune* tunes, const char** why) {
+    if (count < 0) return refuse(why, OPV_EINVAL, "opv_wb_retune: count below 0");
+    if (count == 0) return OPV_OK;
+    if (!tunes) return refuse(why, OPV_EINVAL, "opv_wb_retune: null pointer");
+    const int K = (int)s.seg.size();
+    // ---- what is wrong with an entry by itself
+    for (int i = 0; i < count; ++i) {
+        const opv_wb_tune& t = tunes[i];
+        if (t.channel < 0 || t.channel >= K) return refuse(why, OPV_EINVAL, "opv_wb_retune: channel out of range");
+        if (!std::isfinite(t.centre_hz) || !std::isfinite(t.rate_hz_s)) return refuse(why, OPV_EINVAL, "opv_wb_retune: non-finite centre or rate");
+        if (std::fabs(t.rate_hz_s) > OPV_WB_TUNE_MAX_RATE) return refuse(why, OPV_EINVAL, "opv_wb_retune: |rate_hz_s| above OPV_WB_TUNE_MAX_RATE");
+    }
+    for (int i = 0; i < count; ++i)
+        if (tunes[i].at < A) return refuse(why, OPV_ESTATE, "opv_wb_retune: the past cannot be retuned");
+    // ---- the batch on copies of the lists it touches: the object's own change only once nothing can refuse any more
+    std::vector<int> touched;
+    std::vector<std::vector<opv_wb_seg>> lists;
+    std::vector<uint8_t> flags;
+    for (int i = 0; i < count; ++i) {
+        const opv_wb_tune& t = tunes[i];
+        size_t at = 0;
+        while (at < touched.size() && touched[at] != t.channel) ++at;
+        if (at == touched.size()) {
+            touched.push_back(t.channel);
+            lists.push_back(s.seg[(size_t)t.channel]);
+            flags.push_back(s.created[(size_t)t.channel]);
+            prune_channel(lists[at], flags[at], oldest);
+        }
+        std::vector<opv_wb_seg>& seg = lists[at];
+        const opv_wb_seg& last = seg.back();
+        const bool creation = flags[at] && seg.size() == 1;
+        if (!creation && t.at - last.start < (uint64_t)OPV_WB_TUNE_GAP)           // (t.at >= A >= last.start unless last lies ahead: then the difference wraps or is small)
+            return refuse(why, OPV_EINVAL, "opv_wb_retune: less than OPV_WB_TUNE_GAP samples behind the channel's last segment");
+        if (!creation && (int64_t)(t.at - last.start) < 0) return refuse(why, OPV_EINVAL, "opv_wb_retune: in front of the channel's last segment");
+        opv_wb_seg next;
+        if (int r = wb_seg_next(&last, s.down, s.up, t.at, t.centre_hz, t.rate_hz_s, &next, why)) return r;
+        if (t.phase_given) next.phase = t.phase;
+        seg.push_back(next);
+        prune_channel(seg, flags[at], oldest);                                   // (a tune at the oldest sample replaces what was there: N = 0 and the creation segment)
+        if (seg.size() > (size_t)OPV_WB_TUNE_SEGS) return refuse(why, OPV_ECAPACITY, "opv_wb_retune: more than OPV_WB_TUNE_SEGS segments on a channel");
+    }
+    for (size_t i = 0; i < touched.size(); ++i) {
+        s.seg[(size_t)touched[i]].swap(lists[i]);
+        s.created[(size_t)touched[i]] = flags[i];
+    }
+    return OPV_OK;
+}
+
+int wb_sched_copy(const WbSchedule& s, int channel, opv_wb_seg* out, size_t cap) {
+    if (channel < 0 || channel >= (int)s.seg.size()) return OPV_EINVAL;
+    const std::vector<opv_wb_seg>& seg = s.seg[(size_t)channel];
+    for (size_t i = 0; i < seg.size() && i < cap && out; ++i) out[i] = seg[i];
+    return (int)seg.size();
+}
+
+void wb_sched_table(const WbSchedule& s, uint64_t origin, uint64_t reach, OpvWbDevSched* out) {
+    for (size_t k = 0; k < s.seg.size(); ++k) {
+        const std::vector<opv_wb_seg>& seg = s.seg[k];
+        OpvWbDevSched& t = out[k];
+        uint32_t n = 0;
+        for (size_t i = 0; i < seg.size() && n < (uint32_t)OPV_WB_TUNE_SEGS; ++i) {
+            const int64_t rel = (int64_t)(seg[i].start - origin);
+            if (i + 1 < seg.size() && (int64_t)(seg[i + 1].start - origin) <= 0) continue;   // over before the origin
+            if (rel > 0 && (uint64_t)rel >= reach) break;                                     // begins behind the push
+            if (rel <= 0) {                                                                   // re-based to the origin
+                const uint64_t d0 = origin - seg[i].start;
+                t.start[n] = 0;
+                t.phase[n] = wb_seg_phase(seg[i], origin);
+                t.inc[n] = seg[i].inc + (uint64_t)seg[i].ramp * d0;
+            } else {
+                t.start[n] = (uint32_t)rel;
+                t.phase[n] = seg[i].phase;
+                t.inc[n] = seg[i].inc;
+            }
+            t.ramp[n] = seg[i].ramp;
+            ++n;
+        }
+        for (; n < (uint32_t)OPV_WB_TUNE_SEGS; ++n) {
+            t.start[n] = 0xFFFFFFFFu;
+            t.phase[n] = t.inc[n] = 0;
+            t.ramp[n] = 0;
+        }
+    }
+}
+
 extern "C" void opv_wb_lo_table(int16_t out4096[4096]) {
     if (!out4096) return;
     for (int i = 0; i < 4096; ++i) out4096[i] = (int16_t)std::lrint(32767.0 * std::cos(2.0 * 3.14159265358979323846 * (double)i / 4096.0));

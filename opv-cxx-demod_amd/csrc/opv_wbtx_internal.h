@@ -34,6 +34,8 @@ constexpr uint32_t OPV_WBTX_SPAN = OPV_WBTX_THREADS + 1024;                 // i
 constexpr uint32_t OPV_WBTX_TAPS = 1024 + 16;                               // J U <= L - 1 + U entries, zeros from L on
 
 extern "C" __global__ void k_wbtx_duc(OpvWbtxArgs a);
+struct OpvWbDevSched;        // opv_wb_rules.h: one channel's LO schedule as the kernels of one push read it
+extern "C" __global__ void k_wbtx_duc_tuned(OpvWbtxArgs a, const OpvWbDevSched* sched);  // the same behind an LO schedule; a.inc is not read
 
 // Arguments of k_wbtxr_duc (k_wideband_tx_rational.hip: the object made by opv_wbtx_create_rational). The wide rate is
 // 2 168 000 x M / U: output i of this push is wide sample W(N) + i of the object; with t = p0 + i U it reads input floor(t / M) of
@@ -50,5 +52,6 @@ constexpr uint32_t OPV_WBTXR_MAXJ = 64;                                     // (
 constexpr uint32_t OPV_WBTXR_SPAN = OPV_WBTXR_THREADS + OPV_WBTXR_MAXJ;     // input samples a workgroup holds per channel: <= floor(255 U / M) + 1 new ones + 2 J2 - 1 <= 63 in front
 
 extern "C" __global__ void k_wbtxr_duc(OpvWbtxrArgs a);
+extern "C" __global__ void k_wbtxr_duc_tuned(OpvWbtxrArgs a, const OpvWbDevSched* sched);
 
 #endif

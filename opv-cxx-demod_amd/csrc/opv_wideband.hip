@@ -18,6 +18,7 @@
 #include "opv_wb_rules.h"
 
 static_assert(kWbrSpan == OPV_WB_SPAN && kWbrMaxTile == OPV_WB_THREADS, "opv_wb_rules.h sizes k_wbr_ddc's tile for this span");
+static_assert(kWbSchedBack == OPV_WB_SPAN && OPV_WB_TUNE_GAP == OPV_WB_SPAN, "a workgroup's span reaches no further back than a schedule table's origin, and meets at most two segments");
 
 namespace {
 
@@ -45,6 +46,8 @@ struct opv_wb {
     uint32_t* d_inc = nullptr;
     OpvStage stage;                      // pageable sources: the block is copied here first (grow-only)
     int** h_tab = nullptr;               // pinned: kTabSlots x K destination pointers, read in place by the kernel
+    WbSchedule sched;                    // the LO schedule of every channel (opv_wb_retune); plain until the first retune
+    OpvWbDevSched* h_sched = nullptr;    // pinned: kTabSlots x K schedule tables, a slot per push like h_tab's, read in place by the kernel
     hipEvent_t tab_ev[kTabSlots] = {};
     unsigned pushes = 0;
     uint32_t tile = 0, lpad = 0, rowlen = 0;
@@ -81,6 +84,8 @@ int make_object(opv_wb** out, opv_ctx* ctx, const char* who, int K, uint32_t car
     w->K = (uint32_t)K;
     w->carry = carry;
     w_init(w);
+    if (w->kind == WbKind::Rational) wb_sched_reset(w->sched, w->rcfg.down, w->rcfg.up, (uint32_t)K, inc);
+    else wb_sched_reset(w->sched, w->cfg.decim, 1, (uint32_t)K, inc);
     int16_t lo[4096];
     opv_wb_lo_table(lo);
     auto undo = [&](hipError_t e, const char* what) { opv_wb_destroy(w); return opv_int_fail(OPV_EHIP, what, e); };
@@ -92,6 +97,7 @@ int make_object(opv_wb** out, opv_ctx* ctx, const char* who, int K, uint32_t car
     HIPCHK_OR(undo, hipMalloc(&w->d_taps, taps_bytes));
     HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
     HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)kTabSlots * K * sizeof(int*), hipHostMallocDefault));
+    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_sched, (size_t)kTabSlots * K * sizeof(OpvWbDevSched), hipHostMallocDefault));
     HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
     HIPCHK_OR(undo, hipMemcpy(w->d_taps, taps, taps_bytes, hipMemcpyHostToDevice));
     HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc, (size_t)K * 4, hipMemcpyHostToDevice));
@@ -125,6 +131,7 @@ extern "C" void opv_wb_destroy(opv_wb* w) {
     for (auto& e : w->tab_ev)
         if (e) (void)hipEventDestroy(e);
     if (w->h_tab) (void)hipHostFree(w->h_tab);
+    if (w->h_sched) (void)hipHostFree(w->h_sched);
     void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->stage.d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -225,6 +232,16 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     std::memcpy(tab, dst.data(), (size_t)K * sizeof(int*));
     void* d_tab = nullptr;
     HIPCHK(hipHostGetDevicePointer(&d_tab, tab, 0));
+    // ---- the LO: an object never retuned launches the unscheduled kernel; any other one this push's schedule tables, in the slot
+    // beside its destinations (a retune between two asynchronous pushes changes the lists, never a table in flight)
+    const uint64_t first_sample = rational ? w->rcfg.first_sample : w->cfg.first_sample;
+    const bool tuned = !wb_sched_plain(w->sched);
+    void* d_sched = nullptr;
+    if (tuned) {
+        OpvWbDevSched* st = w->h_sched + (size_t)slot * K;
+        wb_sched_table(w->sched, first_sample + w->n_total - kWbSchedBack, (uint64_t)n_new + kWbSchedBack, st);
+        HIPCHK(hipHostGetDevicePointer(&d_sched, st, 0));
+    }
     // few output tiles (a short push, a large ratio): the channels are shared out over blockIdx.y so that the device still fills
     const uint32_t tiles = n_out ? (n_out + w->tile - 1) / w->tile : 1;
     uint32_t ky = tiles >= 512 ? 1 : (512 + tiles - 1) / tiles;
@@ -240,7 +257,7 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     h.inc = w->d_inc;
     h.dst = (int* const*)d_tab;
     h.n_before = w->n_total;
-    h.a0_lo = (uint32_t)((rational ? w->rcfg.first_sample : w->cfg.first_sample) + w->n_total);
+    h.a0_lo = (uint32_t)(first_sample + w->n_total);
     h.n_new = (uint32_t)n_new;
     h.hist_len = w->hist_len;
     h.n_out = n_out;
@@ -251,13 +268,15 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
         a.p0 = first.phase;
         a.M = (uint32_t)w->rcfg.down; a.U = (uint32_t)w->rcfg.up; a.J = w->carry + 1;
         a.rowlen = w->rowlen; a.tile = w->tile;
-        k_wbr_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+        if (tuned) k_wbr_ddc_tuned<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a, (const OpvWbDevSched*)d_sched);
+        else k_wbr_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
     } else {
         OpvWbArgs a{h};
         a.r0 = r0;
         a.D = (uint32_t)w->cfg.decim; a.L = (uint32_t)w->cfg.n_taps;
         a.tile = w->tile; a.lpad = w->lpad; a.rowlen = w->rowlen;
-        k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
+        if (tuned) k_wb_ddc_tuned<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a, (const OpvWbDevSched*)d_sched);
+        else k_wb_ddc<<<dim3(tiles, ky), OPV_WB_THREADS, 0, w->door.copy_stream>>>(a);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(w->tab_ev[slot], w->door.copy_stream));
@@ -265,6 +284,7 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     w->cur ^= 1;
     w->n_total += n_new;
     w->hist_len = w->n_total < (uint64_t)w->carry ? (uint32_t)w->n_total : w->carry;
+    wb_sched_prune(w->sched, first_sample + w->n_total - w->hist_len);  // what no later push can mix any more
     return opv_int_push_end(w->ctx, wait);
 }
 
@@ -280,4 +300,29 @@ extern "C" int opv_wb_flush(opv_wb* w) {
     for (int s : w->streams)
         if (int r = opv_flush(w->ctx, s)) return r;
     return OPV_OK;
+}
+
+// ---- the LO schedule (include/opv_demod.h, "per-channel retune and Doppler ramps"); the rules are opv_wb_rules.h's
+extern "C" uint64_t opv_wb_seg_phase(const opv_wb_seg* seg, uint64_t a) { return seg ? wb_seg_phase(*seg, a) : 0; }
+
+extern "C" int opv_wb_seg_next(const opv_wb_seg* prev, int32_t down, int32_t up, uint64_t at, double centre_hz, double rate_hz_s, opv_wb_seg* out) {
+    const char* why = nullptr;
+    if (int r = wb_seg_next(prev, down, up, at, centre_hz, rate_hz_s, out, &why)) return opv_int_fail(r, why);
+    return OPV_OK;
+}
+
+// host only: the lists change, nothing is enqueued and nothing waited for; pushes in flight read the tables they were launched with
+extern "C" int opv_wb_retune(opv_wb* w, int count, const opv_wb_tune* tunes) {
+    if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_retune: null object");
+    if (!w->door.shared->ctx_alive) return opv_int_fail(OPV_ESTATE, "opv_wb_retune: the object's context has been destroyed");
+    const uint64_t A = (w->kind == WbKind::Rational ? w->rcfg.first_sample : w->cfg.first_sample) + w->n_total;
+    const char* why = nullptr;
+    if (int r = wb_sched_retune(w->sched, A, A - w->hist_len, count, tunes, &why)) return opv_int_fail(r, why);
+    return OPV_OK;
+}
+
+extern "C" int opv_wb_segments(opv_wb* w, int channel, opv_wb_seg* out, size_t cap) {
+    if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_segments: null object");
+    const int n = wb_sched_copy(w->sched, channel, out, cap);
+    return n < 0 ? opv_int_fail(OPV_EINVAL, "opv_wb_segments: channel out of range") : n;
 }

@@ -33,6 +33,9 @@ struct opv_wbtx {
     uint32_t* d_inc = nullptr;
     const int** d_tab = nullptr;         // the push's K input pointers as the kernel reads them ...
     const int** h_tab = nullptr;         // ... and the pinned copy they are uploaded from
+    WbSchedule sched;                    // the LO schedule of every channel (opv_wbtx_retune); plain until the first retune
+    OpvWbDevSched* d_sched = nullptr;    // a retuned object: the push's K schedule tables as the kernel reads them ...
+    OpvWbDevSched* h_sched = nullptr;    // ... and the pinned copy they are uploaded from (a push waits for its launch: one slot)
 };
 
 extern "C" int opv_wbtx_plan(const opv_wbtx_cfg* cfg, const double* centre_hz, const int16_t* taps, uint32_t* inc_out) {
@@ -46,7 +49,8 @@ extern "C" void opv_wbtx_destroy(opv_wbtx* w) {
     (void)hipSetDevice(w->door.device);
     if (w->door.shared && w->door.shared->ctx_alive && w->stream) (void)hipStreamSynchronize(w->stream);   // (a context destroyed first waited for its stream itself)
     if (w->h_tab) (void)hipHostFree(w->h_tab);
-    void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->d_tab};
+    if (w->h_sched) (void)hipHostFree(w->h_sched);
+    void* ptrs[] = {w->d_hist[0], w->d_hist[1], w->d_lo, w->d_taps, w->d_inc, w->d_tab, w->d_sched};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     delete w;
@@ -63,6 +67,7 @@ static int wbtx_make(opv_wbtx** out, opv_ctx* ctx, const char* what, const opv_w
     w->ctx = ctx;
     w->door = door;
     w->stream = ctx->stream;
+    wb_sched_reset(w->sched, (int32_t)w->shape.down, (int32_t)w->shape.up, K, inc);
     int16_t lo[4096];
     opv_wb_lo_table(lo);
     auto undo = [&](hipError_t e, const char* where) { opv_wbtx_destroy(w); return fail(OPV_EHIP, where, e); };
@@ -77,6 +82,8 @@ static int wbtx_make(opv_wbtx** out, opv_ctx* ctx, const char* what, const opv_w
     HIPCHK_OR(undo, hipMalloc(&w->d_inc, (size_t)K * 4));
     HIPCHK_OR(undo, hipMalloc(&w->d_tab, (size_t)K * sizeof(int*)));
     HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_tab, (size_t)K * sizeof(int*), hipHostMallocDefault));
+    HIPCHK_OR(undo, hipMalloc(&w->d_sched, (size_t)K * sizeof(OpvWbDevSched)));
+    HIPCHK_OR(undo, hipHostMalloc((void**)&w->h_sched, (size_t)K * sizeof(OpvWbDevSched), hipHostMallocDefault));
     HIPCHK_OR(undo, hipMemcpy(w->d_lo, lo, sizeof lo, hipMemcpyHostToDevice));
     HIPCHK_OR(undo, hipMemcpy(w->d_taps, image, image_len * 2, hipMemcpyHostToDevice));
     HIPCHK_OR(undo, hipMemcpy(w->d_inc, inc, (size_t)K * 4, hipMemcpyHostToDevice));
@@ -143,6 +150,8 @@ extern "C" int opv_wbtx_reset(opv_wbtx* w, uint64_t first_sample) {
     HIPCHK(hipStreamSynchronize(w->stream));
     w->n_total = 0;
     w->first_sample = first_sample;
+    const std::vector<uint32_t> inc = w->sched.inc;
+    wb_sched_reset(w->sched, w->sched.down, w->sched.up, w->shape.K, inc.data());   // every channel back to its creation schedule
     return OPV_OK;
 }
 
@@ -170,23 +179,53 @@ extern "C" int opv_wbtx_push(opv_wbtx* w, const int16_t* const* d_in, size_t n_i
     h.n_in = (uint32_t)n_in;
     h.n_out = (uint32_t)n_out;
     h.K = K; h.S = w->S; h.H = w->H;
-    if (w->shape.kind == WbtxKind::Rational) {
+    // ---- the LO: an object never retuned launches the unscheduled kernel; any other one the tables of this push, whose origin
+    // is the push's first wide sample
+    const bool rational = w->shape.kind == WbtxKind::Rational;
+    const uint64_t wide0 = rational ? wbtxr_first_output(M, U, w->n_total).n0 : w->n_total * M;
+    const bool tuned = !wb_sched_plain(w->sched);
+    if (tuned) {
+        wb_sched_table(w->sched, w->first_sample + wide0, n_out, w->h_sched);
+        HIPCHK(hipMemcpyAsync(w->d_sched, w->h_sched, (size_t)K * sizeof(OpvWbDevSched), hipMemcpyHostToDevice, w->stream));
+    }
+    if (rational) {
         const WbtxrFirst first = wbtxr_first_output(M, U, w->n_total);
         h.a0_lo = (uint32_t)(w->first_sample + first.n0);
         OpvWbtxrArgs a{h};
         a.M = M; a.U = U; a.J2 = (w->J + 1) / 2; a.rowlen = w->rowlen;
         a.p0 = first.phase;
-        k_wbtxr_duc<<<(h.n_out + OPV_WBTXR_THREADS - 1) / OPV_WBTXR_THREADS, OPV_WBTXR_THREADS, 0, w->stream>>>(a);
+        const uint32_t grid = (h.n_out + OPV_WBTXR_THREADS - 1) / OPV_WBTXR_THREADS;
+        if (tuned) k_wbtxr_duc_tuned<<<grid, OPV_WBTXR_THREADS, 0, w->stream>>>(a, w->d_sched);
+        else k_wbtxr_duc<<<grid, OPV_WBTXR_THREADS, 0, w->stream>>>(a);
     } else {
         const uint32_t interp = M;                                        // (the integer bank's ratio is interp / 1)
         h.a0_lo = (uint32_t)(w->first_sample + w->n_total * interp);      // the first wide sample is N interp
         OpvWbtxArgs a{h};
         a.U = interp; a.L = w->L; a.J = w->J;
-        k_wbtx_duc<<<(h.n_out + OPV_WBTX_THREADS - 1) / OPV_WBTX_THREADS, OPV_WBTX_THREADS, 0, w->stream>>>(a);
+        const uint32_t grid = (h.n_out + OPV_WBTX_THREADS - 1) / OPV_WBTX_THREADS;
+        if (tuned) k_wbtx_duc_tuned<<<grid, OPV_WBTX_THREADS, 0, w->stream>>>(a, w->d_sched);
+        else k_wbtx_duc<<<grid, OPV_WBTX_THREADS, 0, w->stream>>>(a);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(w->stream));                               // (the inputs and the output are the caller's again)
     w->cur ^= 1;
     w->n_total += n_in;
+    wb_sched_prune(w->sched, w->first_sample + wide0 + n_out);            // what no later push can write any more
     return OPV_OK;
+}
+
+// ---- the LO schedule (include/opv_demod.h, "per-channel retune and Doppler ramps"); the rules are opv_wb_rules.h's
+extern "C" int opv_wbtx_retune(opv_wbtx* w, int count, const opv_wb_tune* tunes) {
+    if (!w) return fail(OPV_EINVAL, "opv_wbtx_retune: null object");
+    if (!w->door.shared->ctx_alive) return fail(OPV_ESTATE, "opv_wbtx_retune: the object's context has been destroyed");
+    const uint64_t wide = w->shape.kind == WbtxKind::Rational ? wbtxr_outputs(w->shape.down, w->shape.up, w->n_total) : w->n_total * w->shape.down;
+    const char* why = nullptr;
+    if (int r = wb_sched_retune(w->sched, w->first_sample + wide, w->first_sample + wide, count, tunes, &why)) return fail(r, why);
+    return OPV_OK;
+}
+
+extern "C" int opv_wbtx_segments(opv_wbtx* w, int channel, opv_wb_seg* out, size_t cap) {
+    if (!w) return fail(OPV_EINVAL, "opv_wbtx_segments: null object");
+    const int n = wb_sched_copy(w->sched, channel, out, cap);
+    return n < 0 ? fail(OPV_EINVAL, "opv_wbtx_segments: channel out of range") : n;
 }

@@ -38,6 +38,7 @@ EXPORTS = [
     "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
     "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
     "opv_wbr_plan", "opv_wbr_outputs", "opv_wb_create_rational",
+    "opv_wb_seg_phase", "opv_wb_seg_next", "opv_wb_retune", "opv_wb_segments", "opv_wbtx_retune", "opv_wbtx_segments",
     "opv_tx_stream_create", "opv_tx_stream_reset", "opv_tx_stream_frames", "opv_tx_stream_tail", "opv_tx_stream_destroy", "opv_tap_tx_frame",
     "opv_tap_push_soft",
     "opv_enable_link_report", "opv_pop_frames_link", "opv_device_link", "opv_link_payloads",
@@ -80,6 +81,20 @@ class WbtxCfg(C.Structure):
 class WbtxrCfg(C.Structure):
     _fields_ = [("down", C.c_int32), ("up", C.c_int32), ("n_channels", C.c_int32), ("n_taps", C.c_int32), ("out_shift", C.c_int32),
                 ("reserved", C.c_int32), ("first_sample", C.c_uint64)]
+
+
+class WbSeg(C.Structure):
+    """opv_wb_seg: a segment of a channel's LO schedule (32 bytes)"""
+    _fields_ = [("start", C.c_uint64), ("phase", C.c_uint64), ("inc", C.c_uint64), ("ramp", C.c_int64)]
+
+    def astuple(self):
+        return (int(self.start), int(self.phase), int(self.inc), int(self.ramp))
+
+
+class WbTune(C.Structure):
+    """opv_wb_tune: an entry of a retune (40 bytes)"""
+    _fields_ = [("channel", C.c_int32), ("phase_given", C.c_int32), ("at", C.c_uint64), ("centre_hz", C.c_double), ("rate_hz_s", C.c_double),
+                ("phase", C.c_uint64)]
 
 
 class ScanCfg(C.Structure):
@@ -297,6 +312,13 @@ def lib():
         L.opv_txb_round.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.opv_txb_plan_round.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.opv_tap_txb_patch.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_void_p]
+        L.opv_wb_seg_phase.restype = C.c_uint64
+        L.opv_wb_seg_phase.argtypes = [C.POINTER(WbSeg), C.c_uint64]
+        L.opv_wb_seg_next.argtypes = [C.POINTER(WbSeg), C.c_int32, C.c_int32, C.c_uint64, C.c_double, C.c_double, C.POINTER(WbSeg)]
+        L.opv_wb_retune.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.opv_wb_segments.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.opv_wbtx_retune.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.opv_wbtx_segments.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
         L.opv_wbtx_plan.argtypes = [C.POINTER(WbtxCfg), C.c_void_p, C.c_void_p, C.c_void_p]
         L.opv_wbtx_create.argtypes = [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(WbtxCfg), C.c_void_p, C.c_void_p]
         L.opv_wbtx_destroy.restype = None
@@ -679,6 +701,45 @@ def wbr_outputs(down, up, n_wide_total):
     return int(lib().opv_wbr_outputs(C.byref(cfg), int(n_wide_total)))
 
 
+# ---- the LO schedule of a channel (opv_wb_seg_*, opv_wb_retune, opv_wbtx_retune)
+WB_TUNE_GAP, WB_TUNE_SEGS, WB_TUNE_MAX_RATE = 4096, 16, 1.0e7
+
+
+def _wb_seg(seg):
+    return seg if isinstance(seg, WbSeg) else WbSeg(*[int(v) for v in seg])
+
+
+def wb_seg_phase(seg, a):
+    """opv_wb_seg_phase: phi64(a) of a segment (a WbSeg or (start, phase, inc, ramp)); host only"""
+    return int(lib().opv_wb_seg_phase(C.byref(_wb_seg(seg)), int(a) % (1 << 64)))
+
+
+def wb_seg_next(prev, down, up, at, centre_hz, rate_hz_s=0.0):
+    """opv_wb_seg_next: the WbSeg that follows `prev` from sample `at` on at centre_hz, moving by rate_hz_s; host only, needs no device"""
+    out = WbSeg()
+    _chk(lib().opv_wb_seg_next(C.byref(_wb_seg(prev)), int(down), int(up), int(at), float(centre_hz), float(rate_hz_s), C.byref(out)))
+    return out
+
+
+def _wb_tunes(tunes):
+    """entries (channel, at, centre_hz[, rate_hz_s[, phase]]) or WbTune -> (count, array); a phase that is given is taken as is"""
+    arr = (WbTune * max(len(tunes), 1))()
+    for i, t in enumerate(tunes):
+        if isinstance(t, WbTune):
+            arr[i] = t
+            continue
+        t = tuple(t)
+        arr[i] = WbTune(int(t[0]), int(len(t) > 4 and t[4] is not None), int(t[1]), float(t[2]), float(t[3]) if len(t) > 3 else 0.0,
+                        int(t[4]) % (1 << 64) if len(t) > 4 and t[4] is not None else 0)
+    return len(tunes), arr
+
+
+def _wb_segments(call, h, channel):
+    out = (WbSeg * WB_TUNE_SEGS)()
+    n = _chk(call(h, int(channel), out, WB_TUNE_SEGS))
+    return [WbSeg(*out[i].astuple()) for i in range(n)]
+
+
 class Wideband:
     """A bank of DDCs on the device that feeds streams[k] of `demod` with the channel at centre_hz[k] of one wide capture
     (opv_wb_*, include/opv_demod.h). Close it before its Demod."""
@@ -721,6 +782,16 @@ class Wideband:
 
     def flush(self):
         _chk(lib().opv_wb_flush(self.h))
+
+    def retune(self, tunes):
+        """opv_wb_retune: `tunes` is a list of (channel, at, centre_hz[, rate_hz_s[, phase]]) or WbTune, `at` an absolute wide-sample
+        index not yet pushed; the whole batch or nothing. Allowed between push_async calls."""
+        n, arr = _wb_tunes(tunes)
+        _chk(lib().opv_wb_retune(self.h, n, arr))
+
+    def segments(self, channel):
+        """opv_wb_segments: the channel's live segments (WbSeg), oldest first"""
+        return _wb_segments(lib().opv_wb_segments, self.h, channel)
 
     def close(self):
         if getattr(self, "h", None):
@@ -859,6 +930,15 @@ class WidebandTx:
 
     def reset(self, first_sample=0):
         _chk(lib().opv_wbtx_reset(self.h, int(first_sample)))
+
+    def retune(self, tunes):
+        """opv_wbtx_retune: as Wideband.retune; `at` is the absolute index of a wide sample not yet written"""
+        n, arr = _wb_tunes(tunes)
+        _chk(lib().opv_wbtx_retune(self.h, n, arr))
+
+    def segments(self, channel):
+        """opv_wbtx_segments: the channel's live segments (WbSeg), oldest first"""
+        return _wb_segments(lib().opv_wbtx_segments, self.h, channel)
 
     def close(self):
         if getattr(self, "h", None):

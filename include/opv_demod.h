@@ -155,7 +155,7 @@ typedef struct opv_ctx opv_ctx;
 /* ---- lifetime: replaces constructing MSKDemodulatorAFC + SyncTracker + FrameDecoder
  *      (src/opv-demod.cpp:999-1001 / :1164,:1182-1183) for n_streams independent captures */
 int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg);
-/* Environment variables. The library reads FIVE, all of them TEST HOOKS - never set in production -, all of them in opv_create
+/* Environment variables. The library reads SEVEN, all of them TEST HOOKS - never set in production -, all of them in opv_create
  * and nowhere else (a context's behaviour is fixed when it is created; grep getenv csrc/):
  *   OPV_OFFSET_DISTRUST_LIBM  (any value) the offset search's last-place ties are decided by the device's sincos although the host's
  *                             libm reproduces the reference's (opv_offset_ties_on_host() == 0): moves a stream whose search ties
@@ -167,7 +167,13 @@ int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg);
  *   OPV_PUSH_GATHER_BLOCKS    (a number > 0) workgroups of that gather kernel (default 32; a measurement knob, results unaffected).
  *   OPV_FRONTEND_INT16_RING   (any value) k_msk_frontend_rb keeps its int16 sample ring at every stream count, instead of the fp64 ring
  *                             a helper wave fills while the context has no more streams than the device has CUs: same results
- *                             bit for bit, slower. Its parity test runs both. */
+ *                             bit for bit, slower. Its parity test runs both.
+ *   OPV_FRONTEND_TF_GUARD     (a number != 0) k_msk_frontend_rb / _rb_wg4 keep the timing loop's clamp in every demodulate() call, instead
+ *                             of dropping it in calls that provably cannot reach it (csrc/opv_tf_rule.h): same results bit for bit.
+ *                             tests/test_gpu_trip8_tf_proof.py runs both.
+ *   OPV_TEST_TIMING_FREQ0     (a double, strtod: hex floats welcome) the timing_freq every stream starts from at creation and reset,
+ *                             0 otherwise like the reference's. Nothing else puts a stream near the +/-0.1 clamp: with the reference's
+ *                             loop gains timing_freq moves by about 2e-4 per call whatever the input. */
 void opv_destroy(opv_ctx* ctx);
 const char* opv_last_error(void);
 int opv_abi_version(void);
@@ -683,6 +689,11 @@ uint64_t opv_offset_ties_left_to_device(opv_ctx* ctx);
  * out[3] = 100 MHz ticks (s_memrealtime) spent inside the kernel. Diagnostic: placement census and the clock the
  * chip held (cycles / ticks x 100 MHz); no counterpart in the reference. */
 int opv_tap_wave_info(opv_ctx* ctx, int stream, uint64_t out[4]);
+
+/* demodulate() calls of `stream` since its reset that k_msk_frontend_rb / _rb_wg4 ran out[0] = without the timing loop's clamp (the
+ * per-call proof of csrc/opv_tf_rule.h held) and out[1] = with it. The four- and sixteen-streams-per-wave mappings always clamp and
+ * count nothing; an imported stream starts at 0. Diagnostic; no counterpart in the reference. */
+int opv_tap_frontend_calls(opv_ctx* ctx, int stream, uint64_t out[2]);
 
 /* Workgroups of each hot-path kernel the runtime can keep resident per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor), in the
  * order k_msk_frontend_rb, _rb_wg4, k_msk_frontend_x16_wg4, k_msk_frontend_x4_wg4, k_frame_decode, k_frame_scale. Diagnostic. */

@@ -38,7 +38,8 @@
 //     correlations of both tones + the on-time sums P1..P4) as row partials in lane t = lane & 15, one all-reduce over
 //     the four rows completes them, v_mov_b64_dpp row_newbcast hands out what the loop filters need, the energies and
 //     the dominant-tone select (shift and select in one v_cndmask_b32_dpp per word) are lane-parallel. The four-symbol loop
-//     holds 142.25 instructions per symbol on the fp64 ring, 150.25 on the int16 ring (census of the device assembly).
+//     holds 140.25 instructions per symbol on the fp64 ring (142.25 in a call that keeps the timing clamp), 148.25 / 150.25 on the
+//     int16 ring (scripts/experiments/trip_census.py on the device assembly).
 //     The scalar loop filters run redundantly on all lanes (wave-uniform, no divergence).
 //   * A LONE wave on a SIMD issues one instruction of ANY kind (VALU, SALU, LDS, s_nop, branch)
 //     every ~4.7 cycles and gains nothing from independent chains (scripts/microbench): the
@@ -74,6 +75,7 @@
 #include <type_traits>
 
 #include "k_frontend_common.h"
+#include "opv_tf_rule.h"
 
 namespace {
 
@@ -141,9 +143,10 @@ __device__ inline bool uni_lt(double a, double b) { return __builtin_amdgcn_fcmp
 __device__ inline bool uni_eq(double a, double b) { return __builtin_amdgcn_fcmp(a, b, 1 /*FCMP_OEQ*/) != 0ull; }
 
 // instantiations of the per-symbol body (see `symbol` in the kernel)
-struct TagFirst { static constexpr bool first = true, wide = true; };     // first symbol of a demodulate() call
-struct TagSecond { static constexpr bool first = false, wide = true; };   // second symbol under an out-of-range -o
-struct TagSteady { static constexpr bool first = false, wide = false; };  // everything else
+struct TagFirst { static constexpr bool first = true, wide = true, tf_free = false; };     // first symbol of a demodulate() call
+struct TagSecond { static constexpr bool first = false, wide = true, tf_free = false; };   // second symbol under an out-of-range -o
+struct TagSteady { static constexpr bool first = false, wide = false, tf_free = false; };  // everything else ...
+struct TagSteadyFree { static constexpr bool first = false, wide = false, tf_free = true; };   // ... in a call whose timing clamp cannot act (opv_tf_clamp_cannot_act)
 
 // X = exp(j x), x = kfs * fo, |x| <= 0.284 (fo within the AFC clamp of +/-2000 Hz, |kf| <= 49):
 //   sin x = x + x u q(u),  cos x = 1 + u r(u),  u = x^2,
@@ -346,6 +349,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
     const int eof = (int)uni((uint32_t)st.eof);
     int overflow = (int)uni((uint32_t)st.overflow), stalled = 0;
     uint32_t edge_ties = uni(st.edge_ties);
+    uint32_t calls_free = 0, calls_guarded = 0;   // demodulate() calls of this launch by the nest they took (opv_tap_frontend_calls)
     const uint64_t cap_soft = st.cap_soft;
     if (cap_soft > (1ull << 28)) overflow = 1;  // byte offsets into the soft ring are kept in 32 bits
     // oldest soft symbol the tracker may still read: its 24-symbol window, or the payload / next
@@ -722,7 +726,10 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 ted = fma(fma(-den, ted, num), iden, ted);
             }
             __builtin_amdgcn_sched_barrier(0);
-            tf = clampd(fma(kc_beta, ted, tf), kc_ntfmax, kc_tfmax);  // beta (ref :118,:283-284)
+            // beta (ref :118,:283-284). Without the clamp where the call's proof holds (opv_tf_rule.h: opv_tf_clamp_cannot_act):
+            // fmin(fmax(x, -0.1), 0.1) returns every non-NaN x inside the bounds unchanged, so the bits are the same.
+            if constexpr (decltype(tag)::tf_free) tf = fma(kc_beta, ted, tf);
+            else tf = clampd(fma(kc_beta, ted, tf), kc_ntfmax, kc_tfmax);
             const double adj = fma(kc_alpha, ted, tf);                // alpha (ref :117,:285); the +/-2 clamp (:286) cannot act
             pos += 40.0 + adj;                                        // ref :313
             fetch_addr(pos, false);
@@ -765,6 +772,10 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         using Slot3 = std::integral_constant<uint32_t, 3>;
         auto sym = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) { symbol_r(tag, slot, cur, prv); };
 
+        // The call's symbols, from the first one through the batch loop, in two instantiations chosen once per call (below):
+        // `steady` is TagSteady, or TagSteadyFree where the timing clamp provably cannot act in this call. The first symbol and
+        // the second one under an out-of-range -o keep the clamp in both.
+        auto call_symbols = [&](auto steady) {
         if (uni_lt(pos + 40.0 + 10.0, Nd)) {               // ref :221
             (void)housekeeping(pos, NoAdvance{});
             fetch(pos, true);
@@ -798,17 +809,18 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 //    in program order and one wave's LDS operations execute in order, the taps (>= floor(pos) - 10) are at or
                 //    above the new `low` as well, and the helper never writes a slot at or above `low`; on the int16 ring a
                 //    tile request refills the slot of tile t_lo only once the lowest tap has left it.
-                // (Six s_nop in front of the nest put the trip loop's top at 8 mod 32: the same loop ran 5.6 cycles per symbol
-                // slower at 16 mod 32. tools/align_vop3.py reports the address at every build and says how many to add when
-                // code in front of here has moved it. The fp64 ring only: with two waves per CU, 512 streams on the int16 ring,
+                // (The s_nop in front of each nest put its trip loop's top at 8 mod 32: the same loop ran 5.6 cycles per symbol
+                // slower at 16 mod 32. tools/align_vop3.py reports both addresses at every build and says how many to add when
+                // code in front of here has moved one; the two nests carry their own counts. The fp64 ring only: with two waves per CU, 512 streams on the int16 ring,
                 // a loop so placed measured 1.2 % slower than where hipcc happened to put it. NOTEBOOK.md, Round 13.)
-                if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                if constexpr (F64 && decltype(steady)::tf_free) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                else if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
                 while (more >= 4u) {
                     for (uint32_t quads = more >> 2; quads != 0u; --quads) {
-                        sym(TagSteady{}, Slot0{}, qq, qp);
-                        sym(TagSteady{}, Slot1{}, qp, qq);
-                        sym(TagSteady{}, Slot2{}, qq, qp);
-                        sym(TagSteady{}, Slot3{}, qp, qq);
+                        sym(steady, Slot0{}, qq, qp);
+                        sym(steady, Slot1{}, qp, qq);
+                        sym(steady, Slot2{}, qq, qp);
+                        sym(steady, Slot3{}, qp, qq);
                         soft_v += 32u;
                     }
                     more = uni(housekeeping(pos, more & ~3u));   // (0 once the helper is lost)
@@ -819,16 +831,24 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 uint32_t pairs = more >> 1;
                 const uint32_t batch = 2u * pairs + 1u;    // symbols of this batch: they fit in front of the soft ring's wrap
                 for (; pairs != 0u; --pairs) {
-                    sym(TagSteady{}, Slot0{}, qq, qp);
-                    sym(TagSteady{}, Slot1{}, qp, qq);
+                    sym(steady, Slot0{}, qq, qp);
+                    sym(steady, Slot1{}, qp, qq);
                     soft_v += 16u;
                 }
-                sym(TagSteady{}, Slot0{}, qq, qp);
+                sym(steady, Slot0{}, qq, qp);
                 fo_settle();
                 soft_advance(batch);
                 qp = qq;
             }
         }
+        };
+        // Once per call, wave-uniform: can the timing clamp act on any symbol of it? (tf moves by kc_beta |ted| per symbol.)
+        // Both nests compute the same bits wherever the rule holds; where it does not, the guarded nest is the reference's text.
+        // tf cannot turn NaN inside a call (den >= 1e-10 and dm >= 1e-100 keep ted finite on int16 input), and a NaN handed in
+        // fails the rule.
+        const double tf_uni = mkd((int)uni((uint32_t)dhi(tf)), (int)uni((uint32_t)dlo(tf)));
+        if (cfg.tf_guard == 0 && opv_tf_clamp_cannot_act(tf_uni, N)) { ++calls_free; call_symbols(TagSteadyFree{}); }
+        else { ++calls_guarded; call_symbols(TagSteady{}); }
 
         // ---- end of this demodulate() call (ref :318-328, :1067-1076) ------------------------
         const uint32_t nsym_call = ((soft_off - soft_off0) & soft_bmask) >> 3;
@@ -859,6 +879,7 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         st.origin = origin; st.n_soft = n_soft; st.total_samples = total_samples;
         st.n_chunks = n_chunks; st.tail_done = tail_done; st.overflow = overflow;
         st.stalled = stalled;
+        st.fe_calls_free += calls_free; st.fe_calls_guarded += calls_guarded;
         // where and at which clock this stream's wave ran (two scalar reads per launch; opv_tap_wave_info)
         unsigned hw, xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));

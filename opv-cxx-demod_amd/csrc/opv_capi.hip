@@ -144,13 +144,16 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
         HIPCHK_OR(hip_failed, hipMalloc(&c->d_offs_wtab, sizeof(double) * w.size()));
         HIPCHK_OR(hip_failed, hipMemcpy(c->d_offs_wtab, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice));
     }
-    // The library's four environment switches, all TEST HOOKS (include/opv_demod.h has the table): read here, once per context,
+    // The library's environment switches, all TEST HOOKS (include/opv_demod.h has the table): read here, once per context,
     // and nowhere else - a context never changes its behaviour after it has been created.
     c->host_ties = opv_offset_host_libm_matches_reference() && !std::getenv("OPV_OFFSET_DISTRUST_LIBM");
     c->tx_trust_libm = opv_tx_libm_flat_tops_as_assumed() && !std::getenv("OPV_TX_DISTRUST_LIBM");
     c->push_gather = !std::getenv("OPV_PUSH_NO_GATHER");
     if (const char* e = std::getenv("OPV_PUSH_GATHER_BLOCKS")) { const int v = atoi(e); if (v > 0) c->push_gather_blocks = (uint32_t)v; }
     c->rb_fp64_ring = !std::getenv("OPV_FRONTEND_INT16_RING");
+    if (const char* e = std::getenv("OPV_FRONTEND_TF_GUARD")) c->tf_guard = atoi(e) != 0;
+    double timing_freq0 = 0.0;               // (strtod, not atof: the tests hand over values one ulp apart as hex floats)
+    if (const char* e = std::getenv("OPV_TEST_TIMING_FREQ0")) timing_freq0 = std::strtod(e, nullptr);
     {   // k_msk_frontend_rb addresses its dynamic LDS from address 0 on: it must have no static LDS (k_frontend.hip)
         hipFuncAttributes fa;
         HIPCHK_OR(hip_failed, hipFuncGetAttributes(&fa, kFrontend[FE_RB].fn));
@@ -192,6 +195,7 @@ extern "C" int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg) {
         // demod.set_freq_offset(init_offset) only in streaming mode (ref :1004-1005)
         s.freq_offset = (cfg->streaming && cfg->have_init_offset) ? cfg->init_offset_hz : 0.0;
         s.afc_alpha = cfg->afc_alpha;  // set_afc_bandwidth (ref :1009 / :1172)
+        s.timing_freq = timing_freq0;  // 0 (ref :341) unless the test hook says otherwise
         s.est_offset = NAN;
         s.x40c = 1.0;  // X[40] of a (non-existent) previous symbol; only ever multiplies a zero prev
         s.trk_state = OPV_HUNTING;
@@ -377,7 +381,7 @@ extern "C" int opv_process(opv_ctx* c) {
     if (!round_fits_grid(fr, S)) return fail(OPV_EINVAL, "opv_process: streams x frames per round exceeds the grid limit");
     commit_host_view(c, slot);
     c->div.launched(fr);
-    const OpvGlobalCfg g{c->cfg.streaming, c->cfg.have_init_offset, c->cfg.init_offset_hz};
+    const OpvGlobalCfg g{c->cfg.streaming, c->cfg.have_init_offset, c->cfg.init_offset_hz, c->tf_guard ? 1 : 0, 0};
     if (int r = upload_inputs(c, in, slot)) return r;
     if (int r = launch_search(c, g)) return r;
     if (int r = launch_frontend(c, g)) return r;
@@ -647,6 +651,14 @@ extern "C" int opv_tap_wave_info(opv_ctx* c, int s, uint64_t out[4]) {
     if (int r = c->refresh()) return r;
     const OpvStream& st = c->mirror[s];
     out[0] = st.dbg_hw_id; out[1] = st.dbg_xcc_id; out[2] = st.dbg_cycles; out[3] = st.dbg_ticks;
+    return OPV_OK;
+}
+
+extern "C" int opv_tap_frontend_calls(opv_ctx* c, int s, uint64_t out[2]) {
+    if (int r = check_stream(c, s)) return r;
+    if (!out) return fail(OPV_EINVAL, "null out");
+    if (int r = c->refresh()) return r;
+    out[0] = c->mirror[s].fe_calls_free; out[1] = c->mirror[s].fe_calls_guarded;
     return OPV_OK;
 }
 

@@ -177,6 +177,7 @@ struct opv_ctx {
     bool tx_trust_libm = false;         // the host's sin / cos behave at the transmit NCOs' flat tops as k_tx_modulate.hip assumes (probed at opv_create)
     bool push_gather = true;            // opv_push_iq_batch moves pinned blocks with one gather kernel (else: one copy per block)
     uint32_t push_gather_blocks = 32;   // workgroups of that kernel (see push_deferred)
+    bool tf_guard = false;              // OPV_FRONTEND_TF_GUARD: every demodulate() call keeps the timing clamp (k_frontend.hip)
     bool rb_fp64_ring = true;           // k_msk_frontend_rb in its fp64-ring shape (128 threads) while S <= n_cu
     int n_cu = 0;                       // the device's compute units (multiProcessorCount)
     struct TieWork {                    // what the host function gets: stable for the context's life (opv_destroy drains the stream first)

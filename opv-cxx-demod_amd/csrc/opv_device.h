@@ -105,6 +105,9 @@ struct OpvStream {
     // ---- diagnostics of the last front-end launch (opv_tap_wave_info) ----
     uint32_t dbg_hw_id, dbg_xcc_id;   // HW_REG_HW_ID / HW_REG_XCC_ID of the wave that served the stream
     uint64_t dbg_cycles, dbg_ticks;   // s_memtime (shader clock) and s_memrealtime (100 MHz) spent in the kernel
+    // demodulate() calls since reset by the symbol nest they took in k_msk_frontend_rb / _rb_wg4 (opv_tap_frontend_calls): without
+    // the timing clamp (opv_tf_clamp_cannot_act held) / with it. Not carried by a migration: 0 after an import.
+    uint64_t fe_calls_free, fe_calls_guarded;
 };
 
 // ---- offset-search ties decided with the host's libm, in stream order (k_offset_search.hip: k_tie_collect / k_tie_apply,
@@ -157,4 +160,6 @@ struct OpvGlobalCfg {
     int32_t streaming;
     int32_t have_init_offset;
     double init_offset;
+    int32_t tf_guard;         // test hook (OPV_FRONTEND_TF_GUARD): every call takes the nest that keeps the timing clamp
+    int32_t pad;
 };

@@ -213,6 +213,7 @@ extern "C" int opv_import_streams(opv_ctx* c, int count, const int* dst, const v
         st.frec = ini.frec; st.events = ini.events; st.chunk_log = ini.chunk_log;
         st.frames = ini.frames; st.metrics = ini.metrics; st.fscale = ini.fscale;
         st.cap_frames = ini.cap_frames; st.cap_events = ini.cap_events; st.cap_chunks = ini.cap_chunks;
+        st.fe_calls_free = st.fe_calls_guarded = 0;        // (a count of this context's launches, not part of a stream's carry)
         it.stream = (uint32_t)dst[i];
         it.live_first = e.popped % ini.cap_frames;
         it.live_n = (uint32_t)e.seg_n[SEG_FREC];

@@ -33,7 +33,7 @@ EXPORTS = [
     "opv_attach_device_iq", "opv_process", "opv_sync", "opv_set_frontend", "opv_reset_stream", "opv_pop_frames", "opv_pop_events",
     "opv_get_state", "opv_device_frames", "opv_hip_stream", "opv_comm_unique_id", "opv_comm_init", "opv_comm_init_all",
     "opv_comm_destroy", "opv_gather_frames", "opv_gather_frames_all", "opv_tap_soft", "opv_tap_chunks",
-    "opv_tap_offset_energies", "opv_offset_ties_on_host", "opv_offset_ties_decided_on_host", "opv_offset_ties_left_to_device", "opv_tap_wave_info", "opv_tap_occupancy", "opv_decode_payloads", "opv_tx_bert_frame", "opv_tx_bert_frames", "opv_tx_modulated_samples",
+    "opv_tap_offset_energies", "opv_offset_ties_on_host", "opv_offset_ties_decided_on_host", "opv_offset_ties_left_to_device", "opv_tap_wave_info", "opv_tap_frontend_calls", "opv_tap_occupancy", "opv_decode_payloads", "opv_tx_bert_frame", "opv_tx_bert_frames", "opv_tx_modulated_samples",
     "opv_tx_modulate", "opv_tap_tx_checkpoints", "opv_frontend_kernel", "opv_channel_device", "opv_resample_device", "opv_enable_timing", "opv_kernel_times", "opv_tx_modulate_device", "opv_tx_modulate_device_to_host",
     "opv_export_size", "opv_export_streams", "opv_import_streams", "opv_blob_streams",
     "opv_wb_plan", "opv_wb_lo_table", "opv_wb_outputs", "opv_wb_create", "opv_wb_destroy", "opv_wb_push", "opv_wb_push_async", "opv_wb_push_device", "opv_wb_flush", "opv_tap_iq",
@@ -235,6 +235,7 @@ def lib():
         L.opv_tap_chunks.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t]
         L.opv_tap_offset_energies.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.opv_tap_wave_info.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.opv_tap_frontend_calls.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.opv_offset_ties_on_host.argtypes = [C.c_void_p]
         L.opv_offset_ties_decided_on_host.restype = C.c_uint64
         L.opv_offset_ties_decided_on_host.argtypes = [C.c_void_p]
@@ -1141,6 +1142,12 @@ class Demod:
         out = (C.c_uint64 * 4)()
         _chk(lib().opv_tap_wave_info(self.h, stream, out))
         return tuple(int(v) for v in out)
+
+    def frontend_calls(self, stream):
+        """(free, guarded): the stream's demodulate() calls since reset that ran without / with the timing clamp (opv_tap_frontend_calls)"""
+        out = (C.c_uint64 * 2)()
+        _chk(lib().opv_tap_frontend_calls(self.h, stream, out))
+        return int(out[0]), int(out[1])
 
     def occupancy(self):
         """workgroups per CU the runtime can keep resident, per hot-path kernel (opv_tap_occupancy)"""

@@ -151,16 +151,26 @@ def plan(ins, lines_idx, lines, banned):
     return flips
 
 
-def signature(x):
-    """what must survive the pass: the operation and its operands (branch targets are addresses: they move)"""
+def signature(x, distance=False):
+    """what must survive the pass: the operation and its operands (branch targets are addresses: they move; so does the literal
+    of a long branch's s_add_u32 / s_addc_u32, the distance between two labels: `distance`)"""
     mn = base(x[2])
+    if distance:
+        return (mn, x[3].rsplit(",", 1)[0])
     return (mn, "" if mn.startswith(("s_branch", "s_cbranch", "s_call")) else x[3])
 
 
-def verify(before, after, flipped):
+def label_distances(idx, lines):
+    """instructions (indices into a function's list) whose last operand is the distance between two labels: the pair behind the
+    s_getpc_b64 of a branch hipcc relaxed because its target lies beyond the 16-bit range (a function of more than 128 KiB)"""
+    return {k for k, i in enumerate(idx) if ".Lpost_getpc" in lines[i] and mnemonic(lines[i]) in ("s_add_u32", "s_addc_u32")}
+
+
+def verify(before, after, flipped, distances=None):
     """exit non-zero unless every function the pass touched still holds the same instruction and operand sequence"""
     for f in flipped:
-        a, b = [signature(x) for x in before[f]], [signature(x) for x in after.get(f, [])]
+        d = (distances or {}).get(f, ())
+        a, b = [signature(x, k in d) for k, x in enumerate(before[f])], [signature(x, k in d) for k, x in enumerate(after.get(f, []))]
         while a and a[-1][0] == "s_nop":       # padding behind s_endpgm up to the next function is not code
             a.pop()
         while b and b[-1][0] == "s_nop":
@@ -262,7 +272,7 @@ def main():
         else:
             sys.exit("align_vop3: no assembling output after 40 attempts")
         after = disassemble(obj)
-        verify(before, after, flipped)
+        verify(before, after, flipped, {f: label_distances(where[f], lines) for f in flipped})
         report_marked_loops(out, where, after)
         dst.write_text("\n".join(out))
         for f in before:

@@ -38,8 +38,8 @@
 //     correlations of both tones + the on-time sums P1..P4) as row partials in lane t = lane & 15, one all-reduce over
 //     the four rows completes them, v_mov_b64_dpp row_newbcast hands out what the loop filters need, the energies and
 //     the dominant-tone select (shift and select in one v_cndmask_b32_dpp per word) are lane-parallel. The four-symbol loop
-//     holds 140.25 instructions per symbol on the fp64 ring (142.25 in a call that keeps the timing clamp), 148.25 / 150.25 on the
-//     int16 ring (scripts/experiments/trip_census.py on the device assembly).
+//     holds 138.25 instructions per symbol on the fp64 ring (140.25 in a call that keeps the timing clamp), 146.25 / 148.25 on the
+//     int16 ring, 147.25 / 149.25 with four waves per workgroup (scripts/experiments/trip_census.py on the device assembly).
 //     The scalar loop filters run redundantly on all lanes (wave-uniform, no divergence).
 //   * A LONE wave on a SIMD issues one instruction of ANY kind (VALU, SALU, LDS, s_nop, branch)
 //     every ~4.7 cycles and gains nothing from independent chains (scripts/microbench): the
@@ -62,7 +62,7 @@
 //     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
 //     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
 //     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
-//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, round 13 - the batch boundary below - 652.5, profiles/r13_bench_ab.txt).
+//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, round 13 - the batch boundary below - 652.5, profiles/r13_bench_ab.txt; now 631.6 = 9.63 GS/s on 64 streams, profiles/symbol_slots_bench_ab.txt).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
 //     decisions on noisy input do. No MFMA: the per-symbol contraction is
 //     3x4x60 with a serial dependence between symbols.
@@ -323,8 +323,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
     // Loop constants parked in VGPRs: one wave per SIMD has registers to spare, while hipcc
     // otherwise keeps re-forming 64-bit literals in SGPR pairs inside the loop.
     double kc_tfmax = 0.1, kc_beta = 0.00001, kc_alpha = 0.005, kc_fomax = 2000.0, kc_eps = 1e-10;
-    double kc_tiny = 1e-100;
-    asm volatile("" : "+v"(kc_tiny));
+    double kc_tiny = 1e-100, kc_m1 = -1.0;
+    asm volatile("" : "+v"(kc_tiny), "+v"(kc_m1));
     double kc_halfpi = 1.57079632679489661923, kc_32 = 32.0, kc_m1_32 = -1.0 / 32.0, kc_gain = st.afc_alpha * (kSymRate / kTwoPi);
     // rows per unit of the angle table, its inverse, 1.5 * 2^52 + the row offset (the 1025 rows of opv_atan2_q3r)
     [[maybe_unused]] double kc_64 = 512.0, kc_m1_64 = -1.0 / 512.0, kc_magic = 6755399441055744.0 + 512.0;
@@ -632,9 +632,10 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             __builtin_amdgcn_sched_barrier(0);
             // soft value = |S_2|^2 - |S_1|^2 (ref :264-268): the difference of the two energies like the reference, each from its
             // own correlation. (Where the reference's tones tie exactly - a real or imaginary Z - so do these: the two
-            // correlations' accumulation chains are mirror images.)
-            const double en1 = row_bcast<0>(acc0, en), en2 = row_bcast<1>(acc1, en);
-            const double soft = en2 - en1;
+            // correlations' accumulation chains are mirror images.) Two instructions: |S_2|^2 handed out by one DPP move, then
+            // soft += |S_1|^2 * -1.0 by one v_fmac_f64_dpp whose first source is the row's lane 0 (the first instruction of the
+            // block below). The product with -1.0 is exact and the sum is rounded once: en2 - en1 bit for bit, a tie gives +0.
+            double soft = row_bcast<1>(acc1, en);
             __builtin_amdgcn_sched_barrier(0);
             // The dominant tone's early / late pair moves to t = 2, 3, then one hand-out each; tone 1 iff e1 > e2 (ref :272 / :291;
             // a tie gives +0: tone 2). Shift and select are ONE instruction per word: v_cndmask_b32_dpp takes its first source
@@ -643,13 +644,15 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             // it depends on); en was written seven instructions earlier.
             double P3o, P4o;
             int sel_lo, sel_hi;
-            asm("v_cmp_gt_f64 vcc, 0, %[soft]\n\t"
+            asm(
+                "v_fmac_f64_dpp %[soft], %[en], %[m1] row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
+                "v_cmp_gt_f64 vcc, 0, %[soft]\n\t"
                 "v_mov_b64_dpp %[p3], %[v] row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
                 "v_mov_b64_dpp %[p4], %[v] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
                 "v_cndmask_b32_dpp %[sl], %[el], %[el], vcc row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
                 "v_cndmask_b32_dpp %[sh], %[eh], %[eh], vcc row_shl:2 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                : [p3] "=&v"(P3o), [p4] "=&v"(P4o), [sl] "=&v"(sel_lo), [sh] "=&v"(sel_hi)
-                : [soft] "v"(soft), [v] "v"(v), [el] "v"(dlo(en)), [eh] "v"(dhi(en))
+                : [p3] "=&v"(P3o), [p4] "=&v"(P4o), [sl] "=&v"(sel_lo), [sh] "=&v"(sel_hi), [soft] "+v"(soft)
+                : [v] "v"(v), [en] "v"(en), [m1] "v"(kc_m1), [el] "v"(dlo(en)), [eh] "v"(dhi(en))
                 : "vcc");
             const double seln = mkd(sel_hi, sel_lo);
             __builtin_amdgcn_sched_barrier(0);
@@ -662,6 +665,11 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             [[maybe_unused]] double pd = 0.0, cx = 0, cy = 0, sum = 1.0, dif = 0, dm_ = 1.0, ee, el;
             [[maybe_unused]] uint64_t zmask = 0;
             if constexpr (!kFirst) {
+                // hand-outs of the two energies, HERE: they are the wait state between the sign insert above and the first fma
+                // that reads nsg (an s_nop otherwise), and the pad hipcc puts behind the select block (soft is one of its
+                // outputs, the sign insert reads it) and that insert are the two wait states their own DPP reads of seln need
+                ee = row_bcast<2>(sq, seln); el = row_bcast<3>(shv, seln);
+                __builtin_amdgcn_sched_barrier(0);
                 // phase detector operands: dom * conj(prev) (ref :299), prev advanced by one symbol's LO rotation
                 // (header: P_t = S_t (-/+ j) X[40]); sg picks the dominant tone's combination of the shared sums
                 const double dr = fma(sg, P2o, P1o), di = fma(-sg, P4o, P3o);
@@ -669,8 +677,6 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 const double ar = fma(dr, prs, di * pis), ai = fma(di, prs, -(dr * pis));
                 cy = fma(ar, prv.x40c, ai * prv.x40s);              // Im z
                 cx = fma(ar, prv.x40s, -(ai * prv.x40c));           // Re z
-                __builtin_amdgcn_sched_barrier(0);
-                ee = row_bcast<2>(sq, seln); el = row_bcast<3>(shv, seln);   // hand-outs of the two energies
                 __builtin_amdgcn_sched_barrier(0);
                 // cx < 0: pi - pd, as a +/-1 multiplier and a 0/pi offset built from the sign bit
                 sx = mkd((dhi(cx) & (int)0x80000000) | (dhi(sx) & 0x7fffffff), dlo(sx));
@@ -681,13 +687,14 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 dm_ = sum + kc_tiny;
                 // One wave per workgroup (WPB == 1): the silence test's compare HERE, its branch 35 instructions later - a v_cmp
                 // whose mask a scalar branch reads in the next instruction costs a lone wave a VALU -> SALU round trip (798 ->
-                // 774 cycles per symbol on clean 60-frame streams, 779 -> 774 on the bench workload, although this form issues
-                // one instruction more, an s_cmp on the mask). Four waves per workgroup keep the adjacent pair: with the CU's
-                // other three SIMDs busy the early form measured 850 cycles per symbol against 804 (1024 streams).
-                if constexpr (WPB == 1) {
-                    zmask = __builtin_amdgcn_fcmp(sum, 0.0, 1 /*FCMP_OEQ*/);
-                    asm volatile("" : "+s"(zmask));
-                }
+                // 774 cycles per symbol on clean 60-frame streams, 779 -> 774 on the bench workload). The mask is left to hipcc
+                // as a plain value: the compare lands here (the sched_barriers keep it in this stretch), writes vcc, and the
+                // branch is one s_cbranch_vccnz - nothing between the two touches vcc (the tone select stands in front), and
+                // if that ever changes hipcc copies the mask and scripts/experiments/trip_census.py shows the copy. (Pinned
+                // through an opaque SGPR pair it cost an s_cmp per symbol: 8.2 cycles.) Four waves per workgroup keep the
+                // adjacent pair: with the CU's other three SIMDs busy the early form measured 850 cycles per symbol against
+                // 804 (1024 streams).
+                if constexpr (WPB == 1) zmask = __builtin_amdgcn_fcmp(sum, 0.0, 1 /*FCMP_OEQ*/);
             } else {
                 ee = row_bcast<2>(sq, seln); el = row_bcast<3>(shv, seln);
             }
@@ -813,8 +820,8 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 // slower at 16 mod 32. tools/align_vop3.py reports both addresses at every build and says how many to add when
                 // code in front of here has moved one; the two nests carry their own counts. The fp64 ring only: with two waves per CU, 512 streams on the int16 ring,
                 // a loop so placed measured 1.2 % slower than where hipcc happened to put it. NOTEBOOK.md, Round 13.)
-                if constexpr (F64 && decltype(steady)::tf_free) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
-                else if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                if constexpr (F64 && decltype(steady)::tf_free) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                else if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
                 while (more >= 4u) {
                     for (uint32_t quads = more >> 2; quads != 0u; --quads) {
                         sym(steady, Slot0{}, qq, qp);

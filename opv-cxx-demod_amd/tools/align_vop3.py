@@ -185,8 +185,8 @@ MARK = "opv_symbol_loop_top"
 
 
 def symbol_loop_tops(ins):
-    """addresses of the innermost loops of a function that hold four symbol bodies (120 v_fmac_f64_dpp between a label and the
-    backward branch to it)"""
+    """addresses of the innermost loops of a function that hold four symbol bodies (124 v_fmac_f64_dpp between a label and the
+    backward branch to it: per symbol the thirty of the window sums and the one that forms the soft value)"""
     index = {x[0]: i for i, x in enumerate(ins)}
     cands = []
     for i, x in enumerate(ins):
@@ -194,7 +194,7 @@ def symbol_loop_tops(ins):
             continue
         simm = (int(x[3].split()[0]) ^ 0x8000) - 0x8000
         tgt = x[0] + 4 + 4 * simm
-        if tgt < x[0] and tgt in index and sum(1 for y in ins[index[tgt]:i] if y[2].startswith("v_fmac_f64_dpp")) == 120:
+        if tgt < x[0] and tgt in index and sum(1 for y in ins[index[tgt]:i] if y[2].startswith("v_fmac_f64_dpp")) == 124:
             cands.append((x[0] - tgt, tgt, x[0]))
     tops = []
     for _, tgt, end in sorted(cands):

@@ -1,5 +1,5 @@
-"""dev: instruction census of the steady-state symbol loop (the backward branch that spans 120 v_fmac_f64_dpp = four
-symbols) of the one-wave front-end kernels, read from the aligned device assembly the library is built from."""
+"""dev: instruction census of the steady-state symbol loop (the backward branch that spans 124 v_fmac_f64_dpp = four
+symbols of 31) of the one-wave front-end kernels, read from the aligned device assembly the library is built from."""
 import collections
 import re
 import sys
@@ -20,7 +20,7 @@ for fn in sys.argv[1:] or ("k_msk_frontend_rb", "k_msk_frontend_rd"):
         m = re.match(r"\s+s_cbranch_\w+\s+(\.LBB\d+_\d+)", L[i])
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             a = labels[m.group(1)]
-            if sum(1 for k in range(a, i) if "v_fmac_f64_dpp" in L[k]) == 120:
+            if sum(1 for k in range(a, i) if "v_fmac_f64_dpp" in L[k]) == 124:
                 best = (a, i)
     a, b = best
     body = [l.strip().split(";")[0].strip() for l in L[a:b + 1] if l.strip() and not l.strip().startswith(";") and not re.match(r"^\.L", l.strip())]

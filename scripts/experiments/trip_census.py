@@ -1,8 +1,8 @@
 """dev: census of the steady-state symbol loops of the one-wave front-end kernels, read from the device assembly the library is
 built from (default: build/k_frontend.al.s; another file as first argument). Every innermost loop (a label and the conditional
-backward branch to it, no other such loop between them) that holds N x 30 v_fmac_f64_dpp is one trip loop of N symbols: its instruction
+backward branch to it, no other such loop between them) that holds N x 31 v_fmac_f64_dpp (thirty for the window sums, one for the soft value) is one trip loop of N symbols: its instruction
 count per symbol, s_nop, v_max_f64 / v_min_f64 (two per symbol are the AFC clamp, two more the timing clamp where the nest keeps
-it), backward branches; and per kernel the VGPR count and scratch. (loop_census.py takes the last loop with 120 FMACs, which
+it), backward branches; and per kernel the VGPR count and scratch. (loop_census.py takes the last loop with 124 FMACs, which
 since the batches of whole trips is the batch loop around them.)"""
 import collections
 import re
@@ -30,8 +30,22 @@ for fn in ("k_msk_frontend_rb", "k_msk_frontend_rb_wg4"):
         body = [l.strip().split(";")[0].strip() for l in L[a:b + 1] if l.strip() and not l.strip().startswith(";") and not re.match(r"^\.L", l.strip())]
         c = collections.Counter(x.split()[0].replace("_e32", "").replace("_e64", "") for x in body)
         n = c["v_fmac_f64_dpp"]
-        if n == 0 or n % 30:
+        if n == 0 or n % 31:
             continue
-        n //= 30
+        n //= 31
         print(f"  loop at line {a + 1}: {n} symbols, {len(body)} instructions = {len(body) / n:.2f} per symbol; s_nop {c['s_nop']}, "
               f"v_max_f64 {c['v_max_f64']}, v_min_f64 {c['v_min_f64']}, backward branches {sum(1 for a2, b2 in back if a <= a2 and b2 <= b)}")
+        # the silence test: a v_cmp_eq_f64 and the forward branch that reads its mask. Where the mask is vcc, what stands between
+        # the two must neither write vcc nor copy it
+        cmps = [i for i, x in enumerate(body) if x.startswith("v_cmp_eq_f64")]
+        on_vcc = [i for i in cmps if re.match(r"v_cmp_eq_f64\w*\s+vcc\b", body[i])]
+        gaps, touched = [], 0
+        for i in on_vcc:
+            j = next((k for k in range(i + 1, len(body)) if body[k].startswith("s_cbranch_vcc")), None)
+            if j is None:
+                touched += 1
+                continue
+            gaps.append(j - i - 1)
+            touched += sum(1 for x in body[i + 1:j] if re.search(r"\bvcc\b", x))
+        print(f"    silence test: {len(cmps)} compares, {len(on_vcc)} on vcc with an s_cbranch_vcc* {gaps} instructions later, "
+              f"{touched} instructions between that name vcc, s_cmp on the mask {c['s_cmp_eq_u64'] + c['s_cmp_lg_u64']}")

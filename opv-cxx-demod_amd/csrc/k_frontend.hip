@@ -36,10 +36,11 @@
 //     v_fmac_f64_dpp acc, src0 row_newbcast:n, src1 lets a row of 16 lanes form 16 differently weighted sums of its
 //     samples; with 15 samples per row, 2 x 15 FMACs give ALL window sums of the symbol (on-time / early / late
 //     correlations of both tones + the on-time sums P1..P4) as row partials in lane t = lane & 15, one all-reduce over
-//     the four rows completes them, v_mov_b64_dpp row_newbcast hands out what the loop filters need, the energies and
+//     the four rows (two independent v_mfma_f64_4x4x4_4b_f64 with 0/1 row selectors and an add: the fp64 matrix pipe contracts over
+//     lane bits 4-5, which is exactly the row index; bit for bit the two permlane swaps it replaced) completes them, v_mov_b64_dpp row_newbcast hands out what the loop filters need, the energies and
 //     the dominant-tone select (shift and select in one v_cndmask_b32_dpp per word) are lane-parallel. The four-symbol loop
-//     holds 138.25 instructions per symbol on the fp64 ring (140.25 in a call that keeps the timing clamp), 146.25 / 148.25 on the
-//     int16 ring, 147.25 / 149.25 with four waves per workgroup (scripts/experiments/trip_census.py on the device assembly).
+//     holds 133.75 instructions per symbol on the fp64 ring (135.75 in a call that keeps the timing clamp), 141.75 / 143.75 on the
+//     int16 ring, 142.75 / 144.75 with four waves per workgroup (scripts/experiments/trip_census.py on the device assembly).
 //     The scalar loop filters run redundantly on all lanes (wave-uniform, no divergence).
 //   * A LONE wave on a SIMD issues one instruction of ANY kind (VALU, SALU, LDS, s_nop, branch)
 //     every ~4.7 cycles and gains nothing from independent chains (scripts/microbench): the
@@ -62,10 +63,10 @@
 //     int16 ring (ds_read2_b32) and widen in registers. While a stream can have a CU to itself
 //     (no more streams than CUs) the launch has a second, helper wave that widens the IQ into an
 //     fp64 ring instead, and the symbol body reads its interpolation operands ready-made
-//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, round 13 - the batch boundary below - 652.5, profiles/r13_bench_ab.txt; now 631.6 = 9.63 GS/s on 64 streams, profiles/symbol_slots_bench_ab.txt).
+//     (f64_ring_helper: 8 instructions per symbol fewer; round 8 measured 687 against 750 cycles per symbol, round 10 - this body - 663, round 13 - the batch boundary below - 652.5, profiles/r13_bench_ab.txt; then 631.6, profiles/symbol_slots_bench_ab.txt; with the cross-row sums on the matrix pipe and two soft values per store 621.7, profiles/rowsum_mfma_step0.txt).
 //   * fp64 everywhere: the 1e-5 soft contract does not need it, bit-exact quantiser/sync
-//     decisions on noisy input do. No MFMA: the per-symbol contraction is
-//     3x4x60 with a serial dependence between symbols.
+//     decisions on noisy input do. No MFMA for the correlations: the per-symbol
+//     contraction is 3x4x60 with a serial dependence between symbols (the matrix pipe only adds the four row partials).
 //
 // Roofline: HBM-bound on paper (4 B/sample in, 8 B/symbol out => 4.2 B/sample) but actually
 // issue-bound by the per-symbol feedback recurrence; see DESIGN.md and profiles/.
@@ -119,19 +120,10 @@ typedef __attribute__((address_space(3))) unsigned char lbyte;
 typedef __attribute__((address_space(3))) int lint;
 typedef __attribute__((address_space(3))) double ldouble;
 typedef __attribute__((address_space(3))) d2v ld2v;
+typedef __attribute__((address_space(1), aligned(8))) d2v gd2v8;   // two soft values in one store: 8-byte aligned, 0 or 8 mod 16
+// a symbol's place in its loop trip; `paired`: the trip of four, whose symbols log their soft values two per 16-byte store
+template <uint32_t K, bool PAIRED> struct SlotTag { static constexpr uint32_t value = K; static constexpr bool paired = PAIRED; };
 
-// A-values end in lanes 0..31, B-values in lanes 32..63: returns A[l]+A[l+32] | B[l-32]+B[l]
-__device__ inline double swap32_add(double a, double b) {
-    auto lo = __builtin_amdgcn_permlane32_swap((unsigned)dlo(a), (unsigned)dlo(b), false, false);
-    auto hi = __builtin_amdgcn_permlane32_swap((unsigned)dhi(a), (unsigned)dhi(b), false, false);
-    return mkd((int)hi[0], (int)lo[0]) + mkd((int)hi[1], (int)lo[1]);
-}
-// rows of 16: even rows get A[l]+A[l+16], odd rows B[l-16]+B[l]
-__device__ inline double swap16_add(double a, double b) {
-    auto lo = __builtin_amdgcn_permlane16_swap((unsigned)dlo(a), (unsigned)dlo(b), false, false);
-    auto hi = __builtin_amdgcn_permlane16_swap((unsigned)dhi(a), (unsigned)dhi(b), false, false);
-    return mkd((int)hi[0], (int)lo[0]) + mkd((int)hi[1], (int)lo[1]);
-}
 // v_mov_b64_dpp row_newbcast:N - lane N of every row of 16 to all lanes of that row (the one DPP control 64-bit operations
 // take). Through the builtin, so that hipcc sees the DPP hazards and schedules around them; every lane is written, `old`
 // only names the register: pass a dead value (a zero or an undefined one would cost a move or an s_nop).
@@ -336,6 +328,17 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
     kc_tfmax = __builtin_canonicalize(kc_tfmax);
     double sx = 1.0, nsg = 1.0;          // +/-1.0 rebuilt per symbol by rewriting the high word only
     asm volatile("" : "+v"(sx), "+v"(nsg));
+    // Selectors of the cross-row sums (symbol_r): v_mfma_f64_4x4x4_4b_f64 takes A's contraction index k from lane bits 4-5, B's k
+    // from lane bits 4-5 and its column and block from lane bits 0-3, and writes D's row to lane bits 4-5, column and block to
+    // lane bits 0-3 (scripts/microbench/mfma_rows.hip, part 1). With A = sel[k] in every row and B = v, every lane 16 i + t
+    // receives sum_k sel[k] * v[16 k + t]: selE picks rows 0 and 2, selO rows 1 and 3.
+    // The bits are those of the swap tree (r0 + r2) + (r1 + r3): each MFMA adds two products 1.0 * r, which are exact, and two
+    // exact zeros onto +0, so whatever the order inside the instruction, and with or without rounding between its steps, it
+    // returns fl(r0 + r2) resp. fl(r1 + r3), and one v_add_f64 adds the two. A row partial is never -0 (both accumulators
+    // start at +0 and a sum of products that cancels is +0), so a zero sum is +0 on both paths; with int16 input the partials
+    // are finite and their non-zero values far from denormal (the smallest is about 1e-18), so 0 * r is a zero and never a NaN.
+    double selE = ((lane >> 4) & 1) ? 0.0 : 1.0, selO = ((lane >> 4) & 1) ? 1.0 : 0.0;
+    asm volatile("" : "+v"(selE), "+v"(selO));
 
     // ---- carry ---------------------------------------------------------------------------
     double fo = st.freq_offset, tf = st.timing_freq, mu = st.mu;
@@ -549,17 +552,18 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
         // lets the 16 lanes of a row form 16 differently weighted sums of the row's samples, one broadcast step per
         // sample and component: 2 x 15 full-rate FMACs produce ALL twelve window sums of the symbol (on-time P1..P4, early
         // and late correlations of BOTH tones) as row partials in lanes t = lane & 15, with no product instructions, no
-        // dominant-tone dependence and no v_readlane. One all-reduce over the four rows (two permlane swaps of the value
-        // with a copy of itself) completes them; v_mov_b64_dpp row_newbcast hands the numbers the loop filters need to
+        // dominant-tone dependence and no v_readlane. One all-reduce over the four rows (two v_mfma_f64_4x4x4 that each sum
+        // two rows, and an add) completes them; v_mov_b64_dpp row_newbcast hands the numbers the loop filters need to
         // every lane (one instruction per double instead of two v_readlane + the SGPR-operand restrictions), and the four
         // early / late energies are formed lane-parallel (square, row_ror:8, add: Re at t, Im at t + 8), the dominant
         // tone's pair selected lane-parallel (row_shl:2), before two of them are handed out. The phase detector's angle
         // comes without the octant fix-up (opv_atan2.h: opv_atan2_q3r, 1025-row table of pi/4 + atan, cubics in the argument itself; round 2: 257 rows, degree 5).
         // Scheduling notes: hipcc counts an asm block as no wait state and pads behind one, so neighbouring pieces are ONE block
-        // (the AFC clamp with the LO factor, the thirty FMACs with the sum and its copy, the tone compare with the P3 / P4
-        // hand-outs and the selects), and the wait states DPP reads / permlane swaps need behind a VALU write are filled with
-        // useful instructions where there are any: two s_nop per symbol remain (in front of the second swap, nothing
-        // independent is left; behind the select block). (scripts/microbench/dpp64.hip has the instruction costs.)
+        // (the AFC clamp with the LO factor, the thirty FMACs with the sum and the all-reduce, the tone compare with the P3 / P4
+        // hand-outs and the selects), and the wait states DPP reads / MFMAs need behind a VALU write are filled with
+        // useful instructions where there are any: three s_nop per symbol remain (two behind the MFMA pair, nothing
+        // independent is cheap there; one behind the select block). (scripts/microbench/dpp64.hip has the instruction costs.)
+        [[maybe_unused]] double soft_held = 0.0;               // the soft value of a trip's slot 0 / 2 until slot 1 / 3 stores the pair
         auto symbol_r = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) {
             constexpr bool kFirst = decltype(tag)::first;
             constexpr bool kWide = decltype(tag)::wide;
@@ -594,29 +598,31 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             double acc0, acc1, v, t;
 #define OPV_RB(N) "v_fmac_f64_dpp %[a0], %[zr], %[r" #N "] row_newbcast:" #N " row_mask:0xf bank_mask:0xf\n\t" \
                   "v_fmac_f64_dpp %[a1], %[zi], %[i" #N "] row_newbcast:" #N " row_mask:0xf bank_mask:0xf\n\t"
-            // (one block: the sum of the two accumulators and the copy the all-reduce swaps with behind the thirty FMACs)
+            // One block with the all-reduce over the four rows behind the thirty FMACs: the sum of the two accumulators, then two
+            // independent v_mfma_f64_4x4x4 with the row selectors (at `selE`: why the bits are the swap tree's (r0 + r2) + (r1 + r3))
+            // and one add. The X[40] hand-over (the spare lane 15 of every row carries sample 50: two DPP moves, equal in every
+            // lane) stands IN FRONT of the pair, as the two wait states an MFMA needs behind the VALU write of its operand: behind
+            // the pair, in the six wait states its result needs, the same two moves cost 20 cycles (mfma_rows.hip; in the loop 13
+            // cycles per symbol slower than the swaps). Those six are s_nop 3 + s_nop 1 and not one s_nop 5: a lone 4-byte
+            // instruction flips the parity of the eleven 8-byte instructions behind it, which tools/align_vop3.py has nothing
+            // to widen against (11 cycles per symbol, profiles/rowsum_mfma_step0.txt).
             asm("v_mov_b64 %[a0], 0\n\tv_mov_b64 %[a1], 0\n\t" OPV_RB(0) OPV_RB(1) OPV_RB(2) OPV_RB(3) OPV_RB(4) OPV_RB(5) OPV_RB(6) OPV_RB(7)
                 OPV_RB(8) OPV_RB(9) OPV_RB(10) OPV_RB(11) OPV_RB(12) OPV_RB(13) OPV_RB(14)
-                "v_add_f64 %[v], %[a0], %[a1]\n\t"
-                "v_mov_b64 %[t], %[v]"
-                : [a0] "=&v"(acc0), [a1] "=&v"(acc1), [v] "=&v"(v), [t] "=&v"(t)
+                "v_add_f64 %[t], %[a0], %[a1]\n\t"
+                "v_mov_b64_dpp %[x40c], %[xc] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
+                "v_mov_b64_dpp %[x40s], %[xs] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
+                "v_mfma_f64_4x4x4_4b_f64 %[a0], %[selE], %[t], 0\n\t"
+                "v_mfma_f64_4x4x4_4b_f64 %[a1], %[selO], %[t], 0\n\t"
+                "s_nop 3\n\ts_nop 1\n\t"
+                "v_add_f64 %[v], %[a0], %[a1]"
+                : [a0] "=&v"(acc0), [a1] "=&v"(acc1), [v] "=&v"(v), [t] "=&v"(t), [x40c] "=&v"(cur.x40c), [x40s] "=&v"(cur.x40s)
                 : [zr] "v"(zr), [zi] "v"(zi), [r0] "v"(wr[0]), [i0] "v"(wi[0]), [r1] "v"(wr[1]), [i1] "v"(wi[1]), [r2] "v"(wr[2]), [i2] "v"(wi[2]),
                   [r3] "v"(wr[3]), [i3] "v"(wi[3]), [r4] "v"(wr[4]), [i4] "v"(wi[4]), [r5] "v"(wr[5]), [i5] "v"(wi[5]),
                   [r6] "v"(wr[6]), [i6] "v"(wi[6]), [r7] "v"(wr[7]), [i7] "v"(wi[7]),
                   [r8] "v"(wr[8]), [i8] "v"(wi[8]), [r9] "v"(wr[9]), [i9] "v"(wi[9]), [r10] "v"(wr[10]), [i10] "v"(wi[10]),
                   [r11] "v"(wr[11]), [i11] "v"(wi[11]), [r12] "v"(wr[12]), [i12] "v"(wi[12]), [r13] "v"(wr[13]), [i13] "v"(wi[13]),
-                  [r14] "v"(wr[14]), [i14] "v"(wi[14]));
+                  [r14] "v"(wr[14]), [i14] "v"(wi[14]), [xc] "v"(xc), [xs] "v"(xs), [selE] "v"(selE), [selO] "v"(selO));
 #undef OPV_RB
-            __builtin_amdgcn_sched_barrier(0);
-            // ---- all-reduce over the four rows; the X[40] hand-over (the spare lane 15 of every row carries sample 50: two
-            // DPP moves, equal in every lane) fills the two wait states a swap needs behind the copy
-            cur.x40c = row_bcast<15>(lr, xc);                       // (`old` operands: dead temporaries)
-            cur.x40s = row_bcast<15>(li, xs);
-            __builtin_amdgcn_sched_barrier(0);
-            v = swap32_add(v, t);
-            asm("v_mov_b64 %0, %1" : "=v"(t) : "v"(v));
-            __builtin_amdgcn_sched_barrier(0);
-            v = swap16_add(v, t);                                   // (nothing independent is left for this swap's wait states: one s_nop 1)
             __builtin_amdgcn_sched_barrier(0);
             double fo_sum_next = fo_sum + fo;                       // sum of the fo every symbol USED
             asm volatile("" : "+v"(fo_sum_next));
@@ -743,7 +749,15 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             __builtin_amdgcn_sched_barrier(0);
             fetch_read();                                             // next symbol's taps requested as soon as their address exists
             __builtin_amdgcn_sched_barrier(0);
+            if constexpr (decltype(slot)::paired) {
+                if constexpr ((kSlot & 1u) == 0u) soft_held = soft;
+                else *(gd2v8*)(soft_base + soft_v + 16u * (kSlot / 2u)) = d2v{soft_held, soft};
+            } else
             *(gdouble*)(soft_base + soft_v + 8u * kSlot) = soft;      // (the slot's 8 kSlot is the store's immediate offset)
+            // (a trip of four: slots 0 and 2 hold their value - a register, no instruction - and slots 1 and 3 store both as one
+            // global_store_dwordx4 at soft_v + 16 (kSlot / 2). A batch of whole trips does not wrap the soft ring, so the pair is
+            // contiguous; every trip is run whole, so nothing is held at any way out of the loop; the silence block of slot 1
+            // reads and writes other registers. In the loop 3.7 cycles per symbol, profiles/rowsum_mfma_step0.txt.)
             if constexpr (!kFirst) {
                 const double pd_off = fma(-sx, kc_halfpi, kc_halfpi);
                 __builtin_amdgcn_sched_barrier(0);
@@ -773,10 +787,12 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
             asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3" : "=&v"(fo) : "v"(fo_raw), "v"(kc_nfomax), "v"(kc_fomax));
             fo_raw = fo;
         };
-        using Slot0 = std::integral_constant<uint32_t, 0>;
-        using Slot1 = std::integral_constant<uint32_t, 1>;
-        using Slot2 = std::integral_constant<uint32_t, 2>;
-        using Slot3 = std::integral_constant<uint32_t, 3>;
+        using Slot0 = SlotTag<0, false>;
+        using Slot1 = SlotTag<1, false>;
+        using Trip0 = SlotTag<0, true>;
+        using Trip1 = SlotTag<1, true>;
+        using Trip2 = SlotTag<2, true>;
+        using Trip3 = SlotTag<3, true>;
         auto sym = [&](auto tag, auto slot, PrevSums& cur, const PrevSums& prv) { symbol_r(tag, slot, cur, prv); };
 
         // The call's symbols, from the first one through the batch loop, in two instantiations chosen once per call (below):
@@ -820,14 +836,14 @@ __device__ __forceinline__ void msk_frontend_body(OpvStream* __restrict__ stream
                 // slower at 16 mod 32. tools/align_vop3.py reports both addresses at every build and says how many to add when
                 // code in front of here has moved one; the two nests carry their own counts. The fp64 ring only: with two waves per CU, 512 streams on the int16 ring,
                 // a loop so placed measured 1.2 % slower than where hipcc happened to put it. NOTEBOOK.md, Round 13.)
-                if constexpr (F64 && decltype(steady)::tf_free) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
-                else if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                if constexpr (F64 && decltype(steady)::tf_free) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0\n\ts_nop 0");
+                else if constexpr (F64) asm volatile("; opv_symbol_loop_top\n\ts_nop 0\n\ts_nop 0");
                 while (more >= 4u) {
                     for (uint32_t quads = more >> 2; quads != 0u; --quads) {
-                        sym(steady, Slot0{}, qq, qp);
-                        sym(steady, Slot1{}, qp, qq);
-                        sym(steady, Slot2{}, qq, qp);
-                        sym(steady, Slot3{}, qp, qq);
+                        sym(steady, Trip0{}, qq, qp);
+                        sym(steady, Trip1{}, qp, qq);
+                        sym(steady, Trip2{}, qq, qp);
+                        sym(steady, Trip3{}, qp, qq);
                         soft_v += 32u;
                     }
                     more = uni(housekeeping(pos, more & ~3u));   // (0 once the helper is lost)

@@ -35,6 +35,11 @@ for fn in ("k_msk_frontend_rb", "k_msk_frontend_rb_wg4"):
         n //= 31
         print(f"  loop at line {a + 1}: {n} symbols, {len(body)} instructions = {len(body) / n:.2f} per symbol; s_nop {c['s_nop']}, "
               f"v_max_f64 {c['v_max_f64']}, v_min_f64 {c['v_min_f64']}, backward branches {sum(1 for a2, b2 in back if a <= a2 and b2 <= b)}")
+        # the cross-row sums (two v_mfma_f64_4x4x4 per symbol, no permlane swap) and the soft log's stores (a trip of four: two
+        # global_store_dwordx4; a remainder loop: one global_store_dwordx2 per symbol); AGPR traffic would be a spill
+        print(f"    v_mfma_f64 {sum(v for k, v in c.items() if k.startswith('v_mfma_f64'))}, permlane swaps {sum(v for k, v in c.items() if k.startswith('v_permlane'))}, "
+              f"global_store_dwordx2 {c['global_store_dwordx2']}, global_store_dwordx4 {c['global_store_dwordx4']}, "
+              f"v_accvgpr {sum(v for k, v in c.items() if k.startswith('v_accvgpr'))}, forward branches {sum(1 for x in body if x.startswith(('s_cbranch', 's_branch'))) - 1}")
         # the silence test: a v_cmp_eq_f64 and the forward branch that reads its mask. Where the mask is vcc, what stands between
         # the two must neither write vcc nor copy it
         cmps = [i for i, x in enumerate(body) if x.startswith("v_cmp_eq_f64")]

@@ -7,15 +7,15 @@
 // dominant tone's correlation drives a second-order loop with the phase error Im / |.| (:512-530) and the AFC with
 // arg(dom conj(prev)) (:535-543).
 //
-// PARITY STATUS: prefix only, by the nature of the reference. Its loop does not lock (on the reference's own clean
-// loopback the AFC runs to the +/-2000 Hz clamp and 4 garbage frames come out of 10) and its trajectory is chaotic:
-// 1e-15 rad on the initial carrier phase grows to 3e-13 after 2000 symbols and to O(1) after ~12 000
-// (tests/test_oracle_golden.py::test_coherent_loop_is_chaotic). This kernel forms the per-sample phases in closed
-// form (phase + i * increment instead of i sequential additions) and uses the device's sincos / atan2 / hypot, i.e.
-// it differs from the reference in the last place of those - and therefore follows the reference's soft symbols to
-// <= 1e-9 for the first ~2000 symbols and departs from them, like ANY implementation that is not the reference's own
-// libm, within a few frames (tests/test_gpu_parity.py::test_coherent_prefix_parity). It exists so that `-c` runs;
-// it is not tuned (a stream is serial, ~300 issued instructions per symbol).
+// PARITY STATUS: held to the oracle inside a DERIVED envelope as far as a MEASURED gain rule reaches (tests/coherent_inputs.py,
+// tests/test_gpu_coherent.py; the oracle == the compiled reference on every case, tests/test_coherent_host.py). The rule: 1e-9 rad on
+// the initial carrier phase, handed on with a gain g(s) <= 64 up to the prefix P. The envelope: E(s) = max(1, g) [(s + 1) 80 2^-51 +
+// 2^-40] M, M = 80 sqrt(2) max|IQ|: this kernel forms the per-sample phases in closed form (phase + i * increment, ONE wrap per symbol)
+// where the reference adds 40 times, and uses the device's sincos / atan2 / hypot. KEEP that order of operations: E assumes it.
+// Measured on MI355X (profiles/coherent_parity.txt): whole 21 780-symbol captures at pll_bw 1 Hz with afc_alpha 0 / 0.001 / 0.05 (the
+// AFC on both +/-2000 Hz clamps thousands of times): err / E <= 0.024; loop_freq on +/-0.1 at pll_bw 5000, silence (exact +0.0), 1 - 70
+// streams per context, en1 == en2: inside E, clamped values ==. At the default gains the loop is chaotic (1e-15 rad -> O(1) within
+// ~12 000 symbols): P = 1546 - 5890 symbols there, err / E <= 0.029. Not tuned (a stream is serial, ~300 issued instructions per symbol).
 #include <hip/hip_runtime.h>
 #include <math.h>
 

@@ -8,7 +8,7 @@ from functools import partial
 
 import numpy as np
 
-from oracle_lib import CHUNK_SAMPLES as CHUNK, accidents, impair, resample_clock
+from oracle_lib import CHUNK_SAMPLES as CHUNK, accidents, format_events, impair, resample_clock
 from soak_inputs import host_workers, oracle_receive_job, pathological_captures
 
 LONG = "clamp+2600"     # the 30-frame capture of the hostile set: the one that keeps a push test running for >= 12 rounds
@@ -50,12 +50,17 @@ def gapped_capture(oracle, iq10, nudge=True):
 
 
 # ------------------------------------------------------------------ the hostile set (tests/test_gpu_mapping_matrix.py)
+def slip_capture(iq10, ppm):
+    """the 10-frame capture as an ADC `ppm` parts per million fast took it, 300 Hz low, 20 dB (test_timing_loop_slipping's recipe)"""
+    return impair(resample_clock(iq10, ppm), amp=5000.0, f0_hz=-300.0, ebn0_db=20.0, seed=9)
+
+
 def hostile_captures(oracle):
     """[(name, class, int16 IQ)]; class: "full" (check_stream), "patho" / "gap" (1e-8 + chunk log), "tie" (un-nudged gaps)"""
     iq10 = oracle.modulate(oracle.bert_frames(10))
     caps = [(f"patho{k}", "patho", x) for k, x in enumerate(pathological_captures(iq10))]
     for ppm in (-25000.0, -3000.0, 3000.0, 25000.0):                         # test_timing_loop_slipping's recipe
-        caps.append((f"slip{ppm:+.0f}", "full", impair(resample_clock(iq10, ppm), amp=5000.0, f0_hz=-300.0, ebn0_db=20.0, seed=9)))
+        caps.append((f"slip{ppm:+.0f}", "full", slip_capture(iq10, ppm)))
     rng = np.random.default_rng(20261004)                                     # test_channel_accidents' recipe (its captures 0, 5, 6, 7)
     for k in range(8):
         base = oracle.modulate(oracle.bert_frames(int(rng.integers(6, 12)), "A%d" % k, first=40 * k))
@@ -109,6 +114,32 @@ def receive_pairs(jobs):
     comparison of many captures waits for"""
     with ProcessPoolExecutor(host_workers()) as pool:
         return list(pool.map(receive_pair_job, jobs))
+
+
+# ------------------------------------------------------------------ the oracle == the compiled reference (tests/test_oracle_pinned_live.py, tests/test_coherent_host.py)
+def bits(x):
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
+def same_float(a, b):
+    return bits(np.float64(a).reshape(1))[0] == bits(np.float64(b).reshape(1))[0]
+
+
+def assert_same_receive(a, b, tag=""):
+    """a: Oracle.receive (or soak_inputs.oracle_receive_job), b: Reference.receive of the same input - everything =="""
+    assert a["soft"].shape == b["soft"].shape, f"{tag}: {a['soft'].shape[0]} soft symbols, the reference {b['soft'].shape[0]}"
+    d = np.nonzero(bits(a["soft"]) != bits(b["soft"]))[0]
+    assert d.size == 0, f"{tag}: {d.size} soft symbols differ, the first at {d[0]}: {a['soft'][d[0]]!r} vs {b['soft'][d[0]]!r}"
+    assert np.array_equal(a["frames"], b["frames"]), f"{tag}: decoded bytes differ"
+    assert np.array_equal(a["metrics"], b["metrics"]), f"{tag}: Viterbi metrics differ"
+    assert np.array_equal(a["frame_sym"], b["frame_sym"]), f"{tag}: release symbols differ"
+    assert format_events(a["events"]) == [ln for ln in b["log"].split("\n") if ln.startswith("[")], f"{tag}: tracker lines differ"
+    ca, cb = a["chunks"][:, [0, 1, 3, 4]], b["chunks"][:, [0, 1, 3, 4]]          # (column 2, mu, is NaN on the reference side)
+    assert ca.shape == cb.shape and np.array_equal(bits(ca), bits(cb)), f"{tag}: chunk log differs:\n{ca}\n{cb}"
+    e0, e1 = a["est_offset"], b["est_offset"]
+    assert (np.isnan(e0) and np.isnan(e1)) or e0 == e1, f"{tag}: offset estimate {e0} vs {e1}"
+    assert same_float(a["final_freq_offset"], b["final_freq_offset"]), f"{tag}: {a['final_freq_offset']!r} vs {b['final_freq_offset']!r}"
+    assert a["final_state"] == b["final_state"], tag
 
 
 def assert_set_is_hostile(names, classes, caps, exp_s, exp_b):

@@ -15,9 +15,9 @@ import numpy as np
 import pytest
 
 from amd_lib import load
-from hostile_inputs import (AFC_ALPHA_FLAG, EXTREME_FLAGS, ambiguous, assert_set_is_hostile, extreme_flags_capture, fuzz_captures,
-                            hostile_captures, near_tie_captures, receive_pairs, staged_ties_capture)
-from oracle_lib import Reference, format_events
+from hostile_inputs import (AFC_ALPHA_FLAG, EXTREME_FLAGS, ambiguous, assert_same_receive, assert_set_is_hostile, extreme_flags_capture,
+                            fuzz_captures, hostile_captures, near_tie_captures, receive_pairs, staged_ties_capture)
+from oracle_lib import Reference
 from soak_inputs import decoder_payloads, offset_openings, symmetric_openings, weak_correlation_openings
 
 pytestmark = pytest.mark.skipif(not Reference.available(), reason="oracle/_ref/libopv_ref.so not built")
@@ -31,31 +31,6 @@ HOSTILE_NAMES = [f"patho{k}" for k in range(8)] + ["slip-25000", "slip-3000", "s
 @pytest.fixture(scope="module")
 def ref():
     return Reference()
-
-
-def bits(x):
-    return np.ascontiguousarray(x, np.float64).view(np.uint64)
-
-
-def same_float(a, b):
-    return bits(np.float64(a).reshape(1))[0] == bits(np.float64(b).reshape(1))[0]
-
-
-def assert_same_receive(a, b, tag=""):
-    """a: Oracle.receive (or soak_inputs.oracle_receive_job), b: Reference.receive of the same input - everything =="""
-    assert a["soft"].shape == b["soft"].shape, f"{tag}: {a['soft'].shape[0]} soft symbols, the reference {b['soft'].shape[0]}"
-    d = np.nonzero(bits(a["soft"]) != bits(b["soft"]))[0]
-    assert d.size == 0, f"{tag}: {d.size} soft symbols differ, the first at {d[0]}: {a['soft'][d[0]]!r} vs {b['soft'][d[0]]!r}"
-    assert np.array_equal(a["frames"], b["frames"]), f"{tag}: decoded bytes differ"
-    assert np.array_equal(a["metrics"], b["metrics"]), f"{tag}: Viterbi metrics differ"
-    assert np.array_equal(a["frame_sym"], b["frame_sym"]), f"{tag}: release symbols differ"
-    assert format_events(a["events"]) == [ln for ln in b["log"].split("\n") if ln.startswith("[")], f"{tag}: tracker lines differ"
-    ca, cb = a["chunks"][:, [0, 1, 3, 4]], b["chunks"][:, [0, 1, 3, 4]]          # (column 2, mu, is NaN on the reference side)
-    assert ca.shape == cb.shape and np.array_equal(bits(ca), bits(cb)), f"{tag}: chunk log differs:\n{ca}\n{cb}"
-    e0, e1 = a["est_offset"], b["est_offset"]
-    assert (np.isnan(e0) and np.isnan(e1)) or e0 == e1, f"{tag}: offset estimate {e0} vs {e1}"
-    assert same_float(a["final_freq_offset"], b["final_freq_offset"]), f"{tag}: {a['final_freq_offset']!r} vs {b['final_freq_offset']!r}"
-    assert a["final_state"] == b["final_state"], tag
 
 
 # ------------------------------------------------------------------ 1. the hostile set

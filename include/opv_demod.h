@@ -20,7 +20,8 @@
 extern "C" {
 #endif
 
-#define OPV_ABI_VERSION 7   /* (still 7, additive: + opv_wb_seg_phase / opv_wb_seg_next / opv_wb_retune / opv_wb_segments / opv_wbtx_retune / opv_wbtx_segments (per-channel retune and Doppler ramps: an LO schedule per channel of the four wideband converters);
+#define OPV_ABI_VERSION 7   /* (still 7, additive: + OPV_IQ_*, opv_push_iq_fmt / opv_push_iq_batch_fmt(_async) / opv_wb_push_fmt(_async) / opv_scan_push_fmt / opv_convert_iq_device / opv_iq_convert / opv_iq_sample_bytes (typed IQ pushes: cs8, cu8 and cf32 converted on the device);
+                               still 7, additive: + opv_wb_seg_phase / opv_wb_seg_next / opv_wb_retune / opv_wb_segments / opv_wbtx_retune / opv_wbtx_segments (per-channel retune and Doppler ramps: an LO schedule per channel of the four wideband converters);
                                still 7, additive: + opv_scan_* (wideband scan: an exact probe bank on a wide capture, and the carriers in a row of its powers);
                                still 7, additive: + opv_div_* (receive diversity: the soft symbols of several streams combined per frame);
                                still 7, additive: + opv_wbtxr_plan / opv_wbtxr_outputs / opv_wbtx_create_rational (wideband transmit at any radio rate: an exact rational up-converter bank);
@@ -163,7 +164,8 @@ int opv_create(opv_ctx** out, int n_streams, const opv_cfg* cfg);
  *   OPV_TX_DISTRUST_LIBM      (any value) the device transmit chain takes every symbol's flat-top bits from the host's libm instead of
  *                             the zone rule its one-time probe of sin / cos allows: same samples, slower set-up. The fallback's test uses it.
  *   OPV_PUSH_NO_GATHER        (any value) opv_push_iq_batch(_async) moves pinned blocks with one copy per block instead of one gather
- *                             kernel: same bytes, the path pageable sources take anyway. Its test runs both.
+ *                             kernel: same bytes, the path pageable sources take anyway. Its test runs both. A typed batch
+ *                             (opv_push_iq_batch_fmt) then sends every block through the context's device stage.
  *   OPV_PUSH_GATHER_BLOCKS    (a number > 0) workgroups of that gather kernel (default 32; a measurement knob, results unaffected).
  *   OPV_FRONTEND_INT16_RING   (any value) k_msk_frontend_rb keeps its int16 sample ring at every stream count, instead of the fp64 ring
  *                             a helper wave fills while the context has no more streams than the device has CUs: same results
@@ -409,6 +411,51 @@ long opv_scan_pop(opv_scan* scan, uint64_t* rows, size_t cap_blocks, uint64_t* f
 int opv_scan_reset(opv_scan* scan, uint64_t first_sample);
 long opv_scan_carriers(const uint64_t* row, int n_probes, double f0_hz, double step_hz, double half_width_hz, uint32_t ratio_q8,
                        opv_scan_carrier* out, size_t cap);
+/* ---- typed IQ pushes: cs8, cu8 and cf32 converted on the device ---------------------------------------------------------------
+ * Replaces nothing in the reference, whose contract is int16. Radios deliver other formats (RTL-SDR unsigned 8-bit, HackRF and many
+ * network front-ends signed 8-bit, USRP / SoapySDR float32); a typed push takes the block AS THE RADIO DELIVERED IT, carries it
+ * across PCIe in its own format - an 8-bit capture at half the bytes of int16 - and widens it behind the link, in the kernel that
+ * writes the stream's device buffer (csrc/opv_push.hip: k_push_convert). From there on the samples are int16 like any other:
+ * formats mix freely within one stream, and capacity, compaction, opv_tap_iq and every index count samples, as before.
+ *
+ * The rule per component (I and Q alike), with an int16 result (csrc/opv_iq_format.h is its one definition, host and device):
+ *   format        bytes / sample   source alignment   result
+ *   OPV_IQ_CS16   4                4                  identity (the int16 path itself: the old kernel with the old arguments)
+ *   OPV_IQ_CS8    2                2                  x * 256             (-32768 .. 32512)
+ *   OPV_IQ_CU8    2                2                  (2 u - 255) * 128   (-32640 .. 32640)
+ *   OPV_IQ_CF32   8                4                  see below
+ *   CS8:  a full-scale 8-bit capture is a full-scale 16-bit one, so out_shift and the offset search's power scaling mean what they
+ *         mean today.
+ *   CU8:  the centre is 127.5, exactly, with no DC term.
+ *   CF32: t = x * 32767.0f as ONE fp32 multiplication, round to nearest even; r = rint(t) with ties to even; the result is
+ *         clamp(r, -32767, 32767); NaN gives 0 and +-Inf gives +-32767.
+ *
+ * opv_push_iq_fmt / opv_push_iq_batch_fmt / _async: opv_push_iq / opv_push_iq_batch / _async for blocks of ONE format per call,
+ *   n_samples counted in samples. A block in pinned host memory of this device (aligned for its format, below 2^32 bytes) is read
+ *   in place by the convert kernel; anything else - pageable memory, pinned memory of another device, every block while
+ *   OPV_PUSH_NO_GATHER is set - is copied raw into a grow-only device stage of the context and converted from there by the same
+ *   launch. Results never depend on the route. Refusals are opv_push_iq's (OPV_ESTATE, OPV_ECAPACITY) plus OPV_EINVAL for a format
+ *   that does not exist or a pointer that is not aligned for it; a refused block changes nothing, and in a batch the streams before
+ *   the error have been pushed, as today. The asynchronous form is settled by opv_push_wait like the int16 one.
+ * opv_wb_push_fmt / _async, opv_scan_push_fmt: the block is converted into the object's device stage (a pinned source is read in
+ *   place by the convert kernel, a pageable one copied raw first) and the call continues as opv_wb_push_device / opv_scan_push_device:
+ *   the wide capture crosses PCIe once, in its own format, and the bank kernels are the int16 ones. Refusals as opv_wb_push /
+ *   opv_scan_push (a refused push changes NOTHING), plus the two above.
+ * opv_convert_iq_device: n_samples of `fmt` at d_in (device-visible, aligned for the format) to int16 at d_out (4-byte aligned) on
+ *   the context's stream, asynchronously like opv_channel_device; the ranges must not overlap. CS16 is a device copy.
+ * opv_iq_convert: the rule itself on the host, no device needed; `in` aligned for the format. opv_iq_sample_bytes: 4, 2, 2, 8; 0
+ *   for a format that does not exist. */
+enum { OPV_IQ_CS16 = 0, OPV_IQ_CS8 = 1, OPV_IQ_CU8 = 2, OPV_IQ_CF32 = 3 };
+int opv_push_iq_fmt(opv_ctx* ctx, int stream, int fmt, const void* samples, size_t n_samples);
+int opv_push_iq_batch_fmt(opv_ctx* ctx, int fmt, int count, const int* streams, const void* const* samples, const size_t* n_samples);
+int opv_push_iq_batch_fmt_async(opv_ctx* ctx, int fmt, int count, const int* streams, const void* const* samples,
+                                const size_t* n_samples);
+int opv_wb_push_fmt(opv_wb* wb, int fmt, const void* wide, size_t n_wide);
+int opv_wb_push_fmt_async(opv_wb* wb, int fmt, const void* wide, size_t n_wide);
+int opv_scan_push_fmt(opv_scan* scan, int fmt, const void* wide, size_t n_wide);
+int opv_convert_iq_device(opv_ctx* ctx, int fmt, const void* d_in, int16_t* d_out, size_t n_samples);
+int opv_iq_convert(int fmt, const void* in, int16_t* out, size_t n_samples);
+size_t opv_iq_sample_bytes(int fmt);
 /* EOF on a stream: enables the tail processing of :1088-1113 (streaming) or the single
  * whole-capture demodulate of :1166-1173 (batch) at the next opv_process. */
 int opv_flush(opv_ctx* ctx, int stream);

@@ -189,6 +189,9 @@ struct opv_ctx {
     std::vector<int> search_now;        // streams whose offset search can run in the round being enqueued
     // opv_push_iq_batch: the table of the gather kernel / of the batched compaction, in pinned memory (the kernels read it in place)
     GrowBuf<void, true> bulk_tab;
+    // typed pushes (opv_push_iq_fmt and its kin): the raw copies of blocks k_push_convert cannot read in place (pageable memory,
+    // another device's pinned memory), rewritten under the rule of bulk_tab's pairs half
+    GrowBuf<char> push_stage;
     // opv_push_iq_batch_async: moves enqueued on the copy stream that no host wait has covered yet; opv_process orders its kernels
     // behind push_ev on the device, every other push entry point waits on the host first
     bool push_pending = false;

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/opv_demod.h"
+#include "opv_iq_format.h"
 #include "opv_scan_internal.h"
 #include "opv_scan_rules.h"
 #include "opv_wb_internal.h"
@@ -98,13 +99,17 @@ namespace {
 
 using Src = OpvSrc;
 
-int scan_push(opv_scan* w, const int16_t* iq, size_t n_new, Src kind) {
+// fmt != OPV_IQ_CS16 (a host block in another format): converted into the object's stage on the copy stream, then as a device push
+int scan_push(opv_scan* w, const void* iq, size_t n_new, Src kind, int fmt = OPV_IQ_CS16) {
     if (!w) return opv_int_fail(OPV_EINVAL, "opv_scan_push: null object");
     if (!w->door.shared->ctx_alive) return opv_int_fail(OPV_ESTATE, "opv_scan_push: the object's context has been destroyed");
     if (int r = opv_int_push_begin(w->ctx)) return r;
     if (n_new == 0) return OPV_OK;
     if (!iq) return opv_int_fail(OPV_EINVAL, "opv_scan_push: null IQ pointer");
-    if (((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_scan_push: IQ pointer must be 4-byte aligned");
+    const bool typed = fmt != OPV_IQ_CS16;
+    if (typed && ((uintptr_t)iq & (opv_iq_align_of(fmt) - 1)) != 0)
+        return opv_int_fail(OPV_EINVAL, "opv_scan_push_fmt: the block is not aligned for its format (2 bytes for cs8 / cu8, 4 for cf32)");
+    if (!typed && ((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_scan_push: IQ pointer must be 4-byte aligned");
     if (n_new >= (1ull << 31)) return opv_int_fail(OPV_EINVAL, "opv_scan_push: more than 2^31 - 1 samples in one push");
     if (w->n_total + n_new > (1ull << 63)) return opv_int_fail(OPV_ECAPACITY, "opv_scan_push: more than 2^63 samples");
     // ---- what can refuse the push, before anything is launched or changed: the rows it completes against the ring's free ones
@@ -118,7 +123,13 @@ int scan_push(opv_scan* w, const int16_t* iq, size_t n_new, Src kind) {
     // ---- the source as the device sees it, and the scratch rows (both grow-only: nothing of the object's state changes)
     const int* src = nullptr;
     bool stage = false;
-    if (int r = opv_int_source(iq, n_new, kind, w->door.device, w->door.copy_stream, &w->stage, &src, &stage)) return r;
+    OpvTypedSrc tsrc;
+    if (typed) {
+        if (int r = opv_int_source_fmt(iq, n_new, opv_iq_bytes_of(fmt), w->door.device, w->door.copy_stream, &w->stage, &tsrc)) return r;
+        src = w->stage.d;
+    } else if (int r = opv_int_source((const int16_t*)iq, n_new, kind, w->door.device, w->door.copy_stream, &w->stage, &src, &stage)) {
+        return r;
+    }
     const size_t part_rows = (size_t)(blocks * shape.runs);
     if (w->part_cap < part_rows) {
         HIPCHK(hipStreamSynchronize(w->door.copy_stream));
@@ -129,6 +140,8 @@ int scan_push(opv_scan* w, const int16_t* iq, size_t n_new, Src kind) {
         w->part_cap = part_rows;
     }
     if (stage) HIPCHK(hipMemcpyAsync(w->stage.d, iq, n_new * 4, hipMemcpyHostToDevice, w->door.copy_stream));
+    if (typed)
+        if (int r = opv_int_convert_enqueue(iq, n_new, fmt, tsrc, &w->stage, w->door.copy_stream)) return r;
     // ---- the launches. A push that completes nothing still moves the carry: enough workgroups for that alone
     OpvScanArgs a{};
     a.src = src;
@@ -178,6 +191,10 @@ int scan_live(opv_scan* w, const char* null_text, const char* dead_text) {
 
 extern "C" int opv_scan_push(opv_scan* w, const int16_t* iq_wide, size_t n_wide) { return scan_push(w, iq_wide, n_wide, Src::Host); }
 extern "C" int opv_scan_push_device(opv_scan* w, const int16_t* d_iq_wide, size_t n_wide) { return scan_push(w, d_iq_wide, n_wide, Src::Device); }
+extern "C" int opv_scan_push_fmt(opv_scan* w, int fmt, const void* wide, size_t n_wide) {
+    if (!opv_iq_align_of(fmt)) return opv_int_fail(OPV_EINVAL, "opv_scan_push_fmt: unknown sample format");
+    return scan_push(w, wide, n_wide, Src::Host, fmt);
+}
 
 extern "C" long opv_scan_pop(opv_scan* w, uint64_t* rows, size_t cap_blocks, uint64_t* first_block) {
     if (int r = scan_live(w, "opv_scan_pop: null object", "opv_scan_pop: the object's context has been destroyed")) return r;

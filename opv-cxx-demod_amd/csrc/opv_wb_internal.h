@@ -109,6 +109,53 @@ inline int opv_int_source(const int16_t* iq, size_t n, OpvSrc kind, int device, 
     return 0;
 }
 
+// ---- a TYPED block (include/opv_demod.h: cs8, cu8, cf32) for the same objects: it is converted to int16 INTO the object's stage
+// and the push goes on as a device-pointer push from there; the bank kernels never see a format.
+// k_push_convert for one block (opv_push.hip): n samples of `fmt` at d_src (device-visible, aligned for the format) to int16 at
+// d_dst, enqueued on `on`; grid_cap: the small grid of the gather kernel where d_src lies across the link
+int opv_int_convert_launch(int fmt, const void* d_src, int16_t* d_dst, size_t n, hipStream_t on, uint32_t grid_cap);
+// the device-visible address of a block in pinned host memory of `device`; nullptr for pageable memory and for pinned memory that
+// belongs to ANOTHER device's context (whether this device may read that in a kernel depends on how it was allocated, and a wrong
+// guess is a page fault, not an error code)
+inline const void* opv_int_pinned_view(const void* p, int device) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) == hipSuccess && at.type == hipMemoryTypeHost && at.devicePointer && at.device == device) return at.devicePointer;
+    (void)hipGetLastError();                                            // (pageable memory: "invalid value" - not an error of ours)
+    return nullptr;
+}
+struct OpvTypedSrc {
+    const void* d_raw = nullptr;  // what the convert kernel reads: the caller's pinned block in place, or its raw copy in the stage
+    bool copy_raw = false;        // pageable: the raw bytes are copied behind the converted samples' place first
+    size_t raw_bytes = 0;
+};
+// The stage grown (as opv_int_source grows it) to n converted samples and, for a pageable source, the raw block behind them.
+// Nothing is enqueued here, and nothing of the object's state changes; sample_bytes: include/opv_demod.h's opv_iq_sample_bytes(fmt).
+inline int opv_int_source_fmt(const void* in, size_t n, size_t sample_bytes, int device, hipStream_t copy_stream, OpvStage* stage,
+                              OpvTypedSrc* out) {
+    out->raw_bytes = n * sample_bytes;
+    size_t need = n;                                                    // (OpvStage counts in samples of 4 bytes)
+    out->d_raw = opv_int_pinned_view(in, device);
+    if (!out->d_raw) {
+        out->copy_raw = true;
+        need = ((n + 3) & ~(size_t)3) + (out->raw_bytes + 3) / 4;       // the raw copy starts on a 16-byte boundary
+    }
+    if (stage->cap < need) {
+        HIPCHK(hipStreamSynchronize(copy_stream));
+        if (stage->d) HIPCHK(hipFree(stage->d));
+        stage->d = nullptr;
+        stage->cap = 0;
+        HIPCHK(hipMalloc(&stage->d, need * 4));
+        stage->cap = need;
+    }
+    if (out->copy_raw) out->d_raw = stage->d + ((n + 3) & ~(size_t)3);
+    return 0;
+}
+// ... and the block on its way, on the copy stream in front of the object's own launch: stage->d then holds n int16 samples
+inline int opv_int_convert_enqueue(const void* in, size_t n, int fmt, const OpvTypedSrc& t, OpvStage* stage, hipStream_t copy_stream) {
+    if (t.copy_raw) HIPCHK(hipMemcpyAsync((void*)t.d_raw, in, t.raw_bytes, hipMemcpyHostToDevice, copy_stream));
+    return opv_int_convert_launch(fmt, t.d_raw, (int16_t*)stage->d, n, copy_stream, t.copy_raw ? 2048u : 32u);
+}
+
 // What a context and its wideband objects share, and what outlives whichever of them goes first: a wideband object destroyed
 // (or used) after its context finds ctx_alive false and touches nothing of the context.
 struct OpvWbShared {

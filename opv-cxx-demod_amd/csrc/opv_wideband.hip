@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/opv_demod.h"
+#include "opv_iq_format.h"
 #include "opv_wb_internal.h"
 #include "opv_wb_rules.h"
 
@@ -191,13 +192,17 @@ namespace {
 
 using Src = OpvSrc;
 
-int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
+// fmt != OPV_IQ_CS16 (a host block in another format): converted into the object's stage on the copy stream, then as a device push
+int wb_push(opv_wb* w, const void* iq, size_t n_new, Src kind, bool wait, int fmt = OPV_IQ_CS16) {
     if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null object");
     if (!w->door.shared->ctx_alive) return opv_int_fail(OPV_ESTATE, "opv_wb_push: the object's context has been destroyed");
     if (int r = opv_int_push_begin(w->ctx)) return r;
     if (n_new == 0) return OPV_OK;
     if (!iq) return opv_int_fail(OPV_EINVAL, "opv_wb_push: null IQ pointer");
-    if (((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_wb_push: IQ pointer must be 4-byte aligned");
+    const bool typed = fmt != OPV_IQ_CS16;
+    if (typed && ((uintptr_t)iq & (opv_iq_align_of(fmt) - 1)) != 0)
+        return opv_int_fail(OPV_EINVAL, "opv_wb_push_fmt: the block is not aligned for its format (2 bytes for cs8 / cu8, 4 for cf32)");
+    if (!typed && ((uintptr_t)iq & 3u) != 0) return opv_int_fail(OPV_EINVAL, "opv_wb_push: IQ pointer must be 4-byte aligned");
     if (n_new >= (1ull << 31)) return opv_int_fail(OPV_EINVAL, "opv_wb_push: more than 2^31 - 1 samples in one push");
     const uint32_t K = w->K;
     const bool rational = w->kind == WbKind::Rational;
@@ -218,7 +223,13 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     // ---- the source as the device sees it (a staging buffer grown at most so far: nothing enqueued, nothing of the object's state changed)
     const int* src = nullptr;
     bool stage = false;
-    if (int r = opv_int_source(iq, n_new, kind, w->door.device, w->door.copy_stream, &w->stage, &src, &stage)) return r;
+    OpvTypedSrc tsrc;
+    if (typed) {
+        if (int r = opv_int_source_fmt(iq, n_new, opv_iq_bytes_of(fmt), w->door.device, w->door.copy_stream, &w->stage, &tsrc)) return r;
+        src = w->stage.d;
+    } else if (int r = opv_int_source((const int16_t*)iq, n_new, kind, w->door.device, w->door.copy_stream, &w->stage, &src, &stage)) {
+        return r;
+    }
     // ---- this push's destination table: a slot of the pinned ring, free once the launch that read it last has finished
     const unsigned slot = w->pushes % kTabSlots;
     if (w->tab_ev[slot]) HIPCHK(hipEventSynchronize(w->tab_ev[slot]));
@@ -228,6 +239,8 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
     std::vector<int*> dst(K);
     if (int r = opv_int_push_reserve(w->ctx, (int)K, w->streams.data(), counts.data(), dst.data())) return r;
     if (stage) HIPCHK(hipMemcpyAsync(w->stage.d, iq, n_new * 4, hipMemcpyHostToDevice, w->door.copy_stream));
+    if (typed)
+        if (int r = opv_int_convert_enqueue(iq, n_new, fmt, tsrc, &w->stage, w->door.copy_stream)) return r;
     int** tab = w->h_tab + (size_t)slot * K;
     std::memcpy(tab, dst.data(), (size_t)K * sizeof(int*));
     void* d_tab = nullptr;
@@ -293,6 +306,13 @@ int wb_push(opv_wb* w, const int16_t* iq, size_t n_new, Src kind, bool wait) {
 extern "C" int opv_wb_push(opv_wb* w, const int16_t* iq_wide, size_t n_wide) { return wb_push(w, iq_wide, n_wide, Src::Host, true); }
 extern "C" int opv_wb_push_async(opv_wb* w, const int16_t* iq_wide, size_t n_wide) { return wb_push(w, iq_wide, n_wide, Src::Host, false); }
 extern "C" int opv_wb_push_device(opv_wb* w, const int16_t* d_iq_wide, size_t n_wide) { return wb_push(w, d_iq_wide, n_wide, Src::Device, true); }
+
+static int wb_push_fmt(opv_wb* w, int fmt, const void* wide, size_t n_wide, bool wait) {
+    if (!opv_iq_align_of(fmt)) return opv_int_fail(OPV_EINVAL, "opv_wb_push_fmt: unknown sample format");
+    return wb_push(w, wide, n_wide, Src::Host, wait, fmt);
+}
+extern "C" int opv_wb_push_fmt(opv_wb* w, int fmt, const void* wide, size_t n_wide) { return wb_push_fmt(w, fmt, wide, n_wide, true); }
+extern "C" int opv_wb_push_fmt_async(opv_wb* w, int fmt, const void* wide, size_t n_wide) { return wb_push_fmt(w, fmt, wide, n_wide, false); }
 
 extern "C" int opv_wb_flush(opv_wb* w) {
     if (!w) return opv_int_fail(OPV_EINVAL, "opv_wb_flush: null object");

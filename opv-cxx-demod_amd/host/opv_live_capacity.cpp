@@ -8,7 +8,11 @@
 // largest N whose p99 stays under 40 ms (extras.live_capacity). No kernel is specific to this tool: it is a caller of
 // include/opv_demod.h like opv-rx-bridge, without sockets so that the number is the library's.
 //
-//   opv-live-capacity <n_streams> [rounds (120)] [warmup (6)] [device (0)] [--pipelined | --wideband K]
+//   opv-live-capacity <n_streams> [rounds (120)] [warmup (6)] [device (0)] [--pipelined | --wideband K] [--format cs16|cs8|cu8|cf32]
+//     --format F    (anywhere on the line) the same signal as a radio of format F would deliver it: quantised on the host, before the
+//                   timed rounds, by the inverse of opv_iq_convert, and pushed typed (opv_push_iq_batch_fmt(_async), opv_wb_push_fmt_async):
+//                   cs8 / cu8 cross PCIe at half the bytes of int16, cf32 at twice, and are widened on the device. The line
+//                   printed then carries "format" and pcie_GBps counts the bytes of that format. Without it: the int16 calls.
 //     --pipelined   the double-buffered server: opv_push_iq_batch_async of round r + 1 is enqueued right behind opv_process of
 //                   round r, so the chunks of the next round cross PCIe while this round's kernels run and its frames are
 //                   popped; a round then costs max(PCIe, kernels + pops). Reported per round: the time from one opv_push_wait
@@ -44,6 +48,31 @@ int main(int argc, char** argv) {
         fprintf(stderr, "Usage: %s <n_streams> [rounds] [warmup] [device]\n", argv[0]);
         return 2;
     }
+    int fmt = -1;                                       // --format F: taken out of the line first; what follows parses as it always did
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--format")) {
+            const char* names[] = {"cs16", "cs8", "cu8", "cf32"};
+            for (int f = 0; f < 4; ++f)
+                if (!strcmp(argv[i + 1], names[f])) fmt = f;
+            if (fmt < 0) { fprintf(stderr, "opv-live-capacity: --format takes cs16, cs8, cu8 or cf32\n"); return 2; }
+            for (int j = i; j + 2 < argc; ++j) argv[j] = argv[j + 2];
+            argc -= 2;
+            break;
+        }
+    const bool typed = fmt > OPV_IQ_CS16;
+    const size_t bps = typed ? opv_iq_sample_bytes(fmt) : 4;
+    // n int16 samples as a radio of the format would have delivered them, in pinned memory (the inverse of opv_iq_convert's rule)
+    auto quantised = [&](const int16_t* src, size_t n) -> unsigned char* {
+        unsigned char* q = nullptr;
+        if (hipHostMalloc((void**)&q, n * bps, hipHostMallocDefault) != hipSuccess) return nullptr;
+        for (size_t i = 0; i < 2 * n; ++i) {
+            const double v = src[i];
+            if (fmt == OPV_IQ_CS8) ((int8_t*)q)[i] = (int8_t)std::min(127l, std::max(-128l, lrint(v / 256.0)));
+            else if (fmt == OPV_IQ_CU8) q[i] = (uint8_t)std::min(255l, std::max(0l, lrint((v / 128.0 + 255.0) / 2.0)));
+            else ((float*)q)[i] = (float)(v / 32767.0);
+        }
+        return q;
+    };
     bool pipelined = false;
     int K = 0;                                          // --wideband K: streams per wide capture (0: one block per stream)
     if (argc > 2 && !strcmp(argv[argc - 1], "--pipelined")) { pipelined = true; --argc; }
@@ -121,6 +150,9 @@ int main(int argc, char** argv) {
             wbs.push_back(w);
         }
     }
+    unsigned char* tq = nullptr;                        // --format: what is pushed instead of iq / wide
+    if (typed && !(tq = quantised(K ? wide : iq, K ? ((size_t)G + (size_t)total) * chunk : n_all))) { fprintf(stderr, "opv-live-capacity: no pinned host memory\n"); return 2; }
+    std::vector<const void*> tptrs(N);
     std::vector<int> ids(N);
     std::vector<const int16_t*> ptrs(N);
     std::vector<size_t> lens(N, chunk);
@@ -132,11 +164,20 @@ int main(int argc, char** argv) {
     std::vector<size_t> next(N, 0);                     // per stream: the number of the next frame it owes
     using clk = std::chrono::steady_clock;
     auto ms = [](clk::time_point a, clk::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    auto set_ptrs = [&](int r) { for (int k = 0; k < N; ++k) ptrs[k] = iq + 2 * ((size_t)r + (size_t)k) * chunk; };   // stream k is k frames into the run
+    auto set_ptrs = [&](int r) {                        // stream k is k frames into the run
+        for (int k = 0; k < N; ++k) {
+            ptrs[k] = iq + 2 * ((size_t)r + (size_t)k) * chunk;
+            if (typed) tptrs[k] = tq + bps * ((size_t)r + (size_t)k) * chunk;
+        }
+    };
     auto push_async = [&](int r) -> int {               // round r's samples, enqueued: one block per stream, or one wide capture per K streams
-        if (!K) { set_ptrs(r); return opv_push_iq_batch_async(ctx, N, ids.data(), ptrs.data(), lens.data()); }
+        if (!K) {
+            set_ptrs(r);
+            return typed ? opv_push_iq_batch_fmt_async(ctx, fmt, N, ids.data(), tptrs.data(), lens.data()) : opv_push_iq_batch_async(ctx, N, ids.data(), ptrs.data(), lens.data());
+        }
         for (int g = 0; g < G; ++g)
-            if (int rc = opv_wb_push_async(wbs[g], wide + 2 * ((size_t)r + (size_t)g) * chunk, chunk)) return rc;
+            if (int rc = typed ? opv_wb_push_fmt_async(wbs[g], fmt, tq + bps * ((size_t)r + (size_t)g) * chunk, chunk)
+                               : opv_wb_push_async(wbs[g], wide + 2 * ((size_t)r + (size_t)g) * chunk, chunk)) return rc;
         return 0;
     };
     if (pipelined) {
@@ -148,7 +189,7 @@ int main(int argc, char** argv) {
             if (opv_push_wait(ctx) < 0) { fprintf(stderr, "push wait: %s\n", opv_last_error()); return 2; }   // round r's chunks have landed
         } else {
             set_ptrs(r);
-            if (opv_push_iq_batch(ctx, N, ids.data(), ptrs.data(), lens.data()) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
+            if ((typed ? opv_push_iq_batch_fmt(ctx, fmt, N, ids.data(), tptrs.data(), lens.data()) : opv_push_iq_batch(ctx, N, ids.data(), ptrs.data(), lens.data())) < 0) { fprintf(stderr, "push: %s\n", opv_last_error()); return 2; }
         }
         const auto t1 = clk::now();
         if (opv_process(ctx) < 0) { fprintf(stderr, "process: %s\n", opv_last_error()); return 2; }
@@ -187,14 +228,18 @@ int main(int argc, char** argv) {
         const size_t i = (size_t)(p * (double)(v.size() - 1) + 0.5);
         return v[i < v.size() ? i : v.size() - 1];
     };
-    printf("{\"streams\": %d, \"wideband\": %d, \"pipelined\": %s, \"rounds\": %d, \"signal_ms_per_round\": 40.0, \"round_ms_p50\": %.3f, \"round_ms_p99\": %.3f, \"round_ms_max\": %.3f, "
+    const char* fmt_names[] = {"cs16", "cs8", "cu8", "cf32"};
+    if (fmt >= 0) printf("{\"format\": \"%s\", ", fmt_names[fmt]);
+    else printf("{");
+    printf("\"streams\": %d, \"wideband\": %d, \"pipelined\": %s, \"rounds\": %d, \"signal_ms_per_round\": 40.0, \"round_ms_p50\": %.3f, \"round_ms_p99\": %.3f, \"round_ms_max\": %.3f, "
            "\"push_ms_p50\": %.3f, \"process_ms_p50\": %.3f, \"pop_ms_p50\": %.3f, \"pcie_GBps_p50\": %.2f, \"frames_released\": %ld, "
            "\"frames_wrong\": %ld, \"frames_imperfect\": %ld, \"rounds_not_one_frame_per_stream\": %ld, \"process_call_ms_p50\": %.3f, \"async_enqueue_ms_p50\": %.3f}\n",
            N, K, pipelined ? "true" : "false", rounds, pct(t_round, 0.5), pct(t_round, 0.99), pct(t_round, 1.0), pct(t_push, 0.5), pct(t_proc, 0.5), pct(t_pop, 0.5),
            // serial: the moves alone; pipelined: push_ms is only the wait for moves that ran beside the previous round - the rate over the period
-           (double)(K ? G : N) * chunk * 4 / (pct(pipelined ? t_round : t_push, 0.5) * 1e-3) / 1e9, released, wrong, imperfect, uneven, pct(t_launch, 0.5), pct(t_enq, 0.5));
+           (double)(K ? G : N) * chunk * bps / (pct(pipelined ? t_round : t_push, 0.5) * 1e-3) / 1e9, released, wrong, imperfect, uneven, pct(t_launch, 0.5), pct(t_enq, 0.5));
     for (opv_wb* w : wbs) opv_wb_destroy(w);
     opv_destroy(ctx);
+    if (tq) (void)hipHostFree(tq);
     if (wide) (void)hipHostFree(wide);
     (void)hipHostFree(iq);
     return wrong ? 1 : 0;

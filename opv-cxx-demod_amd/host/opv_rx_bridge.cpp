@@ -9,13 +9,15 @@
 // one-frame latency (a frame is released once 50 samples of the next one have arrived,
 // src/opv-demod.cpp:221) is unchanged.
 //
-//   opv-rx-bridge [-H host] [-P base_port] [-o hz] [-a alpha] [--device n | --devices a,b,...] [--gather] [-q] [input ...]
+//   opv-rx-bridge [-H host] [-P base_port] [-o hz] [-a alpha] [--format cs16|cs8|cu8|cf32] [--device n | --devices a,b,...] [--gather] [-q] [input ...]
+//     --format F         the sample format of ALL inputs (default cs16: int16 I/Q). cs8 / cu8 / cf32 are pushed as they arrive
+//                        (opv_push_iq_batch_fmt) and widened on the device: `rtl_sdr - | opv-rx-bridge --format cu8 -`
 //     --devices a,b,...  one context per listed GPU, the inputs sharded contiguously over them (stream k -> entry
 //                        k / ceil(S / N) of the list; BASELINE configs[4]'s layout in one C++ process); UDP output unchanged
 //     --gather           at the end, the decoded-frame buffers and counts of every context are gathered to the first
 //                        listed GPU with ONE RCCL gather (opv_gather_frames_all, ncclGather) and compared with what was sent
 //     inputs, one stream each ("N stdin/UDP sources"):
-//       PATH      file or FIFO with int16 I/Q
+//       PATH      file or FIFO with I/Q samples of --format (int16 by default)
 //       -         stdin (also the only stream when no input is named, like `opv-modem -R`)
 //       udp:PORT  IQ bytes arriving as UDP datagrams on 127.0.0.1:PORT (what a network SDR front-end sends);
 //                 a zero-length datagram ends the stream
@@ -37,11 +39,17 @@
 
 #include "../../include/opv_demod.h"
 
+// The typed pushes are additive within ABI 7: a library of the same ABI that predates them does not have these two names. The
+// bridge refers to them weakly, so that it still starts against such a library and refuses --format there in words, where a
+// strong reference would keep the loader from starting it at all - for int16 inputs too.
+extern "C" int opv_push_iq_batch_fmt(opv_ctx*, int, int, const int*, const void* const*, const size_t*) __attribute__((weak));
+extern "C" size_t opv_iq_sample_bytes(int) __attribute__((weak));
+
 namespace {
 struct Input {
     int fd = -1;
     bool eof = false, udp = false;
-    unsigned char carry[4];
+    unsigned char carry[8];   // a split sample: less than one of the widest format (cf32)
     size_t ncarry = 0;
     long frames = 0, perfect = 0;
     uint64_t samples = 0;
@@ -56,13 +64,21 @@ int main(int argc, char** argv) {
     int device = 0;
     std::vector<int> devices;
     bool gather = false;
+    int fmt = OPV_IQ_CS16;
     std::vector<std::string> paths;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-H") && i + 1 < argc) host = argv[++i];
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) base_port = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-o") && i + 1 < argc) { off = atof(argv[++i]); have_off = true; }
         else if (!strcmp(argv[i], "-a") && i + 1 < argc) afc = atof(argv[++i]);
-        else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--format") && i + 1 < argc) {
+            const char* names[] = {"cs16", "cs8", "cu8", "cf32"};
+            fmt = -1;
+            ++i;
+            for (int f = 0; f < 4; ++f)
+                if (!strcmp(argv[i], names[f])) fmt = f;
+            if (fmt < 0) { fprintf(stderr, "opv-rx-bridge: --format takes cs16, cs8, cu8 or cf32, got '%s'\n", argv[i]); return 2; }
+        } else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
             for (const char* p = argv[++i]; *p;) {
                 char* end = nullptr;
@@ -78,9 +94,13 @@ int main(int argc, char** argv) {
         } else if (!strcmp(argv[i], "--gather")) gather = true;
         else if (!strcmp(argv[i], "-q")) quiet = true;
         else if (!strcmp(argv[i], "-h")) {
-            fprintf(stderr, "Usage: %s [-H host] [-P base_port] [-o hz] [-a alpha] [--device n | --devices a,b,...] [--gather] [-q] [input ...]\n", argv[0]);
+            fprintf(stderr, "Usage: %s [-H host] [-P base_port] [-o hz] [-a alpha] [--format cs16|cs8|cu8|cf32] [--device n | --devices a,b,...] [--gather] [-q] [input ...]\n", argv[0]);
             return 0;
         } else paths.push_back(argv[i]);
+    }
+    if (fmt != OPV_IQ_CS16 && (!opv_push_iq_batch_fmt || !opv_iq_sample_bytes)) {
+        fprintf(stderr, "opv-rx-bridge: --format: this build of the library has no typed pushes (opv_push_iq_batch_fmt); int16 inputs only\n");
+        return 2;
     }
     const int S = paths.empty() ? 1 : (int)paths.size();
     if (base_port < 1 || base_port + S - 1 > 65535) {
@@ -151,7 +171,8 @@ int main(int argc, char** argv) {
     if (!bufs) { fprintf(stderr, "opv-rx-bridge: out of host memory\n"); return 2; }
     std::vector<int> pending_flush;
     std::vector<std::vector<int>> ids(D);
-    std::vector<std::vector<const int16_t*>> ptrs(D);
+    std::vector<std::vector<const void*>> ptrs(D);
+    const size_t bps = fmt == OPV_IQ_CS16 ? 4 : opv_iq_sample_bytes(fmt);   // bytes per sample of the inputs' format
     std::vector<std::vector<size_t>> lens(D);
     uint8_t frames[64 * OPV_FRAME_BYTES];
     opv_frame_meta meta[64];
@@ -193,11 +214,11 @@ int main(int argc, char** argv) {
                 if (r == 0) { ended = true; break; }      // EOF / the empty datagram that ends a UDP stream
                 have += (size_t)r;
             }
-            const size_t ns = have / 4;
-            if (ns) { ids[k / per].push_back(k % per); ptrs[k / per].push_back(reinterpret_cast<const int16_t*>(buf)); lens[k / per].push_back(ns); any = true; }
+            const size_t ns = have / bps;
+            if (ns) { ids[k / per].push_back(k % per); ptrs[k / per].push_back(buf); lens[k / per].push_back(ns); any = true; }
             in[k].samples += ns;
-            in[k].ncarry = have - ns * 4;
-            memcpy(in[k].carry, buf + ns * 4, in[k].ncarry);
+            in[k].ncarry = have - ns * bps;
+            memcpy(in[k].carry, buf + ns * bps, in[k].ncarry);
             if (ended) {
                 in[k].eof = true;
                 --open_streams;
@@ -206,7 +227,8 @@ int main(int argc, char** argv) {
             }
         }
         for (int d = 0; d < D; ++d)
-            if (!ids[d].empty() && opv_push_iq_batch(ctxs[d], (int)ids[d].size(), ids[d].data(), ptrs[d].data(), lens[d].data()) < 0) {
+            if (!ids[d].empty() && (fmt == OPV_IQ_CS16 ? opv_push_iq_batch(ctxs[d], (int)ids[d].size(), ids[d].data(), (const int16_t* const*)ptrs[d].data(), lens[d].data())
+                                                       : opv_push_iq_batch_fmt(ctxs[d], fmt, (int)ids[d].size(), ids[d].data(), ptrs[d].data(), lens[d].data())) < 0) {
                 fprintf(stderr, "opv-rx-bridge: %s\n", opv_last_error());
                 return 2;
             }

@@ -50,7 +50,20 @@ EXPORTS = [
     "opv_div_tap_payload", "opv_div_match", "opv_div_earliest",
     "opv_scan_plan", "opv_scan_blocks", "opv_scan_create", "opv_scan_destroy", "opv_scan_push", "opv_scan_push_device", "opv_scan_pop",
     "opv_scan_reset", "opv_scan_carriers",
+    "opv_push_iq_fmt", "opv_push_iq_batch_fmt", "opv_push_iq_batch_fmt_async", "opv_wb_push_fmt", "opv_wb_push_fmt_async", "opv_scan_push_fmt",
+    "opv_convert_iq_device", "opv_iq_convert", "opv_iq_sample_bytes",
 ]
+
+# typed IQ pushes (include/opv_demod.h, OPV_IQ_*): name -> (format code, numpy type of one component)
+IQ_FORMATS = {"cs16": (0, np.int16), "cs8": (1, np.int8), "cu8": (2, np.uint8), "cf32": (3, np.float32)}
+
+
+def _iq_block(fmt, block):
+    """(format code, the block as a flat contiguous array of the format's component type - no copy if it is one already)"""
+    if fmt not in IQ_FORMATS:
+        raise OpvError(f"unknown sample format {fmt!r} (one of {', '.join(IQ_FORMATS)})")
+    code, dtype = IQ_FORMATS[fmt]
+    return code, np.ascontiguousarray(block, dtype).reshape(-1)
 
 
 class OpvError(RuntimeError):
@@ -359,6 +372,16 @@ def lib():
         L.opv_scan_reset.argtypes = [C.c_void_p, C.c_uint64]
         L.opv_scan_carriers.restype = C.c_long
         L.opv_scan_carriers.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.opv_push_iq_fmt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        L.opv_push_iq_batch_fmt.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_push_iq_batch_fmt_async.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.opv_wb_push_fmt.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.opv_wb_push_fmt_async.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.opv_scan_push_fmt.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.opv_convert_iq_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_iq_convert.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.opv_iq_sample_bytes.restype = C.c_size_t
+        L.opv_iq_sample_bytes.argtypes = [C.c_int]
         _lib = L
     return _lib
 
@@ -367,6 +390,15 @@ def _chk(rc):
     if rc < 0:
         raise OpvError(f"opv error {rc}: {lib().opv_last_error().decode()}")
     return rc
+
+
+def iq_convert(fmt, array):
+    """opv_iq_convert: a block of `fmt` ("cs16", "cs8", "cu8", "cf32"; interleaved I, Q) as the int16 a typed push makes of it; host
+    only, needs no device"""
+    code, a = _iq_block(fmt, array)
+    out = np.empty(a.size, np.int16)
+    _chk(lib().opv_iq_convert(code, a.ctypes.data, out.ctypes.data, a.size // 2))
+    return out
 
 
 def comm_create(world, rank, device=0, uid=None):
@@ -767,13 +799,23 @@ class Wideband:
         self._inflight = []
         demod._wideband.add(self)
 
-    def push(self, iq_wide):
+    def push(self, iq_wide, fmt="cs16"):
+        """opv_wb_push; fmt other than "cs16": opv_wb_push_fmt, the block in the radio's own format"""
+        if fmt != "cs16":
+            code, iq = _iq_block(fmt, iq_wide)
+            _chk(lib().opv_wb_push_fmt(self.h, code, iq.ctypes.data, iq.size // 2))
+            return
         iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
         _chk(lib().opv_wb_push(self.h, iq.ctypes.data, iq.size // 2))
 
-    def push_async(self, iq_wide):
+    def push_async(self, iq_wide, fmt="cs16"):
         """opv_wb_push_async: the block must stay alive and unchanged until demod.push_wait(). Several pushes may be in flight, so
-        every block (or the copy made of it) is kept referenced here until then."""
+        every block (or the copy made of it) is kept referenced here until then. fmt other than "cs16": opv_wb_push_fmt_async."""
+        if fmt != "cs16":
+            code, iq = _iq_block(fmt, iq_wide)
+            self._inflight.append(iq)
+            _chk(lib().opv_wb_push_fmt_async(self.h, code, iq.ctypes.data, iq.size // 2))
+            return
         iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
         self._inflight.append(iq)
         _chk(lib().opv_wb_push_async(self.h, iq.ctypes.data, iq.size // 2))
@@ -847,7 +889,12 @@ class Scan:
         self.h = C.c_void_p()
         _chk(lib().opv_scan_create(C.byref(self.h), demod.h, C.byref(self.cfg), probes.ctypes.data, window.ctypes.data))
 
-    def push(self, iq_wide):
+    def push(self, iq_wide, fmt="cs16"):
+        """opv_scan_push; fmt other than "cs16": opv_scan_push_fmt"""
+        if fmt != "cs16":
+            code, iq = _iq_block(fmt, iq_wide)
+            _chk(lib().opv_scan_push_fmt(self.h, code, iq.ctypes.data, iq.size // 2))
+            return
         iq = np.ascontiguousarray(iq_wide, np.int16).reshape(-1)
         _chk(lib().opv_scan_push(self.h, iq.ctypes.data, iq.size // 2))
 
@@ -980,25 +1027,38 @@ class Demod:
         except Exception:  # interpreter shutdown: module globals may already be gone
             pass
 
-    def push(self, stream, iq):
+    def push(self, stream, iq, fmt="cs16"):
+        """opv_push_iq; fmt other than "cs16" ("cs8", "cu8", "cf32"): opv_push_iq_fmt, the block in the radio's own format"""
+        if fmt != "cs16":
+            code, a = _iq_block(fmt, iq)
+            _chk(lib().opv_push_iq_fmt(self.h, stream, code, a.ctypes.data, a.size // 2))
+            return
         iq = np.ascontiguousarray(iq, np.int16).reshape(-1)
         _chk(lib().opv_push_iq(self.h, stream, iq.ctypes.data, iq.size // 2))
 
-    def push_batch(self, streams, blocks, wait=True):
+    def push_batch(self, streams, blocks, wait=True, fmt="cs16"):
         """opv_push_iq_batch: blocks[i] (int16 IQ) goes to streams[i]; one wait for all copies. wait=False:
-        opv_push_iq_batch_async - the blocks must stay alive and unchanged until push_wait() (they are kept referenced here)."""
-        blocks = [np.ascontiguousarray(b, np.int16).reshape(-1) for b in blocks]
+        opv_push_iq_batch_async - the blocks must stay alive and unchanged until push_wait() (they are kept referenced here).
+        fmt other than "cs16": opv_push_iq_batch_fmt(_async), every block in that one format."""
+        code, _ = IQ_FORMATS["cs16"] if fmt == "cs16" else _iq_block(fmt, [])
+        blocks = [_iq_block(fmt, b)[1] for b in blocks]
         n = len(blocks)
         ids = (C.c_int * n)(*[int(s) for s in streams])
         ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in blocks])
         lens = (C.c_size_t * n)(*[b.size // 2 for b in blocks])
+        typed = fmt != "cs16"
         if wait:
-            _chk(lib().opv_push_iq_batch(self.h, n, ids, ptrs, lens))
+            _chk(lib().opv_push_iq_batch_fmt(self.h, code, n, ids, ptrs, lens) if typed else lib().opv_push_iq_batch(self.h, n, ids, ptrs, lens))
         else:
             held = getattr(self, "_inflight", None)        # the previous batch's blocks stay referenced until the call has waited for them
-            _chk(lib().opv_push_iq_batch_async(self.h, n, ids, ptrs, lens))
+            _chk(lib().opv_push_iq_batch_fmt_async(self.h, code, n, ids, ptrs, lens) if typed else lib().opv_push_iq_batch_async(self.h, n, ids, ptrs, lens))
             self._inflight = blocks
             del held
+
+    def convert_device(self, fmt, d_in, d_out, n_samples):
+        """opv_convert_iq_device: n_samples of `fmt` at device address d_in to int16 at d_out, on the context's stream"""
+        code, _ = _iq_block(fmt, [])
+        _chk(lib().opv_convert_iq_device(self.h, code, C.c_void_p(d_in), C.c_void_p(d_out), int(n_samples)))
 
     def push_wait(self):
         _chk(lib().opv_push_wait(self.h))
